@@ -31,11 +31,16 @@ with a replica check: the ranks' parameter buffers must be bit-identical.
 Data dependence: project-then-gather's work follows the DISTINCT tokens of a batch.
 `--doc-fill full` (no zero padding) and `--token-dist uniform` (no Zipf head) are the
 unfriendly points; the value line always uses the SURVEY 8d defaults.
+
+`--dump-outputs DIR` writes what the last timed step computed -- its per-rating prediction and squared error, and every
+parameter after its update (a seeded sample of a large one), 64 MB at most -- as DIR/<name>.npy.  The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -162,6 +167,9 @@ def parse():
     ap.add_argument('--engine', choices=['native', 'module', 'graph'], default='native',
                     help="native: fused r4r_deepconn_step where the model has one (else module); module: op-by-op "
                          "autograd path; graph: the module path captured into one hipGraph per step")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed (per-rating prediction and SE, '
+                         'every parameter after its update) as DIR/<name>.npy: two builds compared output for output')
     return ap.parse_args()
 
 
@@ -175,6 +183,53 @@ def blocked_sweep_leg(leg, engine, traffic, avg_s):
     leg['hbm_side_GBs'] = None if traffic is None else round(traffic / avg_s / 1e9, 1)
     leg['frac'] = None if traffic is None else round(traffic / avg_s / 1e9 / PEAK_HBM_GBS, 4)
     leg['blocked_sweep_period'] = engine.sweep_period        # (frac = counter bytes per launch / launch time / HBM peak: DESIGN 5)
+
+
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 18             # elements kept of a larger tensor (a fixed, seeded sample of its flattened elements)
+
+
+def last_step_arrays(model, engine, graphed, module_last, B):
+    """{name: tensor} of what the timed path's last step computed, as its caller receives it: the per-rating prediction
+    and squared error (the native engines' output buffers of a B-rating batch, which every step and span writes; the
+    captured graph's static SE; the module path's own tensors) and every parameter of the model after the step's
+    update."""
+    out = {}
+    if engine is not None:
+        bufs = getattr(engine, '_out', {}).get(B)
+        if isinstance(bufs, tuple) and len(bufs) == 2:
+            out['pred'], out['se'] = bufs
+        else:
+            print('bench: --dump-outputs: this engine keeps no (pred, se) buffers of %d ratings; parameters only' % B,
+                  file=sys.stderr)
+    elif graphed is not None:
+        out['se'] = graphed.graph_se
+    else:
+        out.update(module_last)
+    for name, p in model.named_parameters():
+        out['param.' + name] = p
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of `arrays` as out_dir/<name>.npy, float64 where the tensor is, float32 otherwise.  A
+    tensor of more elements than its share of DUMP_BUDGET_BYTES (at most DUMP_SAMPLE) is written as a sample of its
+    flattened elements at positions drawn from a fixed seed: the same positions on every run.  -> bytes written"""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_SAMPLE, (DUMP_BUDGET_BYTES // max(1, len(arrays)) - 256) // 8)   # (256 B: the .npy header)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.cpu().numpy()
+        else:
+            a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+    return total
 
 
 def tower_flops_per_doc(hp):
@@ -470,9 +525,10 @@ def make_engine(args, hp, model, dp, rank, world, B):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` with no launcher around it (no RANK / WORLD_SIZE in the environment): replace this
-    process by the N-rank job the driver would have started -- torch.distributed.run, one rank per GPU, static
-    rendezvous on 127.0.0.1 -- so that the bare command is a complete N-GPU run (rank 0 prints the one JSON line).
+    """`python bench.py --gpus N` with no launcher around it (no RANK / WORLD_SIZE in the environment): run the N-rank
+    job the driver would have started -- torch.distributed.run, one rank per GPU, static rendezvous on 127.0.0.1 -- as a
+    child process and exit with its status, so that the bare command is a complete N-GPU run (rank 0 prints the one JSON
+    line).  A child, not an exec: the device count below may already have brought the HIP runtime up in this process.
     The reference side of this is the single-process loop main.py:401-431; data parallelism is new work."""
     if args.gpus <= 1 or 'WORLD_SIZE' in os.environ or 'RANK' in os.environ:
         return
@@ -487,7 +543,7 @@ def self_launch(args):
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def check_device_count(n):
@@ -607,6 +663,7 @@ def run(args, env, is_leg=False):
     exchange_ms = engine.autotune_exchange() if (engine is not None and dp_job
                                                  and hasattr(engine, 'autotune_exchange')) else {}
 
+    module_last = {}                                         # the module path's last step: {'pred', 'se'} (--dump-outputs)
     graphed = None
     if args.engine == 'graph':
         if dp_job:
@@ -644,6 +701,7 @@ def run(args, env, is_leg=False):
                 optimizer[0].step()
                 se = criterion(out[0], y, return_mean=False)
                 metric_sum.add_(se.detach().sum())
+                module_last.update(pred=out[0].detach(), se=se.detach())
                 torch.mean(se).backward()
                 optimizer[1].step()
                 return
@@ -651,6 +709,7 @@ def run(args, env, is_leg=False):
             out = model(data)
             se = criterion(out, y, return_mean=False)
             metric_sum.add_(se.detach().sum())
+            module_last.update(pred=out.detach(), se=se.detach())
             (se.sum() * dp.loss_scale(b, b_global)).backward()
             dp.allreduce_grads()
             optimizer.step()
@@ -807,6 +866,9 @@ def run(args, env, is_leg=False):
     elapsed = timed_region(step, args.steps, ramp + args.warmup, mask)
     if hasattr(engine, 'check_announcements'):               # (outside the region: one int read back from the device)
         engine.check_announcements()
+    if args.dump_outputs and not is_leg and rank == 0:       # (before the steady / opt-in legs train the model further)
+        nbytes = dump_outputs(args.dump_outputs, last_step_arrays(model, engine, graphed, module_last, B))
+        print('bench: --dump-outputs: %d bytes under %s' % (nbytes, args.dump_outputs), file=sys.stderr)
     gpu_ms_per_step = gpu_span_ms[0] / args.steps
     steps_run = ramp + args.warmup + args.steps
     slots = {'textcnn_fwd_kernel': 0, 'textcnn_wgrad_kernel': 1, 'adam_multi_kernel': 2,

@@ -21,15 +21,17 @@ def _args(argv):
 
 
 def test_bare_multi_gpu_command_relaunches_itself_under_torch_distributed_run(monkeypatch):
-    """`python bench.py --gpus 2 ...` with no launcher: the process replaces itself by the N-rank job (one rank per GPU,
-    static rendezvous on 127.0.0.1), passing its own arguments through."""
+    """`python bench.py --gpus 2 ...` with no launcher: the process runs the N-rank job (one rank per GPU, static
+    rendezvous on 127.0.0.1) as its child, passing its own arguments through, and exits with the job's status."""
     seen = {}
     monkeypatch.delenv('WORLD_SIZE', raising=False)
     monkeypatch.delenv('RANK', raising=False)
     monkeypatch.setenv('R4R_DIST_BACKEND', 'gloo')           # (no GPU here: the device-count check is RCCL's)
-    monkeypatch.setattr(os, 'execv', lambda exe, cmd: seen.update(exe=exe, cmd=cmd))
+    monkeypatch.setattr(bench.subprocess, 'call', lambda cmd: seen.update(cmd=cmd) or 3)
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5'])
-    bench.self_launch(bench.parse())
+    with pytest.raises(SystemExit) as e:
+        bench.self_launch(bench.parse())
+    assert e.value.code == 3
     cmd = seen['cmd']
     assert cmd[:3] == [sys.executable, '-m', 'torch.distributed.run']
     assert '--nproc-per-node' in cmd and cmd[cmd.index('--nproc-per-node') + 1] == '2'
@@ -39,7 +41,7 @@ def test_bare_multi_gpu_command_relaunches_itself_under_torch_distributed_run(mo
 
 
 def test_no_relaunch_inside_a_launched_job_or_at_one_gpu(monkeypatch):
-    monkeypatch.setattr(os, 'execv', lambda *a: pytest.fail('re-launched'))
+    monkeypatch.setattr(bench.subprocess, 'call', lambda *a: pytest.fail('re-launched'))
     monkeypatch.setenv('WORLD_SIZE', '2')
     bench.self_launch(_args(['--gpus', '2']))
     monkeypatch.delenv('WORLD_SIZE')
@@ -101,3 +103,63 @@ def test_config_legs_ride_on_the_default_line_only():
     for want in ('cfg1_bias_only_musical', 'cfg2_mfdot_electronics', 'cfg2_mfdot_electronics_b8192', 'cfg4_narre_kindle',
                  'cfg5_transnetpp_synthetic', 'cfg3_full_uniform', 'cfg5_full_uniform_hbm_gather'):
         assert want in labels
+
+
+def test_dump_outputs_writes_every_array_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 where the tensor is), a large tensor as a sample of
+    its elements at positions drawn from a fixed seed -- the same positions on every run -- and 64 MB at most in all."""
+    import torch
+    assert _args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
+    assert _args([]).dump_outputs is None
+    g = torch.Generator().manual_seed(0)
+    arrays = {'pred': torch.randn(128, generator=g), 'se': torch.randn(128, generator=g, dtype=torch.float64),
+              'param.table': torch.randn(1000, 300, generator=g), 'param.ids': torch.arange(10)}
+    n1 = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    n2 = bench.dump_outputs(str(tmp_path / 'b'), arrays)
+    assert sorted(os.listdir(tmp_path / 'a')) == sorted(k + '.npy' for k in arrays) and n1 == n2
+    for k, t in arrays.items():
+        a, b = np.load(tmp_path / 'a' / (k + '.npy')), np.load(tmp_path / 'b' / (k + '.npy'))
+        assert a.dtype == (np.float64 if t.dtype == torch.float64 else np.float32) and np.array_equal(a, b)
+        if t.numel() <= bench.DUMP_SAMPLE:
+            assert a.shape == tuple(t.shape) and np.array_equal(a, t.numpy().astype(a.dtype))
+        else:
+            assert a.shape == (bench.DUMP_SAMPLE,) and np.isin(a, t.numpy().reshape(-1)).all()
+    # many large tensors: each one's share of the budget, 64 MB in all
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 1 << 20)
+    big = {'p%d' % i: torch.zeros(1 << 16, dtype=torch.float64) for i in range(40)}
+    bench.dump_outputs(str(tmp_path / 'c'), big)
+    assert sum(os.path.getsize(tmp_path / 'c' / f) for f in os.listdir(tmp_path / 'c')) <= 1 << 20
+
+
+def test_dump_outputs_of_the_module_path_are_the_last_steps_tensors():
+    import torch
+    model = torch.nn.Linear(3, 1)
+    last = {'pred': torch.ones(4), 'se': torch.zeros(4)}
+    got = bench.last_step_arrays(model, None, None, last, 4)
+    assert sorted(got) == ['param.bias', 'param.weight', 'pred', 'se'] and got['pred'] is last['pred']
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_with_the_same_arguments_agree(tmp_path):
+    """The flagship command with --dump-outputs, twice: the same inputs every run, so the same files -- the last timed
+    step's per-rating prediction and SE of the 128-rating batch and every parameter after its update."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'R4R_DP_SINGLE'):
+        env.pop(k, None)
+    got = []
+    for run in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--ramp', '0',
+               '--no-cpu-baseline', '--no-steady-leg', '--dump-outputs', str(tmp_path / run)]
+        out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 5 and line['ms_per_step'] > 0
+        got.append({f: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = got
+    assert sorted(a) == sorted(b) and a['pred.npy'].shape == a['se.npy'].shape == (128,)
+    assert any(f.startswith('param.') for f in a) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f

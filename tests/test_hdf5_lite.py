@@ -1,7 +1,7 @@
 """reviews4rec_amd.hdf5_lite -- the package's own reader of the reference's HDF5 epoch files
 (data_fast.py:31-45, data_scripts/make_quick_data.py:21-44) -- against files written by the REAL h5py / libhdf5
-(tests/golden/hdf5/, generator: tests/golden/make_golden_hdf5.py) and, where an interpreter with h5py exists
-(this container's /opt/conda/bin/python3.9; not the GPU box), against files it writes on the spot."""
+(tests/golden/hdf5/, generator: tests/golden/make_golden_hdf5.py), and its writer against the bytes h5py was seen to
+read there."""
 import os
 import shutil
 import subprocess
@@ -14,13 +14,6 @@ import torch
 from helpers import GOLDEN_DIR, TINY_DIR
 
 H5 = os.path.join(GOLDEN_DIR, 'hdf5')
-H5PY_PYTHON = '/opt/conda/bin/python3.9'
-
-
-def _have_h5py():
-    if not os.path.exists(H5PY_PYTHON):
-        return False
-    return subprocess.run([H5PY_PYTHON, '-c', 'import h5py'], capture_output=True).returncode == 0
 
 
 def test_every_fixture_dataset_reads_back_bit_for_bit():
@@ -126,44 +119,22 @@ def test_what_is_not_read_raises_instead_of_returning_wrong_data(tmp_path):
             f['f']
 
 
-@pytest.mark.skipif(not _have_h5py(), reason='no interpreter with h5py on this machine')
-def test_against_files_h5py_writes_on_the_spot(tmp_path):
-    """Random shapes, chunkings and filters, written by h5py now, read here; includes a chunk B-tree three levels
-    deep (5,000 chunks) and the libver='latest' refusal."""
+def test_against_random_files_h5py_wrote(tmp_path):
+    """Random shapes, chunkings and filters, as h5py wrote them (tests/golden/hdf5/random_<seed>.hdf5, seeds 1-3), read
+    here; includes a chunk B-tree three levels deep (5,000 chunks) and the libver='latest' refusal."""
     from reviews4rec_amd import hdf5_lite
-    script = r'''
-import sys, numpy as np, h5py
-rng = np.random.default_rng(int(sys.argv[2]))
-exp = {}
-with h5py.File(sys.argv[1] + '/live.hdf5', 'w') as f:
-    for i in range(12):
-        nd = int(rng.integers(1, 4))
-        shape = tuple(int(x) for x in rng.integers(1, 60, size=nd))
-        chunks = tuple(int(rng.integers(1, s + 1)) for s in shape)
-        dt = ['i8', 'f8', 'i4', 'f4', 'u2', 'i1'][int(rng.integers(0, 6))]
-        a = (rng.standard_normal(shape) * 100).astype(dt)
-        kw = [dict(), dict(chunks=chunks), dict(chunks=chunks, compression='gzip'),
-              dict(chunks=chunks, compression='gzip', shuffle=True, compression_opts=9),
-              dict(chunks=chunks, fletcher32=True)][int(rng.integers(0, 5))]
-        f.create_dataset('d%d' % i, data=a, **kw)
-        exp['d%d' % i] = a
-    a = rng.integers(0, 1 << 40, size=(5000, 3), dtype=np.int64)
-    f.create_dataset('deep', data=a, chunks=(1, 3), compression='gzip')
-    exp['deep'] = a
-np.savez(sys.argv[1] + '/live.npz', **exp)
-with h5py.File(sys.argv[1] + '/latest.hdf5', 'w', libver='latest') as f:
-    f.create_dataset('a', data=np.arange(10), chunks=(5,), compression='gzip')
-'''
+    exp = np.load(os.path.join(H5, 'random_expected.npz'))
     for seed in (1, 2, 3):
-        subprocess.run([H5PY_PYTHON, '-c', script, str(tmp_path), str(seed)], check=True, capture_output=True)
-        exp = np.load(str(tmp_path / 'live.npz'))
-        with hdf5_lite.File(str(tmp_path / 'live.hdf5')) as f:
-            assert f.keys() == sorted(exp.files)
-            for k in exp.files:
-                assert np.array_equal(f[k][:], exp[k]) and f[k][:].dtype == exp[k].dtype, (seed, k)
-            assert np.array_equal(f['deep'][1234:4321], exp['deep'][1234:4321])
+        fn = 'random_%d.hdf5' % seed
+        want = {k.split('/', 1)[1]: exp[k] for k in exp.files if k.startswith(fn + '/')}
+        assert len(want) == 13
+        with hdf5_lite.File(os.path.join(H5, fn)) as f:
+            assert f.keys() == sorted(want)
+            for k in want:
+                assert np.array_equal(f[k][:], want[k]) and f[k][:].dtype == want[k].dtype, (seed, k)
+            assert np.array_equal(f['deep'][1234:4321], want['deep'][1234:4321])
     with pytest.raises(hdf5_lite.Hdf5Error, match='latest'):
-        with hdf5_lite.File(str(tmp_path / 'latest.hdf5')) as f:
+        with hdf5_lite.File(os.path.join(H5, 'latest.hdf5')) as f:
             f['a'][:]
 
 
@@ -216,32 +187,18 @@ def test_save_split_writes_the_reference_container(tmp_path, monkeypatch):
         assert all(np.array_equal(fields[s].numpy(), z['train/%d/%d' % (k, s)]) for s in range(7))
 
 
-@pytest.mark.skipif(not _have_h5py(), reason='no interpreter with h5py on this machine')
 def test_h5py_reads_what_the_writer_writes(tmp_path):
-    """The other direction of the interchange: the reference's loader (h5py.File(...)[k][:], [a:b]) on our files."""
+    """The other direction of the interchange: the reference's loader (h5py.File(...)[k][:], [a:b]) on our files.
+    make_golden_hdf5.py wrote these three forms with this writer, opened each with h5py (every dataset's values, dtype,
+    shape and maxshape, a slice, the gzip level or the contiguous layout) and walked it with libhdf5's h5ls, then recorded
+    its bytes (tests/golden/hdf5/writer_checked.json): the writer must still write exactly those bytes."""
+    import hashlib
+    import json
     from reviews4rec_amd import hdf5_lite
     d = _sample_arrays()
-    np.savez(str(tmp_path / 'w.npz'), **d)
-    hdf5_lite.write_file(str(tmp_path / 'w0.hdf5'), d)
-    hdf5_lite.write_file(str(tmp_path / 'w1.hdf5'), d, chunk_bytes=296)
-    hdf5_lite.write_file(str(tmp_path / 'w2.hdf5'), d, compression=None)
-    script = r'''
-import sys, h5py, numpy as np
-exp = np.load(sys.argv[1] + '/w.npz')
-for fn in ('w0', 'w1', 'w2'):
-    with h5py.File(sys.argv[1] + '/' + fn + '.hdf5', 'r') as f:
-        assert sorted(f.keys()) == sorted(exp.files)
-        assert len(f['a']) == 1000
-        for k in exp.files:
-            assert f[k].dtype == exp[k].dtype and f[k].shape == exp[k].shape and f[k].maxshape == exp[k].shape
-            assert np.array_equal(f[k][:], exp[k]), (fn, k)
-        assert np.array_equal(f['a'][200:400], exp['a'][200:400])
-        assert (f['a'].compression == 'gzip' and f['a'].compression_opts == 4) if fn != 'w2' else f['a'].chunks is None
-print('ok')
-'''
-    r = subprocess.run([H5PY_PYTHON, '-c', script, str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stderr
-    h5ls = os.path.join(os.path.dirname(H5PY_PYTHON), 'h5ls')
-    if os.path.exists(h5ls):                                  # libhdf5's own tool walks every structure
-        r = subprocess.run([h5ls, '-r', '-v', str(tmp_path / 'w1.hdf5')], capture_output=True, text=True)
-        assert r.returncode == 0 and 'Dataset {1000/1000, 37/37}' in r.stdout, r.stdout + r.stderr
+    checked = json.load(open(os.path.join(H5, 'writer_checked.json')))
+    assert sorted(checked) == ['w0.hdf5', 'w1.hdf5', 'w2.hdf5']
+    for fn, rec in checked.items():
+        hdf5_lite.write_file(str(tmp_path / fn), d, **rec['write_file_kwargs'])
+        raw = open(str(tmp_path / fn), 'rb').read()
+        assert (len(raw), hashlib.sha256(raw).hexdigest()) == (rec['bytes'], rec['sha256']), fn
