@@ -830,7 +830,10 @@ int r4r_batch_build(const int32_t *user_tok, const int64_t *user_rev_off, const 
  * offset + k * draws_per_step, adam_step + k.  sweep_period / sweep_want: the schedule in force and the one wanted
  * (engine.py _SweepSchedule: a step visits every chunk iff they differ or the period is 1, and the wanted one is in
  * force afterwards); *sweep_base / *sweep_period_out carry the schedule across calls.  Training steps only
- * (flat_g, moments and adam_step >= 1 required); all other arguments as in the family's r4r_*_step.
+ * (flat_g, moments and adam_step >= 1 required); all other arguments as in the family's r4r_*_step.  The documents a
+ * span's steps read must be the ones the ring holds -- T = word 17 with R = word 18 = 0 (DeepCoNN, DeepCoNN++,
+ * TransNet); NARRE: R, T = words 18, 19 and R = 10, the width of the neighbour lists -- and a resident table (word 27)
+ * still takes NARRE's R = 10 only: anything else is refused before anything is enqueued (steps_done = 0).
  * r4r_span_build: make sure the group of `batch` is in the ring.  r4r_span_batch: the eight device pointers of a
  * built batch -- this, who, what, user doc, item doc, uid, iid, y (data_fast.py:101-109 order) -- into HOST slots[8]. */
 #define R4R_LOADER_WORDS 28

@@ -134,6 +134,26 @@ static int run_span(const uint64_t *loader, int64_t first_batch, int64_t steps, 
     return R4R_OK;
 }
 
+// The documents a family's step will read (R = 0: one T-token document per rating; R > 0: NARRE's R x T reviews and
+// NB neighbour ids per side) against those the descriptor's ring holds -- checked before anything is enqueued: the
+// step indexes the ring's blocks by ITS shape, so a mismatch reads tokens as ids and writes row tags out of bounds.
+// A resident table (word 27) carries no shape; NARRE's step still reads b*R + r of its NB-wide neighbour lists.
+static int check_doc_shape(const uint64_t *loader, const char *who, int R, int T, int64_t *steps_done) {
+    if (steps_done) *steps_done = 0;
+    SpanLoader L;
+    if (int rc = decode_loader(loader, L)) return rc;
+    R4R_REQUIRE(R == 0 || R == NB, "%s: R = %d reviews, but the loader holds %d neighbour ids per rating", who, R, NB);
+    if (L.resident) return R4R_OK;
+    R4R_REQUIRE(L.review, "%s: the descriptor is an ids-only loader, the step reads documents", who);
+    if (R == 0)
+        R4R_REQUIRE(L.R == 0 && L.T == T, "%s: T = %d, the descriptor builds documents of %s %d", who, T,
+                    L.R ? "R x W =" : "T =", L.R ? L.R * L.W : L.T);
+    else
+        R4R_REQUIRE(L.R == R && L.W == T, "%s: R x T = %d x %d, the descriptor builds %d x %d reviews", who, R, T, L.R,
+                    L.W);
+    return R4R_OK;
+}
+
 struct Sweep {                                              // engine.py _SweepSchedule, one step at a time
     int period, want;
     int64_t base;
@@ -175,6 +195,7 @@ extern "C" int r4r_deepconn_span(const uint64_t *loader, int64_t first_batch, in
                                  float lr, double beta1, double beta2, float eps, float weight_decay,
                                  int64_t adam_step, void *stream) {
     R4R_REQUIRE(flat_g && flat_m && flat_v && adam_step >= 1, "deepconn_span: training steps only (gradients, moments, adam_step >= 1)");
+    if (int rc = check_doc_shape(loader, "deepconn_span", 0, T, steps_done)) return rc;
     const int64_t B = loader ? (int64_t)loader[26] : 0;
     return run_span(loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
                     [&](int64_t k, const SpanBatch &c, const SpanBatch *n) {
@@ -208,6 +229,7 @@ extern "C" int r4r_deepconn_span_dp(const uint64_t *loader, int64_t first_batch,
     R4R_REQUIRE(collective && comm && world >= 1 && (exchange == 0 || (exchange == 1 && gathered)),
                 "deepconn_span_dp: exchange 0 (all-reduce) or 1 (all-gather into `gathered` [world][total]) with RCCL's "
                 "entry point and a communicator");
+    if (int rc = check_doc_shape(loader, "deepconn_span_dp", 0, T, steps_done)) return rc;
     const int64_t B = loader ? (int64_t)loader[26] : 0;
     return run_span(
         loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
@@ -246,6 +268,7 @@ extern "C" int r4r_deepconnpp_span(const uint64_t *loader, int64_t first_batch, 
                                    int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1, double beta2, float eps,
                                    float weight_decay, int64_t adam_step, void *stream) {
     R4R_REQUIRE(flat_g && flat_m && flat_v && adam_step >= 1, "deepconnpp_span: training steps only");
+    if (int rc = check_doc_shape(loader, "deepconnpp_span", 0, T, steps_done)) return rc;
     const int64_t B = loader ? (int64_t)loader[26] : 0;
     return run_span(loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
                     [&](int64_t k, const SpanBatch &c, const SpanBatch *n) {
@@ -268,6 +291,7 @@ extern "C" int r4r_narre_span(const uint64_t *loader, int64_t first_batch, int64
                               float inv_denom, int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1, double beta2,
                               float eps, float weight_decay, int64_t adam_step, void *stream) {
     R4R_REQUIRE(flat_g && flat_m && flat_v && adam_step >= 1, "narre_span: training steps only");
+    if (int rc = check_doc_shape(loader, "narre_span", R, T, steps_done)) return rc;
     const int64_t B = loader ? (int64_t)loader[26] : 0;
     return run_span(loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
                     [&](int64_t k, const SpanBatch &c, const SpanBatch *n) {
@@ -293,6 +317,10 @@ extern "C" int r4r_transnet_span(const uint64_t *loader, int64_t first_batch, in
                                  double beta2, float eps, float weight_decay, int64_t adam_step, void *stream) {
     R4R_REQUIRE(flat_g && flat_m && flat_v && adam_step >= 1 && sweep_base && sweep_period_out,
                 "transnet_span: training steps only; sweep_base / sweep_period_out are the schedule's state");
+    if (int rc = check_doc_shape(loader, "transnet_span", 0, T, steps_done)) {
+        *sweep_period_out = sweep_period;                   // (nothing was enqueued: the schedule is the one passed in)
+        return rc;
+    }
     const int64_t B = loader ? (int64_t)loader[26] : 0;
     Sweep sw{sweep_period, sweep_want, *sweep_base};
     const int rc = run_span(

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr
+from .data import NEIGHBOURS
 
 
 GEMM_MATH_REFRESH = 32        # steps between two reads of max |conv weights| (one small D2H sync each)
@@ -631,7 +632,8 @@ class DeepCoNNEngine(_ConvRule, _Spans):
 
     # ------------------------------------------------------------------ spans (K steps per host call)
     def _span_ok(self, desc):
-        return desc.review and len(desc.doc_shape) == 1
+        # (the fp16-split GEMM refreshes its scales between steps: main.train's own loop, with next_data)
+        return desc.review and len(desc.doc_shape) == 1 and getattr(self, 'gemm_math', 'f32') != 'f16x2'
 
     def _span_limit(self, desc, ahead=0):
         return self._rule_peek(desc.batch_size, desc.doc_shape[0], ahead)[0]
@@ -1411,6 +1413,8 @@ class NarreEngine(_ConvRule, _Spans):
         if not desc.review or len(desc.doc_shape) != 2:
             return None
         R, W = desc.doc_shape
+        if R != NEIGHBOURS:
+            return None                                      # (the ring holds 10 neighbour ids per rating: train_step refuses)
         if desc.batch_size * (1 + R) > self.FUSED_MAX_ENTRIES or self.L > 32 or R > 32:
             return None                                      # (train_step's split form: per step)
         return R, W
@@ -1419,7 +1423,8 @@ class NarreEngine(_ConvRule, _Spans):
         return (slots[3], slots[4])                          # the documents the TextCNN towers read: user, item
 
     def _span_ok(self, desc):
-        return self._span_doc(desc) is not None
+        # (the fp16-split GEMM refreshes its scales between steps: main.train's own loop, with next_data)
+        return self._span_doc(desc) is not None and getattr(self, 'gemm_math', 'f32') != 'f16x2'
 
     def _span_limit(self, desc, ahead=0):
         R, T = self._span_doc(desc)

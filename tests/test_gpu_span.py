@@ -42,8 +42,10 @@ def hyper(mt, **kw):
     hp = dict(model_type=mt, batch_size=32, input_length=64, narre_num_reviews=10, narre_num_words=12, total_users=300,
               total_items=120, latent_size=8, word_embed_size=16, dropout=0.5, lr=0.002, weight_decay=1e-6, vocab=400,
               total_words=400, engine='native', dataset='span_test')
-    hp['word_vectors'] = (np.random.default_rng(3).random((400, 16), dtype=np.float32) - 0.5) * 0.2
     hp.update(kw)
+    if 'word_vectors' not in kw:                             # (the frozen table follows vocab / word_embed_size)
+        shape = (int(hp['total_words']), int(hp['word_embed_size']))
+        hp['word_vectors'] = (np.random.default_rng(3).random(shape, dtype=np.float32) - 0.5) * 0.2
     return hp
 
 
@@ -62,23 +64,31 @@ def build(mt, corpus, **kw):
     return hp, reader, model, M.make_engine(hp, model)
 
 
-def run_epochs(mt, corpus, spans, epochs=2, span_steps=None, **kw):
+def run_epochs(mt, corpus, spans, epochs=2, span_steps=None, setup=None, **kw):
+    """`setup(engine)`: called before the first epoch (both runs of a comparison).  With spans on, `calls` counts the
+    span and train_step calls, records whether each train_step was given next_data, and the highest ring group any
+    span call found built (`built`: >= 2 means a ring slot was rebuilt)."""
     from reviews4rec_amd import main as M
     from reviews4rec_amd.loss import MSELoss
     hp, reader, model, engine = build(mt, corpus, **kw)
     hp['spans'] = spans
     if span_steps:
         engine.SPAN_STEPS = span_steps
-    calls = {'span': 0, 'step': 0}
+    if setup is not None:
+        setup(engine)
+    calls = {'span': 0, 'step': 0, 'next': [], 'built': -1}
     if spans:
         inner_span, inner_step = engine._span, engine.train_step
 
         def counting_span(*a, **k):
             calls['span'] += 1
-            return inner_span(*a, **k)
+            out = inner_span(*a, **k)
+            calls['built'] = max(calls['built'], int(a[0].built.value))
+            return out
 
         def counting_step(*a, **k):
             calls['step'] += 1
+            calls['next'].append(k.get('next_data') is not None)
             return inner_step(*a, **k)
         engine._span, engine.train_step = counting_span, counting_step
     metrics = [M.train(model, MSELoss(hp), None, reader, hp, engine=engine) for _ in range(epochs)]
