@@ -900,6 +900,86 @@ int r4r_idnet_span(const uint64_t *loader, int64_t first_batch, int64_t steps, i
                    uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom, int sweep_period,
                    int sweep_want, int64_t *sweep_base, int *sweep_period_out, float lr, double beta1,
                    double beta2, float eps, float weight_decay, int64_t adam_step, void *stream);
+/* Data parallel for the other native families (csrc/span.hip): each r4r_<family>_span_dp enqueues, per step k, exactly
+ * the launches, arguments, collectives and order of the engine's per-step data-parallel path (reviews4rec_amd/engine.py
+ * _train_step_dp / _dp_rows) -- the family's step with gradients only (inv_denom = 1 / B_global), the collectives on
+ * `stream`, the updates -- so an epoch through them leaves the bits of the per-step loop.  Replaces, per step, the
+ * reference loop body of main.py:23-60 on every rank + the gradient exchange the reference (single-process) does not
+ * have.  Arguments as in the family's span above, plus:
+ *   total       the flat layout's element count (the all-reduce and r4r_adam_multi)
+ *   allreduce / allgather   the addresses of RCCL's ncclAllReduce / ncclAllGather, resolved by the caller in the
+ *               library it already holds (reviews4rec_amd/dist.py: StreamRccl), `comm` its communicator, `world` ranks;
+ *               nothing is linked here.  The all-reduce is in place on flat_g (float32 sum); an all-gather moves
+ *               `block` (this rank's bytes, as 4-byte words) into `blocks` [world] in rank order
+ *   B_pad       every rank's shard is padded to it (hyper_params['batch_size']); the loader's B <= B_pad
+ *   gathered    HOST array of the unpacked fields' device arrays [world * B_pad, width] (r4r_dp_unpack's dst)
+ * Per step (adam_step + k):
+ *   r4r_narre_span_dp       r4r_narre_step (flat / row moments NULL, sse on) -> ncclAllReduce(flat_g) ->
+ *                           r4r_adam_multi -> r4r_narre_dp_block -> ncclAllGather(block -> blocks) ->
+ *                           r4r_narre_rows_apply_blocks.  world * B_pad * (1 + R) <= 16384, L <= 32, R = 10.
+ *                           (NARRE.py:18-19,110-116: the ID embeddings and biases whose rows travel)
+ *   r4r_deepconnpp_span_dp  r4r_deepconnpp_step (gradients only) -> all-reduce -> r4r_adam_multi -> r4r_dp_pack (uid,
+ *                           iid, d loss / d pred) -> all-gather -> r4r_dp_unpack into gathered[3] ->
+ *                           r4r_deepconnpp_rows_apply.  world * B_pad <= 16384.  (DeepCoNN.py:64-72: the bias head)
+ *   r4r_transnet_span_dp    r4r_transnet_step (gradients only, rows_m / rows_v read for the catch-up, on the sweep
+ *                           schedule) -> all-reduce -> r4r_adam_multi -> TransNet++ only: r4r_transnet_dp_block ->
+ *                           all-gather -> r4r_transnet_rows_apply_blocks; the schedule advances.  TransNet++:
+ *                           world * B_pad <= 2048.  (TransNet.py:75-76,108-109: the ID vectors of TransNet++)
+ *   r4r_idnet_span_dp       r4r_idnet_step (gradients only, on the schedule) -> all-reduce -> r4r_adam_multi ->
+ *                           r4r_dp_pack (uid, iid, d loss / d pred, the compact rows of the 2 / NeuMF 4 tables) ->
+ *                           all-gather -> r4r_dp_unpack into gathered[5 / 7] -> r4r_idnet_rows_apply; the schedule
+ *                           advances.  world * B_pad <= 16384.  (MF.py:21-22,52-53 and NeuMF.py's embeddings)
+ *   r4r_mf_span_dp          r4r_mf_grad (m / v / ws passed when rows may be pending: MF_dot on a schedule of period
+ *                           > 1) -> ncclAllGather(block -> blocks) -> r4r_mf_apply (sse on); the schedule advances.
+ *                           No all-reduce (allgather only); world * B_pad <= 16384; ws: r4r_mf_ws_bytes(world * B_pad).
+ *                           (MF.py:21-22,52-53)
+ * Every argument is checked before anything is enqueued (a refusal names the entry point, *steps_done = 0). */
+int r4r_narre_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce, int64_t *built_group,
+                      int64_t *steps_done, const float *table, int64_t V, float *flat_p, float *flat_g, float *flat_m,
+                      float *flat_v, int64_t total, const uint64_t *rows_p, const uint64_t *rows_m,
+                      const uint64_t *rows_v, int64_t n_users, int64_t n_items, float *pred, float *se,
+                      float *sse_accum, void *ws, size_t ws_bytes, int R, int T, int E, int L, float dropout_p,
+                      int training, uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom,
+                      int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1, double beta2,
+                      float eps, float weight_decay, int64_t adam_step, void *allreduce, void *allgather, void *comm,
+                      int world, int64_t B_pad, void *block, void *blocks, void *stream);
+int r4r_deepconnpp_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce,
+                           int64_t *built_group, int64_t *steps_done, const float *table, int64_t V, float *flat_p,
+                           float *flat_g, float *flat_m, float *flat_v, int64_t total, const uint64_t *rows_p,
+                           const uint64_t *rows_m, const uint64_t *rows_v, int64_t n_users, int64_t n_items,
+                           float *pred, float *se, float *sse_accum, void *ws, size_t ws_bytes, int T, int E, int L,
+                           float dropout_p, int training, uint64_t seed, uint64_t offset, uint64_t draws_per_step,
+                           float inv_denom, int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1,
+                           double beta2, float eps, float weight_decay, int64_t adam_step, void *allreduce,
+                           void *allgather, void *comm, int world, int64_t B_pad, void *block, void *blocks,
+                           const uint64_t *gathered, void *stream);
+int r4r_transnet_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce,
+                         int64_t *built_group, int64_t *steps_done, const float *table, int64_t V, float *flat_p,
+                         float *flat_g, float *flat_m, float *flat_v, int64_t total, const uint64_t *rows_p,
+                         const uint64_t *rows_m, const uint64_t *rows_v, int64_t n_users, int64_t n_items,
+                         float *pred, float *se, float *sse_accum, void *ws, size_t ws_bytes, int T, int E, int L,
+                         int plus, float dropout_p, int training, uint64_t seed, uint64_t offset,
+                         uint64_t draws_per_step, float inv_denom, int conv_algo, int token_buffer, int tokens_ready,
+                         int sweep_period, int sweep_want, int64_t *sweep_base, int *sweep_period_out, float lr,
+                         double beta1, double beta2, float eps, float weight_decay, int64_t adam_step,
+                         void *allreduce, void *allgather, void *comm, int world, int64_t B_pad, void *block,
+                         void *blocks, void *stream);
+int r4r_idnet_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int64_t *steps_done, int variant,
+                      float *flat_p, float *flat_g, float *flat_m, float *flat_v, int64_t total,
+                      const uint64_t *rows_p, const uint64_t *rows_m, const uint64_t *rows_v, int64_t n_users,
+                      int64_t n_items, float *pred, float *se, float *sse_accum, void *ws, size_t ws_bytes, int L,
+                      float dropout_p, int training, uint64_t seed, uint64_t offset, uint64_t draws_per_step,
+                      float inv_denom, int sweep_period, int sweep_want, int64_t *sweep_base, int *sweep_period_out,
+                      float lr, double beta1, double beta2, float eps, float weight_decay, int64_t adam_step,
+                      void *allreduce, void *allgather, void *comm, int world, int64_t B_pad, void *block,
+                      void *blocks, const uint64_t *gathered, void *stream);
+int r4r_mf_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int64_t *steps_done, const uint64_t *p,
+                   const uint64_t *m, const uint64_t *v, int64_t n_users, int64_t n_items, int D, float *pred,
+                   float *se, float *sse_accum, void *ws, size_t ws_bytes, float dropout_p, int training,
+                   uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom, int sweep_period,
+                   int sweep_want, int64_t *sweep_base, int *sweep_period_out, float lr, double beta1, double beta2,
+                   float eps, float weight_decay, int64_t adam_step, void *allgather, void *comm, int world,
+                   int64_t B_pad, void *block, void *blocks, void *stream);
 
 #ifdef __cplusplus
 }

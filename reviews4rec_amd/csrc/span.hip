@@ -391,3 +391,313 @@ extern "C" int r4r_idnet_span(const uint64_t *loader, int64_t first_batch, int64
     *sweep_period_out = sw.period;
     return rc;
 }
+
+// ---- data parallel for the other native families: each is its family's span with the exchange of the per-step
+// data-parallel path (reviews4rec_amd/engine.py: _train_step_dp / _dp_rows) between every step's gradients and its
+// updates -- the same launches, arguments, collectives and order, so an epoch through these leaves the bits of the
+// per-step loop.  Only the exchange forms each family takes at ordinary sizes are here (the packed blocks); beyond them
+// the engine runs the step through train_step.
+namespace r4r {
+
+struct DpComm {                                             // RCCL's entry points, resolved by the caller (dist.StreamRccl)
+    void *allreduce, *allgather, *comm;
+    int world;
+    const char *who;
+    int reduce(float *g, int64_t n, void *stream) const {   // in place, float32 sum (StreamRccl.all_reduce)
+        const int rc = reinterpret_cast<rccl_allreduce_fn>(allreduce)(g, g, (size_t)n, RCCL_FLOAT32, RCCL_SUM, comm, stream);
+        if (rc) { set_error("%s: ncclAllReduce returned %d", who, rc); return R4R_ERR_LAUNCH; }
+        return R4R_OK;
+    }
+    int gather(const void *block, void *blocks, size_t bytes, void *stream) const {   // 4-byte words (StreamRccl.all_gather)
+        const int rc = reinterpret_cast<rccl_allgather_fn>(allgather)(block, blocks, bytes / 4, RCCL_FLOAT32, comm, stream);
+        if (rc) { set_error("%s: ncclAllGather returned %d", who, rc); return R4R_ERR_LAUNCH; }
+        return R4R_OK;
+    }
+};
+
+// The dense half of a step (engine.py _train_step_dp): the all-reduced flat gradient into the flat Adam.
+static int dp_dense(const DpComm &c, float *flat_p, float *flat_g, float *flat_m, float *flat_v, int64_t total, float lr,
+                    double beta1, double beta2, float eps, float weight_decay, int64_t step, void *stream) {
+    if (int rc = c.reduce(flat_g, total, stream)) return rc;
+    const uint64_t p1[1] = {(uint64_t)flat_p}, g1[1] = {(uint64_t)flat_g}, m1[1] = {(uint64_t)flat_m}, v1[1] = {(uint64_t)flat_v};
+    const int64_t n1[1] = {total};
+    return r4r_adam_multi(1, p1, g1, m1, v1, n1, lr, beta1, beta2, eps, weight_decay, step, nullptr, stream);
+}
+
+// engine.gather_entry_fields: this rank's entries packed into one block, ONE all-gather, unpacked into `dst`.
+static int dp_fields(const DpComm &c, int nf, const uint64_t *src, const int *widths, const int *ones, int64_t n,
+                     int64_t B_pad, void *block, void *blocks, const uint64_t *dst, void *stream) {
+    const size_t nbytes = r4r_dp_block_bytes(nf, widths, B_pad);
+    if (int rc = r4r_dp_pack(nf, src, widths, ones, n, B_pad, block, stream)) return rc;
+    if (int rc = c.gather(block, blocks, nbytes > 4 ? nbytes : 4, stream)) return rc;
+    return r4r_dp_unpack(nf, dst, widths, blocks, c.world, B_pad, stream);
+}
+
+// Checked before anything is enqueued (and with *steps_done = 0 already): the collectives' addresses and communicator.
+static int dp_comm_ok(const char *who, bool reduce, void *allreduce, void *allgather, void *comm, int world) {
+    R4R_REQUIRE((!reduce || allreduce) && allgather && comm && world >= 1,
+                "%s: RCCL's entry points (%s), a communicator and world >= 1", who,
+                reduce ? "ncclAllReduce, ncclAllGather" : "ncclAllGather");
+    return R4R_OK;
+}
+
+}  // namespace r4r
+
+extern "C" int r4r_narre_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce,
+                                 int64_t *built_group, int64_t *steps_done, const float *table, int64_t V,
+                                 float *flat_p, float *flat_g, float *flat_m, float *flat_v, int64_t total,
+                                 const uint64_t *rows_p, const uint64_t *rows_m, const uint64_t *rows_v,
+                                 int64_t n_users, int64_t n_items, float *pred, float *se, float *sse_accum, void *ws,
+                                 size_t ws_bytes, int R, int T, int E, int L, float dropout_p, int training,
+                                 uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom,
+                                 int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1,
+                                 double beta2, float eps, float weight_decay, int64_t adam_step, void *allreduce,
+                                 void *allgather, void *comm, int world, int64_t B_pad, void *block, void *blocks,
+                                 void *stream) {
+    if (steps_done) *steps_done = 0;
+    R4R_REQUIRE(flat_g && flat_m && flat_v && rows_m && rows_v && adam_step >= 1 && total > 0,
+                "narre_span_dp: training steps only (gradients, moments, adam_step >= 1)");
+    if (int rc = dp_comm_ok("narre_span_dp", true, allreduce, allgather, comm, world)) return rc;
+    const int64_t B = loader ? (int64_t)loader[26] : 0;
+    R4R_REQUIRE(R == NB, "narre_span_dp: R = %d reviews, the ring holds %d neighbour ids per rating", R, NB);
+    R4R_REQUIRE(block && blocks && B <= B_pad && (int64_t)world * B_pad * (1 + R) <= 16384 && L <= 32,
+                "narre_span_dp: the packed blocks (world x B_pad x (1 + R) <= 16384 entries, L <= 32, B <= B_pad)");
+    if (int rc = check_doc_shape(loader, "narre_span_dp", R, T, steps_done)) return rc;
+    const DpComm c{allreduce, allgather, comm, world, "narre_span_dp"};
+    const size_t nbytes = r4r_narre_dp_block_bytes(B_pad, R, L);
+    return run_span(
+        loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
+        [&](int64_t k, const SpanBatch &b, const SpanBatch *n) {
+            const int64_t step = adam_step + k;
+            // NARRE.py:87-96: reviewed_items = data[2], users_who_reviewed = data[1]; gradients only
+            if (int rc = r4r_narre_step(table, V, b.user_doc, b.item_doc, b.what, b.who, b.uid, b.iid, b.y, flat_p,
+                                        flat_g, nullptr, nullptr, rows_p, nullptr, nullptr, n_users, n_items, pred, se,
+                                        sse_accum, ws, ws_bytes, B, R, T, E, L, dropout_p, training, seed,
+                                        offset + (uint64_t)k * draws_per_step, inv_denom, conv_algo,
+                                        (token_buffer + (int)k) & 1, k ? 1 : tokens_ready, n ? n->user_doc : nullptr,
+                                        n ? n->item_doc : nullptr, lr, beta1, beta2, eps, weight_decay, step, stream))
+                return rc;
+            if (int rc = dp_dense(c, flat_p, flat_g, flat_m, flat_v, total, lr, beta1, beta2, eps, weight_decay, step,
+                                  stream))
+                return rc;
+            if (int rc = r4r_narre_dp_block(ws, ws_bytes, B, R, T, E, L, V, n_users, n_items, block, B_pad, stream))
+                return rc;
+            if (int rc = c.gather(block, blocks, nbytes, stream)) return rc;
+            return r4r_narre_rows_apply_blocks(blocks, world, B_pad, rows_p, rows_m, rows_v, n_users, n_items, ws,
+                                               ws_bytes, B, R, T, E, L, V, lr, beta1, beta2, eps, weight_decay, step,
+                                               stream);
+        });
+}
+
+extern "C" int r4r_deepconnpp_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce,
+                                      int64_t *built_group, int64_t *steps_done, const float *table, int64_t V,
+                                      float *flat_p, float *flat_g, float *flat_m, float *flat_v, int64_t total,
+                                      const uint64_t *rows_p, const uint64_t *rows_m, const uint64_t *rows_v,
+                                      int64_t n_users, int64_t n_items, float *pred, float *se, float *sse_accum,
+                                      void *ws, size_t ws_bytes, int T, int E, int L, float dropout_p, int training,
+                                      uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom,
+                                      int conv_algo, int token_buffer, int tokens_ready, float lr, double beta1,
+                                      double beta2, float eps, float weight_decay, int64_t adam_step, void *allreduce,
+                                      void *allgather, void *comm, int world, int64_t B_pad, void *block,
+                                      void *blocks, const uint64_t *gathered, void *stream) {
+    if (steps_done) *steps_done = 0;
+    R4R_REQUIRE(flat_g && flat_m && flat_v && rows_m && rows_v && adam_step >= 1 && total > 0,
+                "deepconnpp_span_dp: training steps only (gradients, moments, adam_step >= 1)");
+    if (int rc = dp_comm_ok("deepconnpp_span_dp", true, allreduce, allgather, comm, world)) return rc;
+    const int64_t B = loader ? (int64_t)loader[26] : 0;
+    R4R_REQUIRE(block && blocks && gathered && gathered[0] && gathered[1] && gathered[2] && B <= B_pad &&
+                    (int64_t)world * B_pad <= 16384,
+                "deepconnpp_span_dp: the exchange buffers (block, blocks, gathered uid / iid / d loss/d pred) and "
+                "world x B_pad <= 16384, B <= B_pad");
+    if (int rc = check_doc_shape(loader, "deepconnpp_span_dp", 0, T, steps_done)) return rc;
+    const DpComm c{allreduce, allgather, comm, world, "deepconnpp_span_dp"};
+    const int widths[3] = {2, 2, 1}, ones[3] = {1, 1, 0};   // uid, iid (int64, -1 padding), d loss / d pred
+    const uint64_t g = (uint64_t)ws + r4r_deepconnpp_ws_offset(B, T, E, L, V, n_users, n_items, 5);
+    return run_span(
+        loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
+        [&](int64_t k, const SpanBatch &b, const SpanBatch *n) {
+            const int64_t step = adam_step + k;
+            if (int rc = r4r_deepconnpp_step(table, V, b.user_doc, b.item_doc, b.uid, b.iid, b.y, flat_p, flat_g, nullptr,
+                                             nullptr, rows_p, nullptr, nullptr, n_users, n_items, pred, se, sse_accum, ws,
+                                             ws_bytes, B, T, E, L, dropout_p, training, seed,
+                                             offset + (uint64_t)k * draws_per_step, inv_denom, conv_algo,
+                                             (token_buffer + (int)k) & 1, k ? 1 : tokens_ready,
+                                             n ? n->user_doc : nullptr, n ? n->item_doc : nullptr, lr, beta1, beta2,
+                                             eps, weight_decay, step, stream))
+                return rc;
+            if (int rc = dp_dense(c, flat_p, flat_g, flat_m, flat_v, total, lr, beta1, beta2, eps, weight_decay, step,
+                                  stream))
+                return rc;
+            const uint64_t src[3] = {(uint64_t)b.uid, (uint64_t)b.iid, g};
+            if (int rc = dp_fields(c, 3, src, widths, ones, B, B_pad, block, blocks, gathered, stream)) return rc;
+            return r4r_deepconnpp_rows_apply(reinterpret_cast<const int64_t *>(gathered[0]),
+                                             reinterpret_cast<const int64_t *>(gathered[1]),
+                                             reinterpret_cast<const float *>(gathered[2]), world * B_pad, rows_p, rows_m,
+                                             rows_v, n_users, n_items, ws, ws_bytes, B, T, E, L, V, lr, beta1, beta2,
+                                             eps, weight_decay, step, stream);
+        });
+}
+
+extern "C" int r4r_transnet_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int announce,
+                                    int64_t *built_group, int64_t *steps_done, const float *table, int64_t V,
+                                    float *flat_p, float *flat_g, float *flat_m, float *flat_v, int64_t total,
+                                    const uint64_t *rows_p, const uint64_t *rows_m, const uint64_t *rows_v,
+                                    int64_t n_users, int64_t n_items, float *pred, float *se, float *sse_accum,
+                                    void *ws, size_t ws_bytes, int T, int E, int L, int plus, float dropout_p,
+                                    int training, uint64_t seed, uint64_t offset, uint64_t draws_per_step,
+                                    float inv_denom, int conv_algo, int token_buffer, int tokens_ready,
+                                    int sweep_period, int sweep_want, int64_t *sweep_base, int *sweep_period_out,
+                                    float lr, double beta1, double beta2, float eps, float weight_decay,
+                                    int64_t adam_step, void *allreduce, void *allgather, void *comm, int world,
+                                    int64_t B_pad, void *block, void *blocks, void *stream) {
+    if (steps_done) *steps_done = 0;
+    R4R_REQUIRE(flat_g && flat_m && flat_v && adam_step >= 1 && total > 0 && sweep_base && sweep_period_out,
+                "transnet_span_dp: training steps only; sweep_base / sweep_period_out are the schedule's state");
+    *sweep_period_out = sweep_period;                       // (until a step completes: the schedule passed in)
+    if (int rc = dp_comm_ok("transnet_span_dp", true, allreduce, allgather, comm, world)) return rc;
+    const int64_t B = loader ? (int64_t)loader[26] : 0;
+    R4R_REQUIRE(!plus || (rows_m && rows_v && block && blocks && B <= B_pad && (int64_t)world * B_pad <= 2048),
+                "transnet_span_dp: TransNet++ exchanges packed blocks (moments, block, blocks; world x B_pad <= 2048, "
+                "B <= B_pad)");
+    if (int rc = check_doc_shape(loader, "transnet_span_dp", 0, T, steps_done)) return rc;
+    const DpComm c{allreduce, allgather, comm, world, "transnet_span_dp"};
+    const size_t nbytes = plus ? r4r_transnet_dp_block_bytes(B_pad) : 0;
+    Sweep sw{sweep_period, sweep_want, *sweep_base};
+    const int rc = run_span(
+        loader, first_batch, steps, announce, built_group, steps_done, as_stream(stream),
+        [&](int64_t k, const SpanBatch &b, const SpanBatch *n) {
+            const int64_t step = adam_step + k;
+            // gradients only; rows_m / rows_v still read, for the catch-up of the rows a rating names
+            if (int rc = r4r_transnet_step(
+                    table, V, b.user_doc, b.item_doc, b.this_doc, b.uid, b.iid, b.y, flat_p, flat_g, nullptr, nullptr,
+                    rows_p, rows_m, rows_v, n_users, n_items, pred, se, sse_accum, ws, ws_bytes, B, T, E, L, plus,
+                    dropout_p, training, seed, offset + (uint64_t)k * draws_per_step, inv_denom, conv_algo,
+                    (token_buffer + (int)k) & 1, k ? 1 : tokens_ready, n ? n->user_doc : nullptr,
+                    n ? n->item_doc : nullptr, n ? n->this_doc : nullptr, sw.period, sw.base, sw.all(), lr, beta1, beta2,
+                    eps, weight_decay, step, stream))
+                return rc;
+            if (int rc = dp_dense(c, flat_p, flat_g, flat_m, flat_v, total, lr, beta1, beta2, eps, weight_decay, step,
+                                  stream))
+                return rc;
+            if (plus) {
+                if (int rc = r4r_transnet_dp_block(b.uid, b.iid, ws, ws_bytes, B, T, E, L, V, n_users, n_items, block,
+                                                   B_pad, stream))
+                    return rc;
+                if (int rc = c.gather(block, blocks, nbytes, stream)) return rc;
+                if (int rc = r4r_transnet_rows_apply_blocks(blocks, world, B_pad, sw.period, sw.base, sw.all(), rows_p,
+                                                            rows_m, rows_v, n_users, n_items, ws, ws_bytes, B, T, E, L,
+                                                            V, lr, beta1, beta2, eps, weight_decay, step, stream))
+                    return rc;
+            }
+            sw.done(step);
+            return R4R_OK;
+        });
+    *sweep_base = sw.base;
+    *sweep_period_out = sw.period;
+    return rc;
+}
+
+extern "C" int r4r_idnet_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int64_t *steps_done,
+                                 int variant, float *flat_p, float *flat_g, float *flat_m, float *flat_v,
+                                 int64_t total, const uint64_t *rows_p, const uint64_t *rows_m,
+                                 const uint64_t *rows_v, int64_t n_users, int64_t n_items, float *pred, float *se,
+                                 float *sse_accum, void *ws, size_t ws_bytes, int L, float dropout_p, int training,
+                                 uint64_t seed, uint64_t offset, uint64_t draws_per_step, float inv_denom,
+                                 int sweep_period, int sweep_want, int64_t *sweep_base, int *sweep_period_out,
+                                 float lr, double beta1, double beta2, float eps, float weight_decay,
+                                 int64_t adam_step, void *allreduce, void *allgather, void *comm, int world,
+                                 int64_t B_pad, void *block, void *blocks, const uint64_t *gathered, void *stream) {
+    if (steps_done) *steps_done = 0;
+    R4R_REQUIRE(flat_g && flat_m && flat_v && rows_m && rows_v && adam_step >= 1 && total > 0 && sweep_base &&
+                    sweep_period_out,
+                "idnet_span_dp: training steps only; sweep_base / sweep_period_out are the schedule's state");
+    *sweep_period_out = sweep_period;
+    if (int rc = dp_comm_ok("idnet_span_dp", true, allreduce, allgather, comm, world)) return rc;
+    const int ntab = variant == 3 ? 4 : 2, nf = 3 + ntab;  // NeuMF: two table pairs
+    const int64_t B = loader ? (int64_t)loader[26] : 0;
+    bool have = block && blocks && gathered && variant >= 0 && variant <= 3;
+    for (int f = 0; have && f < nf; ++f) have = gathered[f] != 0;
+    R4R_REQUIRE(have && B <= B_pad && (int64_t)world * B_pad <= 16384,
+                "idnet_span_dp: the exchange buffers (block, blocks, gathered uid / iid / d loss/d pred / %d row "
+                "arrays) and world x B_pad <= 16384, B <= B_pad", ntab);
+    const DpComm c{allreduce, allgather, comm, world, "idnet_span_dp"};
+    int widths[7], ones[7];
+    uint64_t src[7];
+    for (int f = 0; f < nf; ++f) {                          // uid, iid (int64, -1 padding), d loss / d pred, the rows
+        widths[f] = f < 2 ? 2 : (f == 2 ? 1 : L);
+        ones[f] = f < 2;
+        src[f] = f < 2 ? 0 : (uint64_t)ws + r4r_idnet_ws_offset(variant, B, L, n_users, n_items, f == 2 ? 1 : 4 + f - 3);
+    }
+    uint64_t gu[2] = {gathered[3], ntab > 2 ? gathered[5] : 0}, gi[2] = {gathered[4], ntab > 2 ? gathered[6] : 0};
+    Sweep sw{sweep_period, sweep_want, *sweep_base};
+    const int rc = run_span(
+        loader, first_batch, steps, 0, nullptr, steps_done, as_stream(stream),
+        [&](int64_t k, const SpanBatch &b, const SpanBatch *) {
+            const int64_t step = adam_step + k;
+            // gradients only; rows_m / rows_v still read, for the catch-up of the rows a rating names
+            if (int rc = r4r_idnet_step(variant, b.uid, b.iid, b.y, flat_p, flat_g, nullptr, nullptr, rows_p, rows_m,
+                                        rows_v, n_users, n_items, pred, se, sse_accum, ws, ws_bytes, B, L, dropout_p,
+                                        training, seed, offset + (uint64_t)k * draws_per_step, inv_denom, sw.period,
+                                        sw.base, sw.all(), lr, beta1, beta2, eps, weight_decay, step, stream))
+                return rc;
+            if (int rc = dp_dense(c, flat_p, flat_g, flat_m, flat_v, total, lr, beta1, beta2, eps, weight_decay, step,
+                                  stream))
+                return rc;
+            src[0] = (uint64_t)b.uid;
+            src[1] = (uint64_t)b.iid;
+            if (int rc = dp_fields(c, nf, src, widths, ones, B, B_pad, block, blocks, gathered, stream)) return rc;
+            if (int rc = r4r_idnet_rows_apply(variant, reinterpret_cast<const int64_t *>(gathered[0]),
+                                              reinterpret_cast<const int64_t *>(gathered[1]),
+                                              reinterpret_cast<const float *>(gathered[2]), gu, gi, sw.period, sw.base,
+                                              sw.all(), world * B_pad, rows_p, rows_m, rows_v, n_users, n_items, ws,
+                                              ws_bytes, B, L, lr, beta1, beta2, eps, weight_decay, step, stream))
+                return rc;
+            sw.done(step);
+            return R4R_OK;
+        });
+    *sweep_base = sw.base;
+    *sweep_period_out = sw.period;
+    return rc;
+}
+
+extern "C" int r4r_mf_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, int64_t *steps_done,
+                              const uint64_t *p, const uint64_t *m, const uint64_t *v, int64_t n_users,
+                              int64_t n_items, int D, float *pred, float *se, float *sse_accum, void *ws,
+                              size_t ws_bytes, float dropout_p, int training, uint64_t seed, uint64_t offset,
+                              uint64_t draws_per_step, float inv_denom, int sweep_period, int sweep_want,
+                              int64_t *sweep_base, int *sweep_period_out, float lr, double beta1, double beta2,
+                              float eps, float weight_decay, int64_t adam_step, void *allgather, void *comm, int world,
+                              int64_t B_pad, void *block, void *blocks, void *stream) {
+    if (steps_done) *steps_done = 0;
+    R4R_REQUIRE(m && v && adam_step >= 1 && sweep_base && sweep_period_out,
+                "mf_span_dp: training steps only; sweep_base / sweep_period_out are the schedule's state");
+    *sweep_period_out = sweep_period;
+    if (int rc = dp_comm_ok("mf_span_dp", false, nullptr, allgather, comm, world)) return rc;
+    const int64_t B = loader ? (int64_t)loader[26] : 0;
+    R4R_REQUIRE(ws && block && blocks && B <= B_pad && (int64_t)world * B_pad <= 16384,
+                "mf_span_dp: the exchange buffers (ws, block, blocks) and world x B_pad <= 16384, B <= B_pad");
+    const DpComm c{nullptr, allgather, comm, world, "mf_span_dp"};
+    const size_t nbytes = r4r_mf_dp_block_bytes(B_pad, D);
+    Sweep sw{sweep_period, sweep_want, *sweep_base};
+    const int rc = run_span(
+        loader, first_batch, steps, 0, nullptr, steps_done, as_stream(stream),
+        [&](int64_t k, const SpanBatch &b, const SpanBatch *) {
+            const int64_t step = adam_step + k;
+            const bool pending = D > 0 && sw.period > 1;   // (rows may carry pending updates: the forward catches them up)
+            if (int rc = r4r_mf_grad(b.uid, b.iid, b.y, p, pending ? m : nullptr, pending ? v : nullptr, n_users,
+                                     n_items, D, pred, se, block, nullptr, B, B_pad, dropout_p, training, seed,
+                                     offset + (uint64_t)k * draws_per_step, inv_denom, pending ? ws : nullptr,
+                                     sw.period, sw.base, lr, beta1, beta2, eps, weight_decay, step, stream))
+                return rc;
+            if (int rc = c.gather(block, blocks, nbytes, stream)) return rc;
+            if (int rc = r4r_mf_apply(blocks, world, B_pad, p, m, v, n_users, n_items, D, ws, ws_bytes, sw.period,
+                                      sw.base, sw.all(), se, B, sse_accum, lr, beta1, beta2, eps, weight_decay, step,
+                                      stream))
+                return rc;
+            sw.done(step);
+            return R4R_OK;
+        });
+    *sweep_base = sw.base;
+    *sweep_period_out = sw.period;
+    return rc;
+}

@@ -100,11 +100,30 @@ class _Spans:
 
     def _span_limit(self, desc, ahead=0):
         """How many consecutive steps, starting `ahead` steps from now, one call may carry (0: that step is its own)."""
-        return self.SPAN_STEPS
+        return self.SPAN_STEPS if self._span_dp_form(desc) else 0
 
     def _span_dp_ok(self):
-        """Can this engine's DATA-PARALLEL step be enqueued from C (the exchange included)?"""
-        return False
+        """Can this engine's DATA-PARALLEL step be enqueued from C (the exchange included)?  Where the job runs over the
+        package's own RCCL communicator (dist.StreamRccl): the collectives are its entry points, called on the stream."""
+        dp = getattr(self, 'dp', None)
+        return bool(dp is not None and dp.on and getattr(dp, 'stream_rccl', None) is not None and dp.stream_rccl.comm)
+
+    def _span_dp_form(self, desc):
+        """Data parallel: does a full step on `desc`'s batches exchange in the form the C side issues (the family's packed
+        blocks, r4r_<family>_span_dp)?  Otherwise -- a shard beyond hyper_params['batch_size'], the generic payload forms
+        of large batches -- the step goes through train_step.  Always true for a single process."""
+        dp = getattr(self, 'dp', None)
+        if dp is None or not dp.on:
+            return True
+        B_pad = self._dp_pad()
+        return 0 < desc.batch_size <= B_pad and self._dp_blocks_fit(B_pad * dp.world, desc)
+
+    def _dp_blocks_fit(self, entries, desc):
+        """world * B_pad gathered ratings: within the limits of the family's packed-block exchange?"""
+        return entries <= 16384
+
+    def _dp_pad(self):
+        return int(self.hp.get('batch_size', 0))             # (every rank's shard is padded to it: _train_step_dp)
 
     def train_epoch(self, reader, counts=None):
         """One epoch over ``reader`` (data.DataLoader on the device): every batch of ``reader.iter()``, in order, as
@@ -140,6 +159,14 @@ class _Spans:
         return float(desc.n_ratings), float(total)
 
 
+def _span_collectives(dp):
+    """(ncclAllReduce, ncclAllGather, communicator): the addresses a data-parallel span calls from C, on the compute
+    stream -- the package's own RCCL communicator (dist.StreamRccl), the one the per-step exchange goes through."""
+    rc = dp.stream_rccl
+    return (ctypes.cast(rc.lib.ncclAllReduce, ctypes.c_void_p).value,
+            ctypes.cast(rc.lib.ncclAllGather, ctypes.c_void_p).value, rc.comm)
+
+
 def load_named_moments(who, m, v, sd):
     """Copy a checkpoint's per-parameter Adam moments into the engine's views -- after checking every one of them (a
     missing name or a size mismatch raises before anything was written: a rejected checkpoint leaves the engine as it
@@ -165,19 +192,8 @@ def gather_entry_fields(owner, fields, n, B_pad, world, all_gather):
     [world * B_pad] / [world * B_pad, w], buffers owned by `owner` and reused from step to step."""
     lib = _lib.lib()
     nf = len(fields)
-    units = [w * (2 if dt == torch.int64 else 1) for _, w, dt in fields]
-    key = ('entry_fields', B_pad, world) + tuple((w, dt) for _, w, dt in fields)
-    cache = owner.__dict__.setdefault('_entry_field_bufs', {})
-    if key not in cache:
-        widths = (ctypes.c_int * nf)(*units)
-        nbytes = lib.r4r_dp_block_bytes(nf, widths, B_pad)
-        dev = owner.dev
-        block = torch.zeros(max(nbytes, 4), dtype=torch.uint8, device=dev)
-        blocks = block if all_gather is None else torch.zeros(world * max(nbytes, 4), dtype=torch.uint8, device=dev)
-        outs = [torch.empty((world * B_pad,) + ((w,) if w > 1 else ()), dtype=dt, device=dev) for _, w, dt in fields]
-        cache[key] = (widths, (ctypes.c_int * nf)(*[1 if dt == torch.int64 else 0 for _, _, dt in fields]), block, blocks, outs,
-                      (ctypes.c_uint64 * nf)(*[o.data_ptr() for o in outs]))
-    widths, ones, block, blocks, outs, dst = cache[key]
+    widths, ones, block, blocks, outs, dst = entry_field_buffers(owner, [(w, dt) for _, w, dt in fields], B_pad, world,
+                                                                 all_gather is not None)
     src = (ctypes.c_uint64 * nf)(*[(t.data_ptr() if n > 0 else 0) for t, _, _ in fields])
     if n > 0:
         for t, w, dt in fields:
@@ -188,6 +204,24 @@ def gather_entry_fields(owner, fields, n, B_pad, world, all_gather):
         all_gather(blocks, block)
     _lib.check(lib.r4r_dp_unpack(nf, dst, widths, ptr(blocks), world, B_pad, _lib.current_stream()), 'r4r_dp_unpack')
     return outs
+
+
+def entry_field_buffers(owner, spec, B_pad, world, gathered=True):
+    """gather_entry_fields' buffers for fields of (width, torch dtype) `spec`, owned by `owner` and reused from step to
+    step (a data-parallel span takes them from here too): -> (widths, pad_ones, block, blocks, outs, dst)."""
+    nf = len(spec)
+    key = ('entry_fields', B_pad, world) + tuple(spec)
+    cache = owner.__dict__.setdefault('_entry_field_bufs', {})
+    if key not in cache:
+        widths = (ctypes.c_int * nf)(*[w * (2 if dt == torch.int64 else 1) for w, dt in spec])
+        nbytes = _lib.lib().r4r_dp_block_bytes(nf, widths, B_pad)
+        dev = owner.dev
+        block = torch.zeros(max(nbytes, 4), dtype=torch.uint8, device=dev)
+        blocks = torch.zeros(world * max(nbytes, 4), dtype=torch.uint8, device=dev) if gathered else block
+        outs = [torch.empty((world * B_pad,) + ((w,) if w > 1 else ()), dtype=dt, device=dev) for w, dt in spec]
+        cache[key] = (widths, (ctypes.c_int * nf)(*[1 if dt == torch.int64 else 0 for _, dt in spec]), block, blocks, outs,
+                      (ctypes.c_uint64 * nf)(*[o.data_ptr() for o in outs]))
+    return cache[key]
 
 
 def pad4(E):
@@ -1022,32 +1056,65 @@ class MFEngine(_SweepSchedule, _Spans):
     def _span_ok(self, desc):
         return not desc.review and desc.batch_size <= self.MAX_TRAIN_BATCH
 
+    def _span_dp_ok(self):
+        # (the C side issues the all-gather form: not the peer-mapped exchange, not the pinned registering launch)
+        return (super()._span_dp_ok() and self.exchange != 'peer'
+                and os.environ.get('R4R_MF_DP_REGISTER', '') != '1')
+
+    def _dp_buffers(self, B_pad):
+        """pred, se, this rank's block and the gathered blocks of a data-parallel step at shards of B_pad."""
+        key = ('dp', B_pad)
+        if key not in self._out:
+            nb = _lib.lib().r4r_mf_dp_block_bytes(B_pad, self.D)
+            self._out[key] = (torch.empty(max(B_pad, 1), dtype=torch.float32, device=self.dev),
+                              torch.empty(max(B_pad, 1), dtype=torch.float32, device=self.dev),
+                              torch.zeros(nb, dtype=torch.uint8, device=self.dev),
+                              torch.zeros(self.dp.world * nb, dtype=torch.uint8, device=self.dev))
+        return self._out[key]
+
     @torch.no_grad()
     def _span(self, desc, first, steps, announce):
-        """`steps` consecutive train_step(defer_sweep=True) calls as ONE C call (r4r_mf_span)."""
+        """`steps` consecutive train_step(defer_sweep=True) calls as ONE C call (r4r_mf_span; data parallel, every rank a
+        full batch: r4r_mf_span_dp -- gradients, RCCL's all-gather of the blocks, the update, per step, from C)."""
         lib, B = _lib.lib(), desc.batch_size
-        if B not in self._out:
-            self._out[B] = (torch.empty(B, dtype=torch.float32, device=self.dev),
-                            torch.empty(B, dtype=torch.float32, device=self.dev))
-        pred, se = self._out[B]
-        ws = self._workspace(B)
+        if self.dp is not None:
+            B_pad, world = self._dp_pad(), self.dp.world
+            pred, se, block, blocks = self._dp_buffers(B_pad)
+            ws = self._workspace(world * B_pad)
+        else:
+            if B not in self._out:
+                self._out[B] = (torch.empty(B, dtype=torch.float32, device=self.dev),
+                                torch.empty(B, dtype=torch.float32, device=self.dev))
+            pred, se = self._out[B]
+            ws = self._workspace(B)
         training, p_drop = self.model.training, float(self.hp['dropout'])
         draws = B * 2 * self.D if (training and p_drop > 0.0) else 0
         want = self.sweep_period if self.has_tables else 1
         base, period, done = ctypes.c_int64(self._tb_base), ctypes.c_int(self._tb_period), ctypes.c_int64(0)
-        rc = lib.r4r_mf_span(
-            desc.words, int(first), int(steps), ctypes.byref(done), self._ptrs(self.params), self._ptrs(self.m),
-            self._ptrs(self.v), self.n_users, self.n_items, self.D, ptr(pred), ptr(se), ptr(self.sse), ptr(ws), ws.numel(),
-            p_drop, int(training), self.seed, self.offset, draws, 1.0 / float(B), self._tb_period, want,
-            ctypes.byref(base), ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-            self.step_count + 1, _lib.current_stream())
+        if self.dp is not None:
+            _, gather, comm = _span_collectives(self.dp)
+            name = 'r4r_mf_span_dp'
+            rc = lib.r4r_mf_span_dp(
+                desc.words, int(first), int(steps), ctypes.byref(done), self._ptrs(self.params), self._ptrs(self.m),
+                self._ptrs(self.v), self.n_users, self.n_items, self.D, ptr(pred), ptr(se), ptr(self.sse), ptr(ws),
+                ws.numel(), p_drop, int(training), self.seed, self.offset, draws, 1.0 / float(B * world), self._tb_period,
+                want, ctypes.byref(base), ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                self.step_count + 1, gather, comm, world, B_pad, ptr(block), ptr(blocks), _lib.current_stream())
+        else:
+            name = 'r4r_mf_span'
+            rc = lib.r4r_mf_span(
+                desc.words, int(first), int(steps), ctypes.byref(done), self._ptrs(self.params), self._ptrs(self.m),
+                self._ptrs(self.v), self.n_users, self.n_items, self.D, ptr(pred), ptr(se), ptr(self.sse), ptr(ws),
+                ws.numel(), p_drop, int(training), self.seed, self.offset, draws, 1.0 / float(B), self._tb_period, want,
+                ctypes.byref(base), ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                self.step_count + 1, _lib.current_stream())
         k = int(done.value)
         self.step_count += k
         self.offset += k * draws
         self._tb_base, self._tb_period = int(base.value), int(period.value)
         if k and want > 1:
             self._tb_used = True
-        _lib.check(rc, 'r4r_mf_span')
+        _lib.check(rc, name)
 
     @torch.no_grad()
     def _train_step_dp(self, data, y, n_global, defer=False):
@@ -1071,14 +1138,7 @@ class MFEngine(_SweepSchedule, _Spans):
             dist.all_gather_into_tensor(all_sizes, sizes, group=self.dp.group)
             B_pad = int(all_sizes.max().item())
             n_global = int(all_sizes.sum().item())
-        key = ('dp', B_pad)
-        if key not in self._out:
-            nb = lib.r4r_mf_dp_block_bytes(B_pad, self.D)
-            self._out[key] = (torch.empty(max(B_pad, 1), dtype=torch.float32, device=self.dev),
-                              torch.empty(max(B_pad, 1), dtype=torch.float32, device=self.dev),
-                              torch.zeros(nb, dtype=torch.uint8, device=self.dev),
-                              torch.zeros(world * nb, dtype=torch.uint8, device=self.dev))
-        pred, se, block, blocks = self._out[key]
+        pred, se, block, blocks = self._dp_buffers(B_pad)
         step = int(self.step_count)
         period, base, sweep_all, want = self._schedule(defer)
         ws = self._workspace(world * B_pad)
@@ -1428,7 +1488,11 @@ class NarreEngine(_ConvRule, _Spans):
 
     def _span_limit(self, desc, ahead=0):
         R, T = self._span_doc(desc)
-        return self._rule_peek(desc.batch_size * R, T, ahead)[0]
+        return self._rule_peek(desc.batch_size * R, T, ahead)[0] if self._span_dp_form(desc) else 0
+
+    def _dp_blocks_fit(self, entries, desc):
+        R = desc.doc_shape[0]                                # (NARRE's loader: R x W documents)
+        return self.BLOCKS_DP and entries * (1 + R) <= self.ROWS_APPLY_MAX and self.L <= 32   # (_dp_rows' block form)
 
     def _span_call(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
         return lib.r4r_narre_span(
@@ -1467,8 +1531,8 @@ class NarreEngine(_ConvRule, _Spans):
             buf = self._last_buf ^ 1
         draws = B * self._draws(R) if (self.model.training and float(self.hp['dropout']) > 0.0) else 0
         done = ctypes.c_int64(0)
-        rc = self._span_call(lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready,
-                             _lib.current_stream())
+        call = self._span_call if self.dp is None else self._span_call_dp   # (data parallel: every rank a full batch)
+        rc = call(lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, _lib.current_stream())
         k = int(done.value)
         self.step_count += k
         self.offset += k * draws
@@ -1478,7 +1542,24 @@ class NarreEngine(_ConvRule, _Spans):
         if rc == 0 and announce and projecting:
             nx = self._span_towers(_span_slots(desc, first + steps))
             self._prepared = (nx + (B, R, T), self._last_buf ^ 1, [_RawPtr(a, desc) for a in nx])
-        _lib.check(rc, 'r4r_%s_span' % self.C)
+        _lib.check(rc, 'r4r_%s_span%s' % (self.C, '' if self.dp is None else '_dp'))
+
+    def _span_dp_args(self, desc):
+        """The data-parallel span's exchange arguments: (inv_denom, ncclAllReduce, ncclAllGather, comm, world, B_pad)."""
+        world = self.dp.world
+        return (1.0 / float(desc.batch_size * world),) + _span_collectives(self.dp) + (world, self._dp_pad())
+
+    def _span_call_dp(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
+        inv, red, gat, comm, world, B_pad = self._span_dp_args(desc)
+        block, blocks = self._dp_blocks(B_pad, world, R, False)
+        return lib.r4r_narre_span_dp(
+            desc.words, int(first), int(steps), int(bool(announce)), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.total,
+            self._p4(self.rows), self._p4(self.rows_m), self._p4(self.rows_v), self.n_users, self.n_items, ptr(pred),
+            ptr(se), ptr(self.sse), ptr(ws), ws.numel(), R, T, self.E, self.L, float(self.hp['dropout']),
+            int(self.model.training), self.seed, self.offset, draws, inv, self._algo_req, buf, ready, self.lr,
+            self.betas[0], self.betas[1], self.eps, self.wd, self.step_count + 1, red, gat, comm, world, B_pad, ptr(block),
+            ptr(blocks), stream)
 
     # ---- data parallel (SURVEY 8e): gradients only on this rank (the C step with flat_m = NULL), C1 -- one
     # all-reduce of the flat dense gradient + the flat Adam -- and C2: the ranks' compact ID rows gathered
@@ -1592,12 +1673,7 @@ class NarreEngine(_ConvRule, _Spans):
         R, T = self._dp_doc_shape(data)
         if self.BLOCKS_DP and 0 < world * B_pad * (1 + R) <= self.ROWS_APPLY_MAX and self.L <= 32:
             lib = _lib.lib()
-            key = ('dp_blocks', B_pad, world, R)
-            if key not in self._out:
-                nb_bytes = lib.r4r_narre_dp_block_bytes(B_pad, R, self.L)
-                block = torch.zeros(nb_bytes, dtype=torch.uint8, device=self.dev)
-                self._out[key] = (block, block if solo else torch.zeros(world * nb_bytes, dtype=torch.uint8, device=self.dev))
-            block, blocks = self._out[key]
+            block, blocks = self._dp_blocks(B_pad, world, R, solo)
             nb = max(n, 1)                                   # (the workspace of this rank's own shape holds the row tags)
             ws = self._workspace(nb, R, T)
             _lib.check(lib.r4r_narre_dp_block(ptr(ws), ws.numel(), n, R, T, self.E, self.L, self.V, self.n_users, self.n_items,
@@ -1625,6 +1701,15 @@ class NarreEngine(_ConvRule, _Spans):
         nb = max(n, 1)                                       # (the workspace of this rank's own shape holds the row tags)
         self._dp_apply(all_ids.view(world * B_pad, id_cols), all_vals.view(world * B_pad, val_cols), world * B_pad,
                        self._workspace(nb, R, T), nb, R, T)
+
+    def _dp_blocks(self, B_pad, world, R, solo):
+        """This rank's packed block and the gathered blocks (one buffer when solo) of the block-form exchange."""
+        key = ('dp_blocks', B_pad, world, R)
+        if key not in self._out:
+            nb_bytes = _lib.lib().r4r_narre_dp_block_bytes(B_pad, R, self.L)
+            block = torch.zeros(nb_bytes, dtype=torch.uint8, device=self.dev)
+            self._out[key] = (block, block if solo else torch.zeros(world * nb_bytes, dtype=torch.uint8, device=self.dev))
+        return self._out[key]
 
     @step_or_nothing
     @torch.no_grad()
@@ -1732,7 +1817,7 @@ class DeepCoNNPPEngine(NarreEngine):
     def _dp_rows(self, data, n, B_pad, world, solo):
         """(uid, iid, d loss / d pred) per rating: one packing launch, ONE all_gather, one unpacking launch, the update."""
         R, T = self._dp_doc_shape(data)
-        fields = [(None, 1, torch.int64), (None, 1, torch.int64), (None, 1, torch.float32)]
+        fields = [(None, w, dt) for w, dt in self.ENTRY_SPEC]
         if n > 0:
             f = self._fields(data)[0]
             off = self._ws_offset(n, R, T, 5)
@@ -1770,6 +1855,23 @@ class DeepCoNNPPEngine(NarreEngine):
             ptr(self.sse), ptr(ws), ws.numel(), T, self.E, self.L, float(self.hp['dropout']), int(self.model.training),
             self.seed, self.offset, draws, 1.0 / float(desc.batch_size), self._algo_req, buf, ready, self.lr,
             self.betas[0], self.betas[1], self.eps, self.wd, self.step_count + 1, stream)
+
+    def _dp_blocks_fit(self, entries, desc):
+        return entries <= self.ROWS_APPLY_MAX                # (r4r_deepconnpp_rows_apply's limit)
+
+    ENTRY_SPEC = [(1, torch.int64), (1, torch.int64), (1, torch.float32)]   # uid, iid, d loss / d pred
+
+    def _span_call_dp(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
+        inv, red, gat, comm, world, B_pad = self._span_dp_args(desc)
+        _, _, block, blocks, _, dst = entry_field_buffers(self, self.ENTRY_SPEC, B_pad, world)   # (_dp_rows' buffers)
+        p2 = lambda ts: (ctypes.c_uint64 * 2)(*[t.data_ptr() for t in ts])   # noqa: E731
+        return lib.r4r_deepconnpp_span_dp(
+            desc.words, int(first), int(steps), int(bool(announce)), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.total,
+            p2(self.rows), p2(self.rows_m), p2(self.rows_v), self.n_users, self.n_items, ptr(pred), ptr(se),
+            ptr(self.sse), ptr(ws), ws.numel(), T, self.E, self.L, float(self.hp['dropout']), int(self.model.training),
+            self.seed, self.offset, draws, inv, self._algo_req, buf, ready, self.lr, self.betas[0], self.betas[1],
+            self.eps, self.wd, self.step_count + 1, red, gat, comm, world, B_pad, ptr(block), ptr(blocks), dst, stream)
 
     def _ws_bytes(self, B, R, T):
         return _lib.lib().r4r_deepconnpp_ws_bytes(B, T, self.E, self.L, self.V, self.n_users, self.n_items)
@@ -1888,6 +1990,28 @@ class TransNetEngine(NarreEngine, _SweepSchedule):
             self._tb_used = True
         return rc
 
+    def _dp_blocks_fit(self, entries, desc):
+        return not self.plus or entries <= self.BLOCKS_MAX_ENTRIES   # (_dp_rows' block form; plain TransNet: no rows)
+
+    def _span_call_dp(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
+        inv, red, gat, comm, world, B_pad = self._span_dp_args(desc)
+        block, blocks = self._dp_blocks(B_pad, world, R, False) if self.plus else (None, None)
+        p2 = lambda ts: (ctypes.c_uint64 * 2)(*[t.data_ptr() for t in ts]) if ts else None   # noqa: E731
+        want = self.sweep_period if self.has_tables else 1   # (main.train: defer_sweep=True for this family)
+        base, period = ctypes.c_int64(self._tb_base), ctypes.c_int(self._tb_period)
+        rc = lib.r4r_transnet_span_dp(
+            desc.words, int(first), int(steps), int(bool(announce)), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), self.total,
+            p2(self.rows), p2(self.rows_m), p2(self.rows_v), self.n_users, self.n_items, ptr(pred), ptr(se),
+            ptr(self.sse), ptr(ws), ws.numel(), T, self.E, self.L, self.plus, float(self.hp['dropout']),
+            int(self.model.training), self.seed, self.offset, draws, inv, self._algo_req, buf, ready, self._tb_period,
+            want, ctypes.byref(base), ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+            self.step_count + 1, red, gat, comm, world, B_pad, ptr(block), ptr(blocks), stream)
+        self._tb_base, self._tb_period = int(base.value), int(period.value)
+        if int(done.value) and want > 1:
+            self._tb_used = True
+        return rc
+
     def _ws_bytes(self, B, R, T):
         return _lib.lib().r4r_transnet_ws_bytes(B, T, self.E, self.L, self.plus, self.V, self.n_users, self.n_items)
 
@@ -1995,12 +2119,7 @@ class TransNetEngine(NarreEngine, _SweepSchedule):
             return super()._dp_rows(data, n, B_pad, world, solo)
         lib = _lib.lib()
         R, T = self._dp_doc_shape(data)
-        key = ('dp_blocks', B_pad, world)
-        if key not in self._out:
-            nb_bytes = lib.r4r_transnet_dp_block_bytes(B_pad)
-            block = torch.zeros(nb_bytes, dtype=torch.uint8, device=self.dev)
-            self._out[key] = (block, block if solo else torch.zeros(world * nb_bytes, dtype=torch.uint8, device=self.dev))
-        block, blocks = self._out[key]
+        block, blocks = self._dp_blocks(B_pad, world, R, solo)
         nb = max(n, 1)                                       # (the workspace of this rank's own shape holds the sweep's state)
         ws = self._workspace(nb, R, T)
         uid = iid = None
@@ -2018,6 +2137,14 @@ class TransNetEngine(NarreEngine, _SweepSchedule):
             ptr(blocks), world, B_pad, period, base, sweep_all, p2(self.rows), p2(self.rows_m), p2(self.rows_v),
             self.n_users, self.n_items, ptr(ws), ws.numel(), nb, T, self.E, self.L, self.V, self.lr, self.betas[0],
             self.betas[1], self.eps, self.wd, int(self.step_count), _lib.current_stream()), 'r4r_transnet_rows_apply_blocks')
+
+    def _dp_blocks(self, B_pad, world, R, solo):
+        key = ('dp_blocks', B_pad, world)
+        if key not in self._out:
+            nb_bytes = _lib.lib().r4r_transnet_dp_block_bytes(B_pad)
+            block = torch.zeros(nb_bytes, dtype=torch.uint8, device=self.dev)
+            self._out[key] = (block, block if solo else torch.zeros(world * nb_bytes, dtype=torch.uint8, device=self.dev))
+        return self._out[key]
 
     def _dp_payload(self, f, n, R, T, ids, vals):
         ws = self._workspace(n, R, T)
@@ -2232,9 +2359,14 @@ class IdNetEngine(_SweepSchedule, _Spans):
     def _span_ok(self, desc):
         return not desc.review and desc.batch_size <= self.MAX_TRAIN_BATCH
 
+    def _entry_spec(self):
+        """_train_step_dp's gathered fields: uid, iid, d loss / d pred, the compact rows of every table."""
+        return [(1, torch.int64), (1, torch.int64), (1, torch.float32)] + [(self.L, torch.float32)] * len(self.tables)
+
     @torch.no_grad()
     def _span(self, desc, first, steps, announce):
-        """`steps` consecutive train_step(defer_sweep=True) calls as ONE C call (r4r_idnet_span)."""
+        """`steps` consecutive train_step(defer_sweep=True) calls as ONE C call (r4r_idnet_span; data parallel, every rank
+        a full batch: r4r_idnet_span_dp -- gradients, RCCL's all-reduce and all-gather, the updates, per step, from C)."""
         lib, B = _lib.lib(), desc.batch_size
         if B not in self._out:
             self._out[B] = (torch.empty(B, dtype=torch.float32, device=self.dev),
@@ -2245,20 +2377,34 @@ class IdNetEngine(_SweepSchedule, _Spans):
         draws = B * self.draws() if (training and p_drop > 0.0) else 0
         want = self.sweep_period
         base, period, done = ctypes.c_int64(self._tb_base), ctypes.c_int(self._tb_period), ctypes.c_int64(0)
-        rc = lib.r4r_idnet_span(
-            desc.words, int(first), int(steps), ctypes.byref(done), self.variant, ptr(self.flat_p), ptr(self.flat_g),
-            ptr(self.flat_m), ptr(self.flat_v), self._p6(self.rows), self._p6(self.rows_m), self._p6(self.rows_v),
-            self.n_users, self.n_items, ptr(pred), ptr(se), ptr(self.sse), ptr(ws), ws.numel(), self.L, p_drop,
-            int(training), self.seed, self.offset, draws, 1.0 / float(B), self._tb_period, want, ctypes.byref(base),
-            ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count + 1,
-            _lib.current_stream())
+        if self.dp is not None:
+            world, B_pad = self.dp.world, self._dp_pad()
+            red, gat, comm = _span_collectives(self.dp)
+            _, _, block, blocks, _, dst = entry_field_buffers(self, self._entry_spec(), B_pad, world)   # (_train_step_dp's)
+            name = 'r4r_idnet_span_dp'
+            rc = lib.r4r_idnet_span_dp(
+                desc.words, int(first), int(steps), ctypes.byref(done), self.variant, ptr(self.flat_p), ptr(self.flat_g),
+                ptr(self.flat_m), ptr(self.flat_v), self.total, self._p6(self.rows), self._p6(self.rows_m),
+                self._p6(self.rows_v), self.n_users, self.n_items, ptr(pred), ptr(se), ptr(self.sse), ptr(ws), ws.numel(),
+                self.L, p_drop, int(training), self.seed, self.offset, draws, 1.0 / float(B * world), self._tb_period, want,
+                ctypes.byref(base), ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                self.step_count + 1, red, gat, comm, world, B_pad, ptr(block), ptr(blocks), dst, _lib.current_stream())
+        else:
+            name = 'r4r_idnet_span'
+            rc = lib.r4r_idnet_span(
+                desc.words, int(first), int(steps), ctypes.byref(done), self.variant, ptr(self.flat_p), ptr(self.flat_g),
+                ptr(self.flat_m), ptr(self.flat_v), self._p6(self.rows), self._p6(self.rows_m), self._p6(self.rows_v),
+                self.n_users, self.n_items, ptr(pred), ptr(se), ptr(self.sse), ptr(ws), ws.numel(), self.L, p_drop,
+                int(training), self.seed, self.offset, draws, 1.0 / float(B), self._tb_period, want, ctypes.byref(base),
+                ctypes.byref(period), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count + 1,
+                _lib.current_stream())
         k = int(done.value)
         self.step_count += k
         self.offset += k * draws
         self._tb_base, self._tb_period = int(base.value), int(period.value)
         if k and want > 1:
             self._tb_used = True
-        _lib.check(rc, 'r4r_idnet_span')
+        _lib.check(rc, name)
 
     @step_or_nothing
     @torch.no_grad()
