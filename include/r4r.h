@@ -62,6 +62,12 @@ int r4r_textcnn_fwd(const float *table, int64_t V, const int64_t *idx,
  * R4R_CONV_AUTO rule and the R4R_CONV_ALGO environment pin applied). */
 int r4r_conv_algo(int requested, int64_t N, int T, int E, int F);
 
+/* The request r4r_textcnn_fwd resolves its algorithm from (A/B runs and tests): R4R_CONV_AUTO (the default),
+ * R4R_CONV_DIRECT or R4R_CONV_PROJECT, passed through r4r_conv_algo's rule -- the R4R_CONV_ALGO environment pin
+ * still wins.  Process-wide, like r4r_gemm_form; the fused engines are not affected (they pass their own
+ * conv_algo).  Returns the previous request, or R4R_ERR_ARG for any other value. */
+int r4r_textcnn_algo(int requested);
+
 /* The MEASURED rule behind the engines' automatic choice: project-then-gather's work follows the batch's
  * DISTINCT tokens, the direct conv's its positions.  `rows`: distinct tokens of a batch summed over its
  * towers (left by the gather kernel next to each tower's token counter: the int after it), `docs`:

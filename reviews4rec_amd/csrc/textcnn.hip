@@ -419,6 +419,9 @@ extern "C" size_t r4r_textcnn_ws_bytes(int64_t N, int T, int E, int F, int64_t V
     return m > proj ? m : proj;
 }
 
+// The request r4r_textcnn_fwd passes to textcnn_pick_algo (r4r_textcnn_algo: A/B runs and tests).
+static int g_textcnn_algo = R4R_CONV_AUTO;
+
 static int check_tower_args(const void *table, int64_t V, const void *idx, int64_t N, int T, int E, int F) {
     R4R_REQUIRE(table && idx, "textcnn: null table/idx");
     R4R_REQUIRE(V > 0 && N >= 0 && T > 0, "textcnn: bad sizes V=%lld N=%lld T=%d", (long long)V, (long long)N, T);
@@ -447,7 +450,7 @@ extern "C" int r4r_textcnn_fwd(const float *table, int64_t V, const int64_t *idx
     const size_t tiles128 = (size_t)(T + 2 + 127) / 128;
     float *pmax = reinterpret_cast<float *>(take((size_t)N * tiles128 * NP * 4));
     int *parg = reinterpret_cast<int *>(take((size_t)N * tiles128 * NP * 4));
-    if (textcnn_pick_algo(R4R_CONV_AUTO, N, T, E, F) == R4R_CONV_PROJECT) {
+    if (textcnn_pick_algo(g_textcnn_algo, N, T, E, F) == R4R_CONV_PROJECT) {
         ProjTower pt;
         pt.idx = idx; pt.conv_w = conv_w; pt.conv_b = conv_b; pt.pmax = pmax; pt.parg = parg;
         pt.flags = reinterpret_cast<int *>(take((size_t)(V + 4) * 4));
@@ -473,6 +476,14 @@ extern "C" int r4r_textcnn_fwd(const float *table, int64_t V, const int64_t *idx
 // per-algorithm state (prepared token buffers) ask instead of restating the rule.
 extern "C" int r4r_conv_algo(int requested, int64_t N, int T, int E, int F) {
     return textcnn_pick_algo(requested, N, T, E, F);
+}
+
+extern "C" int r4r_textcnn_algo(int requested) {
+    R4R_REQUIRE(requested == R4R_CONV_AUTO || requested == R4R_CONV_DIRECT || requested == R4R_CONV_PROJECT,
+                "textcnn_algo: request %d (0 auto, 1 direct, 2 project)", requested);
+    const int prev = g_textcnn_algo;
+    g_textcnn_algo = requested;
+    return prev;
 }
 
 // Measured rule: given what a batch actually holds -- `rows` distinct tokens (summed over the towers)

@@ -169,3 +169,20 @@ def test_conv_pick_reproduces_the_measured_decisions():
     assert lib.r4r_conv_algo(0, 128, 1000, 300, 100) == PROJECT and lib.r4r_conv_algo(0, 8, 100, 64, 100) == DIRECT
     assert lib.r4r_conv_algo(1, 128, 1000, 300, 100) == DIRECT and lib.r4r_conv_algo(2, 8, 100, 64, 100) == PROJECT
     assert lib.r4r_conv_algo(2, 128, 1000, 300, 64) == DIRECT
+
+
+def test_textcnn_algo_hook_sets_and_returns_the_request():
+    """r4r_textcnn_algo: the request r4r_textcnn_fwd resolves (tests and A/B runs); returns the previous one, refuses
+    anything but auto / direct / project, and leaves r4r_conv_algo -- what the engines consult -- unchanged."""
+    from reviews4rec_amd import _lib
+    lib = _lib.lib()
+    try:
+        assert lib.r4r_textcnn_algo(1) == 0
+        assert lib.r4r_textcnn_algo(2) == 1
+        assert lib.r4r_textcnn_algo(3) == -1 and b'textcnn_algo' in lib.r4r_last_error()
+        assert lib.r4r_textcnn_algo(-1) == -1
+        if 'R4R_CONV_ALGO' not in os.environ:                 # (the hook asks for project: the engines' rule is unmoved)
+            assert lib.r4r_conv_algo(0, 8, 100, 64, 100) == 1
+        assert lib.r4r_textcnn_algo(0) == 2
+    finally:
+        lib.r4r_textcnn_algo(0)
