@@ -987,6 +987,69 @@ int r4r_mf_span_dp(const uint64_t *loader, int64_t first_batch, int64_t steps, i
                    float eps, float weight_decay, int64_t adam_step, void *allgather, void *comm, int world,
                    int64_t B_pad, void *block, void *blocks, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Scoring spans: the forward-only launches of a validation / test / ranking pass, many per host call (csrc/span.hip).
+ * Replaces  the loop of evaluate()          eval.py:24-40   for data, y in reader.iter(eval=True): model(data), criterion
+ *           the loop of eval_ranking()      eval.py:64-78   for data, y in reader.iter_negs(): model(data)
+ *           iter_negs' per-slice id lists   data.py:375-447 (six candidates per ranking row, the POSITIVE item's
+ *                                                            overlap indices and reviewer list for all six)
+ *           the batcher's slices            data_fast.py:99-109
+ * `loader`: the R4R_LOADER_WORDS words of "Spans" above, every word with its meaning; n = word 26 is the LAUNCH size
+ * (ratings scored per step, any size the caller's ring was made for -- not necessarily the training batch), and for
+ * scoring only word 15 (y) may be 0: pure prediction, nothing is written to se_out.  Ranking rows are a descriptor
+ * over the flattened candidates (N = 6 x rows, n a multiple of 6, word 15 = 0); `nb_item` (int64 [N], nullable) is
+ * r4r_batch_build's: the item whose reviewer list is reported (data.py:398: the row's positive), NULL = i.
+ * Launch k scores ratings [(first_launch + k) n, + n): its group (and the next launch's) is brought into the ring as a
+ * training span does, then the family's own r4r_*_step runs in the form a per-launch caller's eval forward passes --
+ * no gradients, no moments, training 0, tokens_ready 0, no next batch, inv_denom 1, adam_step 0, y = the slice of
+ * word 15 or NULL -- with pred / se = pred_out + k n / se_out + k n of split-sized device arrays: the same kernels
+ * with the same arguments, so every score keeps its bits.  token_buffer: launch 0's; launch k uses token_buffer ^
+ * (k & 1) (DeepCoNN: only if token_alternate, else the same buffer every launch -- the other one holds an announced
+ * batch).  DeepCoNN's sse_accum (nullable) += the sum of every launch's se, as its r4r_deepconn_step does.
+ * TransNet(++): after each launch with ratings the per-rating (target SE, transform distance) pair -- columns 1:3 of
+ * the workspace's [n, 3] (r4r_transnet_ws_offset which = 3) -- is copied to aux_out + k n 2; the other families
+ * ignore aux_out.  Only the N / n full launches are reachable (a ragged tail goes through the per-step entry).
+ * Refused before anything is enqueued (launches_done = 0): a launch range beyond N / n, NARRE with R != 10, a
+ * resident table (word 27) together with nb_item, documents that are not the ring's, se_out NULL while word 15 is
+ * set, aux_out NULL on TransNet.  The training entries above keep refusing a descriptor without y.
+ *
+ * r4r_rank_top1: HR@1's count (eval.py:79-88) over finished scores [rows, C] fp32, column 0 the positive, 2 <= C <=
+ * 64.  counts (int64 [2], device) -- counts[0] += rows whose positive is STRICTLY greater than every other column;
+ * counts[1] += rows that are UNDECIDED: the positive equals the maximum of the others, or the row holds a NaN (how
+ * torch.topk orders those is the host's to decide).  Integer atomics only: the result does not depend on order. */
+int r4r_rank_top1(const float *scores, int64_t rows, int C, int64_t *counts, void *stream);
+int r4r_deepconn_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                            int64_t *built_group, int64_t *launches_done, const float *table, int64_t V,
+                            float *flat_p, float *sse_accum, void *ws, size_t ws_bytes, int T, int E, int L,
+                            float dropout_p, uint64_t seed, uint64_t offset, int conv_algo, int token_buffer,
+                            int token_alternate, float *pred_out, float *se_out, float *aux_out, void *stream);
+int r4r_deepconnpp_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                              int64_t *built_group, int64_t *launches_done, const float *table, int64_t V,
+                              float *flat_p, const uint64_t *rows_p, int64_t n_users, int64_t n_items, void *ws,
+                              size_t ws_bytes, int T, int E, int L, float dropout_p, uint64_t seed, uint64_t offset,
+                              int conv_algo, int token_buffer, float *pred_out, float *se_out, float *aux_out,
+                              void *stream);
+int r4r_narre_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                         int64_t *built_group, int64_t *launches_done, const float *table, int64_t V, float *flat_p,
+                         const uint64_t *rows_p, int64_t n_users, int64_t n_items, void *ws, size_t ws_bytes, int R,
+                         int T, int E, int L, float dropout_p, uint64_t seed, uint64_t offset, int conv_algo,
+                         int token_buffer, float *pred_out, float *se_out, float *aux_out, void *stream);
+int r4r_transnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                            int64_t *built_group, int64_t *launches_done, const float *table, int64_t V,
+                            float *flat_p, const uint64_t *rows_p, int64_t n_users, int64_t n_items, void *ws,
+                            size_t ws_bytes, int T, int E, int L, int plus, float dropout_p, uint64_t seed,
+                            uint64_t offset, int conv_algo, int token_buffer, float *pred_out, float *se_out,
+                            float *aux_out, void *stream);
+int r4r_mf_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                      int64_t *built_group, int64_t *launches_done, const uint64_t *p, int64_t n_users,
+                      int64_t n_items, int D, void *ws, size_t ws_bytes, float dropout_p, uint64_t seed,
+                      uint64_t offset, float *pred_out, float *se_out, float *aux_out, void *stream);
+int r4r_idnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                         int64_t *built_group, int64_t *launches_done, int variant, float *flat_p,
+                         const uint64_t *rows_p, int64_t n_users, int64_t n_items, void *ws, size_t ws_bytes, int L,
+                         float dropout_p, uint64_t seed, uint64_t offset, float *pred_out, float *se_out,
+                         float *aux_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@
 // its per-step values (batch pointers, Adam step, dropout stream position, token buffer, sweep
 // schedule) advanced here exactly as reviews4rec_amd/engine.py advances them between two
 // train_step calls.  Host code only: every kernel is the one the per-step entry points launch, so
-// a span and K single steps give identical bits (tests/test_gpu_span.py).
+// a span and K single steps give identical bits (tests/test_gpu_span.py).  The forward-only counterpart -- the
+// scoring spans of a validation / ranking pass -- is at the end of the file.
 //
 // Why groups: one r4r_batch_build is a chain of four dependent loads (rating -> owner -> review
 // offsets -> tokens), ~6 us whatever it builds; G batches per launch cost little more than one,
@@ -42,7 +43,8 @@ struct SpanBatch {                                          // device pointers o
     const float *y;
 };
 
-static int decode_loader(const uint64_t *w, SpanLoader &L) {
+// scoring: a forward-only pass (the scoring spans below) -- word 15 may be 0, there is nothing to train on.
+static int decode_loader(const uint64_t *w, SpanLoader &L, bool scoring = false) {
     R4R_REQUIRE(w, "span: null loader descriptor");
     auto p32 = [&](int k) { return reinterpret_cast<const int32_t *>(w[k]); };
     auto p64 = [&](int k) { return reinterpret_cast<const int64_t *>(w[k]); };
@@ -61,7 +63,7 @@ static int decode_loader(const uint64_t *w, SpanLoader &L) {
         R4R_REQUIRE(!L.ring && L.G > 0 && L.B > 0 && L.N >= 0, "span: a resident descriptor has a table of G > 0 batches and no ring");
         return R4R_OK;
     }
-    R4R_REQUIRE(L.u && L.i && L.y && L.N >= 0 && L.B > 0, "span: the descriptor needs u, i, y and a batch size");
+    R4R_REQUIRE(L.u && L.i && (L.y || scoring) && L.N >= 0 && L.B > 0, "span: the descriptor needs u, i, y and a batch size");
     if (L.review) {
         R4R_REQUIRE(L.G > 0 && L.stride >= L.G * L.B * (3 * L.doc() + 2 * NB),
                     "span: ring stride %lld < a group of %lld x %lld ratings", (long long)L.stride, (long long)L.G,
@@ -71,10 +73,11 @@ static int decode_loader(const uint64_t *w, SpanLoader &L) {
     return R4R_OK;
 }
 
-static int build_group(const SpanLoader &L, int64_t g, hipStream_t st) {
+// nb_item: r4r_batch_build's (the negatives' rows report the POSITIVE item's reviewers, data.py:398); null: i.
+static int build_group(const SpanLoader &L, int64_t g, hipStream_t st, const int64_t *nb_item = nullptr) {
     const int64_t at = g * L.G * L.B, n = L.group_ratings(g);
     return r4r_batch_build(L.user_tok, L.user_rev_off, L.user_first, L.user_nb, L.item_tok, L.item_rev_off,
-                           L.item_first, L.item_nb, L.held_tok, L.held_off, L.u + at, L.i + at, L.i + at, L.ku + at,
+                           L.item_first, L.item_nb, L.held_tok, L.held_off, L.u + at, L.i + at, (nb_item ? nb_item : L.i) + at, L.ku + at,
                            L.ki + at, L.held + at, L.train, L.ring + (g & 1) * L.stride, n, L.T, L.R, L.W, L.pad_user,
                            L.pad_item, st);
 }
@@ -88,7 +91,7 @@ static SpanBatch batch_at(const SpanLoader &L, int64_t b) {
         s.uid = p64(5); s.iid = p64(6); s.y = reinterpret_cast<const float *>(t[7]);
         return s;
     }
-    s.uid = L.u + b * L.B; s.iid = L.i + b * L.B; s.y = L.y + b * L.B;
+    s.uid = L.u + b * L.B; s.iid = L.i + b * L.B; s.y = L.y ? L.y + b * L.B : nullptr;
     if (!L.review) return s;
     const int64_t g = b / L.G, j = b - g * L.G, n = L.group_ratings(g), doc = L.doc();
     const int64_t *base = L.ring + (g & 1) * L.stride;
@@ -138,10 +141,11 @@ static int run_span(const uint64_t *loader, int64_t first_batch, int64_t steps, 
 // NB neighbour ids per side) against those the descriptor's ring holds -- checked before anything is enqueued: the
 // step indexes the ring's blocks by ITS shape, so a mismatch reads tokens as ids and writes row tags out of bounds.
 // A resident table (word 27) carries no shape; NARRE's step still reads b*R + r of its NB-wide neighbour lists.
-static int check_doc_shape(const uint64_t *loader, const char *who, int R, int T, int64_t *steps_done) {
+static int check_doc_shape(const uint64_t *loader, const char *who, int R, int T, int64_t *steps_done,
+                           bool scoring = false) {
     if (steps_done) *steps_done = 0;
     SpanLoader L;
-    if (int rc = decode_loader(loader, L)) return rc;
+    if (int rc = decode_loader(loader, L, scoring)) return rc;
     R4R_REQUIRE(R == 0 || R == NB, "%s: R = %d reviews, but the loader holds %d neighbour ids per rating", who, R, NB);
     if (L.resident) return R4R_OK;
     R4R_REQUIRE(L.review, "%s: the descriptor is an ids-only loader, the step reads documents", who);
@@ -700,4 +704,242 @@ extern "C" int r4r_mf_span_dp(const uint64_t *loader, int64_t first_batch, int64
     *sweep_base = sw.base;
     *sweep_period_out = sw.period;
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Scoring spans (include/r4r.h, "Scoring spans"): the forward-only counterpart -- eval.py:24-40 / 64-78's loop body,
+//     for data, y in reader.iter(eval=True) / iter_negs(): output = model(data); criterion(output, y)
+// enqueued from C for consecutive FULL launches of n ratings of a split (or of the ranking rows, six candidates per
+// row, flattened).  Launch k is the family's own r4r_*_step in the form engine.predict calls it (no gradients, no
+// moments, training 0, tokens_ready 0, no next batch), writing pred / se at k * n of split-sized arrays: the kernels
+// and their arguments are the per-launch path's, so every score keeps its bits (tests/test_gpu_score_span.py).
+// The only kernels of this file are the two small ones below: TransNet's per-rating pair out of the workspace, and
+// the HR@1 count over the finished scores.
+namespace r4r {
+
+template <class Launch>
+static int run_score(const char *who, const uint64_t *loader, const int64_t *nb_item, int64_t first, int64_t launches,
+                     int64_t *built_group, int64_t *launches_done, const float *se_out, hipStream_t st, Launch launch) {
+    if (launches_done) *launches_done = 0;
+    SpanLoader L;
+    if (int rc = decode_loader(loader, L, /*scoring=*/true)) return rc;
+    R4R_REQUIRE(first >= 0 && launches >= 0 && first + launches <= L.full_batches(),
+                "%s: launches %lld .. %lld of %lld full ones", who, (long long)first, (long long)(first + launches),
+                (long long)L.full_batches());
+    R4R_REQUIRE(!(L.resident && nb_item), "%s: a resident table holds built batches, nb_item has nothing to build", who);
+    bool rated = L.y != nullptr;
+    if (L.resident)
+        for (int64_t j = 0; j < L.G && !rated; ++j) rated = L.resident[j * 8 + 7] != 0;
+    R4R_REQUIRE(!rated || se_out, "%s: the descriptor has ratings (y), se_out cannot be null", who);
+    R4R_REQUIRE(!L.review || built_group, "%s: built_group is the ring's state, it cannot be null", who);
+    auto need = [&](int64_t b) -> int {                     // (as run_span's: groups in order, the next before it is read)
+        if (!L.review) return R4R_OK;
+        const int64_t g = b / L.G;
+        if (*built_group >= g) return R4R_OK;
+        if (int rc = build_group(L, g, st, nb_item)) return rc;
+        *built_group = g;
+        return R4R_OK;
+    };
+    for (int64_t k = 0; k < launches; ++k) {
+        const int64_t b = first + k;
+        if (int rc = need(b)) return rc;
+        if (k + 1 < launches)
+            if (int rc = need(b + 1)) return rc;
+        if (int rc = launch(k, batch_at(L, b), L.B)) return rc;
+        if (launches_done) *launches_done = k + 1;
+    }
+    return R4R_OK;
+}
+
+// TransNet: columns 1:3 of the workspace's per-rating [n, 3] (target prediction | its SE | transform distance).
+__global__ void score_aux_kernel(const float *__restrict__ aux3, float *__restrict__ out2, int64_t n) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n) {
+        out2[2 * r] = aux3[3 * r + 1];
+        out2[2 * r + 1] = aux3[3 * r + 2];
+    }
+}
+
+// HR@1 (eval.py:79-88) without the scores leaving the device.  One row per lane, 64 rows per wave and pass; a row is
+// a HIT when its positive (column 0) is strictly greater than every other column, UNDECIDED when it equals the best of
+// the others or the row holds a NaN (torch.topk's tie / NaN order decides those on the host).  Counts are summed per
+// wave from the ballots, per workgroup through LDS, then one integer atomic pair: order-independent.
+template <int CT>
+__global__ void __launch_bounds__(256) rank_top1_kernel(const float *__restrict__ scores, int64_t rows, int C,
+                                                         unsigned long long *__restrict__ counts) {
+    __shared__ unsigned int part[2][4];
+    unsigned int hits = 0, open = 0;                        // wave-uniform
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t passes = (rows + stride - 1) / stride;
+    for (int64_t p = 0; p < passes; ++p) {
+        const int64_t r = p * stride + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        bool hit = false, und = false;
+        if (r < rows) {
+            const float *s = scores + r * (CT ? CT : C);
+            float pos, best = -INFINITY;
+            bool nan = false;
+            if (CT == 6) {                                  // the product's shape: three 8-byte loads (24-byte rows)
+                const float2 a = reinterpret_cast<const float2 *>(s)[0], b = reinterpret_cast<const float2 *>(s)[1],
+                             c = reinterpret_cast<const float2 *>(s)[2];
+                pos = a.x;
+                const float o[5] = {a.y, b.x, b.y, c.x, c.y};
+#pragma unroll
+                for (int j = 0; j < 5; ++j) { nan |= o[j] != o[j]; best = fmaxf(best, o[j]); }
+            } else {
+                pos = s[0];
+                for (int j = 1; j < C; ++j) { const float o = s[j]; nan |= o != o; best = fmaxf(best, o); }
+            }
+            nan |= pos != pos;
+            hit = !nan && pos > best;
+            und = nan || pos == best;
+        }
+        hits += (unsigned int)__popcll(__ballot(hit));
+        open += (unsigned int)__popcll(__ballot(und));
+    }
+    const int wave = threadIdx.x / WAVE;
+    if (threadIdx.x % WAVE == 0) { part[0][wave] = hits; part[1][wave] = open; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(&counts[0], (unsigned long long)part[0][0] + part[0][1] + part[0][2] + part[0][3]);
+        atomicAdd(&counts[1], (unsigned long long)part[1][0] + part[1][1] + part[1][2] + part[1][3]);
+    }
+}
+
+}  // namespace r4r
+
+extern "C" int r4r_rank_top1(const float *scores, int64_t rows, int C, int64_t *counts, void *stream) {
+    R4R_REQUIRE(counts && rows >= 0 && C >= 2 && C <= 64, "rank_top1: counts, rows >= 0 and 2 <= C <= 64 (got %d)", C);
+    if (rows == 0) return R4R_OK;
+    R4R_REQUIRE(scores, "rank_top1: null scores");
+    const int64_t blocks = cdiv(rows, 256);
+    const unsigned grid = (unsigned)(blocks < 1024 ? blocks : 1024);
+    auto *c = reinterpret_cast<unsigned long long *>(counts);
+    // (the 8-byte loads of the six-column form need the rows 8-byte aligned: 24-byte rows from an 8-byte aligned base)
+    if (C == 6 && reinterpret_cast<uintptr_t>(scores) % 8 == 0)
+        rank_top1_kernel<6><<<grid, 256, 0, as_stream(stream)>>>(scores, rows, C, c);
+    else
+        rank_top1_kernel<0><<<grid, 256, 0, as_stream(stream)>>>(scores, rows, C, c);
+    return check_launch("rank_top1");
+}
+
+extern "C" int r4r_deepconn_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch,
+                                       int64_t launches, int64_t *built_group, int64_t *launches_done,
+                                       const float *table, int64_t V, float *flat_p, float *sse_accum, void *ws,
+                                       size_t ws_bytes, int T, int E, int L, float dropout_p, uint64_t seed,
+                                       uint64_t offset, int conv_algo, int token_buffer, int token_alternate,
+                                       float *pred_out, float *se_out, float *aux_out, void *stream) {
+    (void)aux_out;
+    if (int rc = check_doc_shape(loader, "deepconn_span_score", 0, T, launches_done, true)) return rc;
+    R4R_REQUIRE(pred_out, "deepconn_span_score: null pred_out");
+    return run_score("deepconn_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+                     as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+                         return r4r_deepconn_step(table, V, c.user_doc, c.item_doc, c.y, flat_p, nullptr, pred_out + k * n,
+                                                  se_out ? se_out + k * n : nullptr, c.y ? sse_accum : nullptr, ws,
+                                                  ws_bytes, n, T, E, L, dropout_p, 0, seed, offset, 1.f, conv_algo,
+                                                  (token_buffer + (token_alternate ? (int)k : 0)) & 1, 0, nullptr, nullptr,
+                                                  nullptr, nullptr, 0.f, 0.0, 0.0, 0.f, 0.f, 0, stream);
+                     });
+}
+
+extern "C" int r4r_deepconnpp_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch,
+                                         int64_t launches, int64_t *built_group, int64_t *launches_done,
+                                         const float *table, int64_t V, float *flat_p, const uint64_t *rows_p,
+                                         int64_t n_users, int64_t n_items, void *ws, size_t ws_bytes, int T, int E,
+                                         int L, float dropout_p, uint64_t seed, uint64_t offset, int conv_algo,
+                                         int token_buffer, float *pred_out, float *se_out, float *aux_out,
+                                         void *stream) {
+    (void)aux_out;
+    if (int rc = check_doc_shape(loader, "deepconnpp_span_score", 0, T, launches_done, true)) return rc;
+    R4R_REQUIRE(pred_out, "deepconnpp_span_score: null pred_out");
+    return run_score("deepconnpp_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+                     as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+                         return r4r_deepconnpp_step(table, V, c.user_doc, c.item_doc, c.uid, c.iid, c.y, flat_p, nullptr,
+                                                    nullptr, nullptr, rows_p, nullptr, nullptr, n_users, n_items,
+                                                    pred_out + k * n, se_out ? se_out + k * n : nullptr, nullptr, ws,
+                                                    ws_bytes, n, T, E, L, dropout_p, 0, seed, offset, 1.f, conv_algo,
+                                                    (token_buffer + (int)k) & 1, 0, nullptr, nullptr, 0.f, 0.0, 0.0, 0.f,
+                                                    0.f, 0, stream);
+                     });
+}
+
+extern "C" int r4r_narre_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch,
+                                    int64_t launches, int64_t *built_group, int64_t *launches_done, const float *table,
+                                    int64_t V, float *flat_p, const uint64_t *rows_p, int64_t n_users, int64_t n_items,
+                                    void *ws, size_t ws_bytes, int R, int T, int E, int L, float dropout_p,
+                                    uint64_t seed, uint64_t offset, int conv_algo, int token_buffer, float *pred_out,
+                                    float *se_out, float *aux_out, void *stream) {
+    (void)aux_out;
+    if (launches_done) *launches_done = 0;
+    R4R_REQUIRE(R == NB, "narre_span_score: R = %d reviews, the ring holds %d neighbour ids per rating", R, NB);
+    if (int rc = check_doc_shape(loader, "narre_span_score", R, T, launches_done, true)) return rc;
+    R4R_REQUIRE(pred_out, "narre_span_score: null pred_out");
+    return run_score("narre_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+                     as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+                         // NARRE.py:87-96: reviewed_items = data[2], users_who_reviewed = data[1]
+                         return r4r_narre_step(table, V, c.user_doc, c.item_doc, c.what, c.who, c.uid, c.iid, c.y, flat_p,
+                                               nullptr, nullptr, nullptr, rows_p, nullptr, nullptr, n_users, n_items,
+                                               pred_out + k * n, se_out ? se_out + k * n : nullptr, nullptr, ws, ws_bytes,
+                                               n, R, T, E, L, dropout_p, 0, seed, offset, 1.f, conv_algo,
+                                               (token_buffer + (int)k) & 1, 0, nullptr, nullptr, 0.f, 0.0, 0.0, 0.f, 0.f,
+                                               0, stream);
+                     });
+}
+
+extern "C" int r4r_transnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch,
+                                       int64_t launches, int64_t *built_group, int64_t *launches_done,
+                                       const float *table, int64_t V, float *flat_p, const uint64_t *rows_p,
+                                       int64_t n_users, int64_t n_items, void *ws, size_t ws_bytes, int T, int E, int L,
+                                       int plus, float dropout_p, uint64_t seed, uint64_t offset, int conv_algo,
+                                       int token_buffer, float *pred_out, float *se_out, float *aux_out,
+                                       void *stream) {
+    if (int rc = check_doc_shape(loader, "transnet_span_score", 0, T, launches_done, true)) return rc;
+    R4R_REQUIRE(pred_out && aux_out && ws, "transnet_span_score: null pred_out / aux_out / workspace");
+    return run_score(
+        "transnet_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+        as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+            if (int rc = r4r_transnet_step(table, V, c.user_doc, c.item_doc, c.this_doc, c.uid, c.iid, c.y, flat_p,
+                                           nullptr, nullptr, nullptr, rows_p, nullptr, nullptr, n_users, n_items,
+                                           pred_out + k * n, se_out ? se_out + k * n : nullptr, nullptr, ws, ws_bytes, n,
+                                           T, E, L, plus, dropout_p, 0, seed, offset, 1.f, conv_algo,
+                                           (token_buffer + (int)k) & 1, 0, nullptr, nullptr, nullptr, 1, 0, 1, 0.f, 0.0,
+                                           0.0, 0.f, 0.f, 0, stream))
+                return rc;
+            if (!c.y) return R4R_OK;                        // (no ratings: the step wrote no target SE to copy)
+            const float *aux3 = reinterpret_cast<const float *>(
+                static_cast<const char *>(ws) + r4r_transnet_ws_offset(n, T, E, L, plus, V, n_users, n_items, 3));
+            score_aux_kernel<<<(unsigned)cdiv(n, 256), 256, 0, as_stream(stream)>>>(aux3, aux_out + k * n * 2, n);
+            return check_launch("transnet_span_score(aux)");
+        });
+}
+
+extern "C" int r4r_mf_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch, int64_t launches,
+                                 int64_t *built_group, int64_t *launches_done, const uint64_t *p, int64_t n_users,
+                                 int64_t n_items, int D, void *ws, size_t ws_bytes, float dropout_p, uint64_t seed,
+                                 uint64_t offset, float *pred_out, float *se_out, float *aux_out, void *stream) {
+    (void)aux_out;
+    if (launches_done) *launches_done = 0;
+    R4R_REQUIRE(pred_out, "mf_span_score: null pred_out");
+    return run_score("mf_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+                     as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+                         return r4r_mf_step(c.uid, c.iid, c.y, p, nullptr, nullptr, n_users, n_items, D, pred_out + k * n,
+                                            se_out ? se_out + k * n : nullptr, nullptr, ws, ws_bytes, n, dropout_p, 0,
+                                            seed, offset, 1.f, 1, 0, 1, 0.f, 0.0, 0.0, 0.f, 0.f, 0, stream);
+                     });
+}
+
+extern "C" int r4r_idnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t first_launch,
+                                    int64_t launches, int64_t *built_group, int64_t *launches_done, int variant,
+                                    float *flat_p, const uint64_t *rows_p, int64_t n_users, int64_t n_items, void *ws,
+                                    size_t ws_bytes, int L, float dropout_p, uint64_t seed, uint64_t offset,
+                                    float *pred_out, float *se_out, float *aux_out, void *stream) {
+    (void)aux_out;
+    if (launches_done) *launches_done = 0;
+    R4R_REQUIRE(pred_out, "idnet_span_score: null pred_out");
+    return run_score("idnet_span_score", loader, nb_item, first_launch, launches, built_group, launches_done, se_out,
+                     as_stream(stream), [&](int64_t k, const SpanBatch &c, int64_t n) {
+                         return r4r_idnet_step(variant, c.uid, c.iid, c.y, flat_p, nullptr, nullptr, nullptr, rows_p,
+                                               nullptr, nullptr, n_users, n_items, pred_out + k * n,
+                                               se_out ? se_out + k * n : nullptr, nullptr, ws, ws_bytes, n, L, dropout_p,
+                                               0, seed, offset, 1.f, 1, 0, 1, 0.f, 0.0, 0.0, 0.f, 0.f, 0, stream);
+                     });
 }

@@ -160,34 +160,42 @@ class SpanDescriptor:
 
     WORDS = 28
 
-    def __init__(self, loader):
+    def __init__(self, loader, launch=None, negs=None, review=None):
+        """``launch``: ratings per step (default: the training batch, hyper_params['batch_size']) -- a scoring pass
+        launches other sizes over the same split (DataLoader.score_descriptor).  ``negs``: the ranking rows as
+        device-resident flattened arrays (u, i, ku, ki, held, nb_item of 6 x rows candidates, no y) in place of
+        the split; ``review``: whether their documents are built (iter_negs' flag)."""
         import ctypes
         hp, st, dev = loader.hyper_params, loader.store, loader.device
-        B, N = int(hp['batch_size']), len(loader.data)
+        B = int(launch or hp['batch_size'])
+        N = len(loader.data) if negs is None else int(negs['u'].numel())
         self.batch_size, self.n_ratings, self.full_batches = B, N, N // B
-        self.review = loader.iter != loader.iter_simple
+        self.review = (loader.iter != loader.iter_simple) if negs is None else bool(review)
+        self.nb_item = None if negs is None else negs.get('nb_item')
+        self.rated = negs is None
         w = [0] * self.WORDS
         if self.review:
             narre = hp['model_type'] in ['NARRE']
             T = int(hp['input_length'])
             R, W = (int(hp['narre_num_reviews']), int(hp['narre_num_words'])) if narre else (0, 0)
             doc = R * W if narre else T
-            d = loader._device_split()
+            d = loader._device_split() if negs is None else negs
             self.group = G = max(1, loader.SPAN_RATINGS // B)
             stride = G * B * (3 * doc + 2 * NEIGHBOURS)
             self.ring = torch.empty(2 * stride, dtype=torch.int64, device=dev)
             pools = list(st.users.device(dev)) + list(st.items.device(dev)) + list(st.held.device(dev))
             self._keep = (pools, d, self.ring)
             w[0:10] = [t.data_ptr() for t in pools]
-            w[10:16] = [d[k].data_ptr() for k in ('u', 'i', 'ku', 'ki', 'held', 'y')]
+            w[10:15] = [d[k].data_ptr() for k in ('u', 'i', 'ku', 'ki', 'held')]
+            w[15] = d['y'].data_ptr() if negs is None else 0
             w[16:22] = [int(loader.this_index_user_item is not None), T, R, W, int(hp['total_users']) + 1,
                         int(hp['total_items']) + 1]
             w[22:24] = [self.ring.data_ptr(), stride]
             self.doc_shape = (R, W) if narre else (T,)
         else:
-            d = loader._device_split_simple()
+            d = loader._device_split_simple() if negs is None else negs
             self.group, self.ring, self._keep = 1, None, (d,)
-            w[10], w[11], w[15] = d['u'].data_ptr(), d['i'].data_ptr(), d['y'].data_ptr()
+            w[10], w[11], w[15] = d['u'].data_ptr(), d['i'].data_ptr(), (d['y'].data_ptr() if negs is None else 0)
             self.doc_shape = None
         w[24:27] = [N, self.group, B]
         self.words = (ctypes.c_uint64 * self.WORDS)(*w)
@@ -219,6 +227,7 @@ class SpanDescriptor:
         self.n_ratings = (1 << 40) * B
         self.full_batches = 1 << 40
         self.review = (data0[3] is not None) if review is None else bool(review)   # (ids-only batches may carry dummy documents)
+        self.nb_item, self.rated = None, y0 is not None
         self.doc_shape = None
         if self.review:
             self.doc_shape = tuple(data0[3].shape[-2:]) if data0[3].dim() - data0[5].dim() == 2 else tuple(data0[3].shape[-1:])
@@ -450,6 +459,64 @@ class DataLoader():
             self._span = SpanDescriptor(self)
         self._span.built.value = -1
         return self._span
+
+    # ------------------------------------------------------------------ scoring spans (include/r4r.h: r4r_*_span_score)
+    def _device_negs(self, review):
+        """_negs_arrays(review) expanded ONCE into what iter_negs sends per slice: per candidate (six per ranking row,
+        flattened) the user, the candidate, the POSITIVE item's overlap indices and the positive itself (nb_item,
+        data.py:398), resident on the device.  Ids-only loaders (review False) keep u and the candidates alone."""
+        cache = self.__dict__.setdefault('_dev_negs_flat', {})
+        key = bool(review)
+        if key not in cache:
+            a = self._negs_arrays(review)
+            t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+            d = dict(u=t(np.repeat(a['u'], 6)), i=t(a['cand'].reshape(-1)))
+            if review:
+                d.update(ku=t(np.repeat(a['ku'], 6)), ki=t(np.repeat(a['ki'], 6)), held=t(np.repeat(a['held'], 6)),
+                         nb_item=t(np.repeat(a['cand'][:, 0], 6)))
+            cache[key] = d
+        return cache[key]
+
+    def score_descriptor(self, launch, negs=False, review=False):
+        """The split (negs False) or the ranking rows (negs True: 6 x rows candidates, `launch` a multiple of 6, no
+        ratings) as the scoring spans read them: SpanDescriptor with `launch` ratings per step and a ring sized for it
+        -- two groups of max(launch, SPAN_RATINGS) ratings at most, no more than one launch at eval.EVAL_LAUNCH_CAP
+        allocates through _device_batch.  One descriptor per (launch, negs, review), kept; its ring state restarts
+        with every call, as span_descriptor()'s does.  None on the host."""
+        if not self._on_device():
+            return None
+        launch = int(launch)
+        if launch <= 0 or (negs and launch % 6):
+            raise ValueError('score_descriptor: launch %d (ranking rows score six candidates each)' % launch)
+        cache = self.__dict__.setdefault('_score_desc', {})
+        key = (launch, bool(negs), bool(review) if negs else None)
+        if key not in cache:
+            cache[key] = (SpanDescriptor(self, launch=launch, negs=self._device_negs(review), review=review)
+                          if negs else SpanDescriptor(self, launch=launch))
+        cache[key].built.value = -1
+        return cache[key]
+
+    def score_tail(self, desc):
+        """What follows `desc`'s full launches -- ratings [full * launch, N) -- as the (data, y) the per-launch
+        iterators yield for that slice (iter(eval=True, batch=launch) / iter_negs(review, batch=launch / 6)); None
+        when the launches cover everything."""
+        s, n = desc.full_batches * desc.batch_size, desc.n_ratings
+        if s >= n:
+            return None
+        if desc.rated:
+            if not desc.review:
+                d = self._device_split_simple()
+                return [None, None, None, None, None, d['u'][s:n], d['i'][s:n]], d['y'][s:n]
+            return self._device_batch(s, n)
+        d, b = self._device_negs(desc.review), (n - s) // 6
+        u, i = d['u'][s:n], d['i'][s:n]
+        y = torch.zeros(b, dtype=torch.float32, device=self.device)
+        if not desc.review:
+            return [torch.zeros(0, dtype=torch.int64, device=self.device) for _ in range(5)] + \
+                [u.view(b, 6), i.view(b, 6)], y
+        f = self._review_fields_device(u, i, d['ku'][s:n], d['ki'][s:n], d['held'][s:n], (b, 6),
+                                       nb_item=d['nb_item'][s:n])
+        return f + [u.view(b, 6), i.view(b, 6)], y
 
     # ------------------------------------------------------------------ iterators
     def iter_review(self, eval=False, simple=False, batch=None):

@@ -158,6 +158,46 @@ class _Spans:
             b += k
         return float(desc.n_ratings), float(total)
 
+    # ---- scoring spans (include/r4r.h, "Scoring spans"): the forward-only launches of a validation / ranking pass
+    def _score_ok(self, desc):
+        """Can this family's eval forward run on `desc`'s launches from C?"""
+        return False
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def score_split(self, reader, desc):
+        """Every rating of `desc` (DataLoader.score_descriptor: a split, or the ranking rows' candidates) scored by this
+        engine's eval forward -> (pred [N], se [N] or None without ratings, aux [N, 2] or None: TransNet's per-rating
+        target SE and transform distance).  The full launches go through r4r_<family>_span_score, at most SPAN_STEPS per
+        host call; the ragged tail (a split shorter than one launch: all of it) through predict on the reader's slice.
+        Each launch is what predict would launch on reader.iter(eval=True, batch=n)'s slice -- the same kernels and
+        arguments, so the same bits -- and the engine's state (token buffers, pending sweeps, running sums) ends where
+        that loop leaves it.  None: no scoring-span form for this reader / engine pair (the caller iterates)."""
+        if desc is None or not self._score_ok(desc):
+            return None
+        N, n, full = desc.n_ratings, desc.batch_size, desc.full_batches
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        pred = torch.empty(N, **f32)
+        se = torch.empty(N, **f32) if desc.rated else None
+        aux = torch.empty(N, 2, **f32) if getattr(self, 'SCORE_AUX', False) else None
+        b = 0
+        while b < full:
+            k = min(self.SPAN_STEPS, full - b)
+            self._score_span(desc, b, k, pred, se, aux)
+            b += k
+        tail = reader.score_tail(desc)
+        if tail is not None:
+            data, y = tail
+            p, s = self.predict(data, y if desc.rated else None)
+            pred[full * n:].copy_(p.reshape(-1))
+            if se is not None:
+                se[full * n:].copy_(s.reshape(-1))
+                if aux is not None:
+                    aux[full * n:].copy_(self.aux(data)[:, 1:3])
+        return pred, se, (aux if desc.rated else None)
+
 
 def _span_collectives(dp):
     """(ncclAllReduce, ncclAllGather, communicator): the addresses a data-parallel span calls from C, on the compute
@@ -742,6 +782,40 @@ class DeepCoNNEngine(_ConvRule, _Spans):
             self._prepared = ((nx[3], nx[4], B, T), self._last_buf ^ 1, None, (_RawPtr(nx[3], desc), _RawPtr(nx[4], desc)))
         _lib.check(rc, 'r4r_deepconn_span_dp' if (self.dp is not None and self.dp.on) else 'r4r_deepconn_span')
 
+    def _score_ok(self, desc):
+        return desc.review and len(desc.doc_shape) == 1
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        """`launches` consecutive predict calls on the slices of `desc` as ONE C call (r4r_deepconn_span_score); the token
+        buffers are chosen, and left, as _launch chooses and leaves them for a forward: never the buffer that holds an
+        announced batch, alternating when nothing is announced."""
+        self.check_exchange()
+        n, T = desc.batch_size, desc.doc_shape[0]
+        ws = self._workspace(n, T)
+        main = torch.cuda.current_stream(self.dev)
+        req, algo, _ = self._rule_request(n, T, False)
+        if self._prepared is not None and algo != 2:
+            self._discard_prepared(main)                     # nobody will consume it (as _launch)
+        held = self._prepared is not None
+        buf = (self._prepared[1] ^ 1) if held else self._last_buf ^ 1
+        done = ctypes.c_int64(0)
+        rc = _lib.lib().r4r_deepconn_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), ptr(self.sse) if se is not None else None, ptr(ws), ws.numel(), T,
+            self.E, self.L, float(self.hp['dropout']), self.seed, self.offset, req, buf, int(not held), ptr(pred) + 4 * first * n,
+            (ptr(se) + 4 * first * n) if se is not None else None, None, main.cuda_stream)
+        k = int(done.value)
+        if k:
+            self._step_launched = True
+            self._last_buf = buf if held else (buf + k - 1) & 1
+            if self._side is not None:
+                ev = torch.cuda.Event()
+                ev.record(main)
+                self._step_done[self._last_buf] = ev
+                if not held and k > 1:
+                    self._step_done[self._last_buf ^ 1] = ev
+        _lib.check(rc, 'r4r_deepconn_span_score')
+
     def _exchange_prepare(self, how):
         """What this rank needs, by itself, before exchange form `how` can run (no collective in here)."""
         if how == 'gather' and self._gathered is None:
@@ -1116,6 +1190,24 @@ class MFEngine(_SweepSchedule, _Spans):
             self._tb_used = True
         _lib.check(rc, name)
 
+    def _score_ok(self, desc):
+        return not desc.review
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        """`launches` consecutive predict calls on the slices of `desc` as ONE C call (r4r_mf_span_score)."""
+        self.flush()                                         # a forward reads the tables: they catch up first
+        n = desc.batch_size
+        ws = self._workspace(n)
+        done = ctypes.c_int64(0)
+        rc = _lib.lib().r4r_mf_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), None, ctypes.byref(done), self._ptrs(self.params),
+            self.n_users, self.n_items, self.D, ptr(ws), ws.numel(), float(self.hp['dropout']), self.seed, self.offset,
+            ptr(pred) + 4 * first * n, (ptr(se) + 4 * first * n) if se is not None else None, None,
+            _lib.current_stream())
+        if int(done.value):
+            self._step_launched = True
+        _lib.check(rc, 'r4r_mf_span_score')
+
     @torch.no_grad()
     def _train_step_dp(self, data, y, n_global, defer=False):
         """Data parallel: this rank's compact gradient rows into a packed block, ONE
@@ -1396,6 +1488,15 @@ class NarreEngine(_ConvRule, _Spans):
             if self._ws is not None:                         # the row tags head the buffer: shared state
                 keep = self._persist_bytes(B, R, T)
                 nxt[:keep].copy_(self._ws[:keep])
+                if self._prepared is not None:
+                    # an announced batch nobody consumed stays behind in the workspace being left (a validation pass at
+                    # another launch size): drop its token state as _launch drops one, or the compaction counters of
+                    # that buffer are still raised when this workspace comes back from the cache
+                    pb = self._prepared[1]
+                    for t in range(self.NTOWER):
+                        at = self._ws_offset(*self._ws_key, 6 + 2 * t + pb)
+                        self._ws[at:at + 4].zero_()
+                    self._last_buf = pb ^ 1
             self._ws, self._ws_key = nxt, key
             self._prepared = None                            # token state lived in the other workspace
         return self._ws
@@ -1543,6 +1644,50 @@ class NarreEngine(_ConvRule, _Spans):
             nx = self._span_towers(_span_slots(desc, first + steps))
             self._prepared = (nx + (B, R, T), self._last_buf ^ 1, [_RawPtr(a, desc) for a in nx])
         _lib.check(rc, 'r4r_%s_span%s' % (self.C, '' if self.dp is None else '_dp'))
+
+    def _score_doc(self, desc):
+        """(R, T) of the loader's documents if this family's forward reads them, else None.  (No launch-size limits:
+        those of _span_doc are the fused TRAINING step's.)"""
+        if not desc.review or len(desc.doc_shape) != 2 or desc.doc_shape[0] != NEIGHBOURS:
+            return None
+        return tuple(desc.doc_shape)
+
+    def _score_ok(self, desc):
+        return self._score_doc(desc) is not None
+
+    def _score_call(self, lib, desc, first, launches, done, pred, se, aux, ws, R, T, buf, stream):
+        return lib.r4r_narre_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), self._p4(self.rows), self.n_users, self.n_items, ptr(ws),
+            ws.numel(), R, T, self.E, self.L, float(self.hp['dropout']), self.seed, self.offset, self._algo_req, buf,
+            pred, se, aux, stream)
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        """`launches` consecutive predict calls on the slices of `desc` as ONE C call (r4r_<family>_span_score): the
+        workspace of that launch shape, a forward's conv request (the rule does not advance), an announced batch
+        dropped and the token buffers alternated as _launch does for every forward."""
+        n = desc.batch_size
+        R, T = self._score_doc(desc)
+        ws = self._workspace(n, R, T)
+        self._algo_req, _, _ = self._rule_request(n * R, T, False)
+        if self._prepared is not None:                       # a forward does not consume it: drop it (as _launch)
+            pb = self._prepared[1]
+            for t in range(self.NTOWER):
+                at = self._ws_offset(n, R, T, 6 + 2 * t + pb)
+                ws[at:at + 4].zero_()
+            self._prepared = None
+            self._last_buf = pb ^ 1
+        buf = self._last_buf ^ 1
+        done = ctypes.c_int64(0)
+        at = 4 * first * n
+        rc = self._score_call(_lib.lib(), desc, first, launches, done, ptr(pred) + at,
+                              (ptr(se) + at) if se is not None else None,
+                              (ptr(aux) + 2 * at) if aux is not None else None, ws, R, T, buf, _lib.current_stream())
+        k = int(done.value)
+        if k:
+            self._step_launched = True
+            self._last_buf = (buf + k - 1) & 1
+        _lib.check(rc, 'r4r_%s_span_score' % self.C)
 
     def _span_dp_args(self, desc):
         """The data-parallel span's exchange arguments: (inv_denom, ncclAllReduce, ncclAllGather, comm, world, B_pad)."""
@@ -1859,6 +2004,16 @@ class DeepCoNNPPEngine(NarreEngine):
     def _dp_blocks_fit(self, entries, desc):
         return entries <= self.ROWS_APPLY_MAX                # (r4r_deepconnpp_rows_apply's limit)
 
+    def _score_doc(self, desc):
+        return (1, desc.doc_shape[0]) if desc.review and len(desc.doc_shape) == 1 else None
+
+    def _score_call(self, lib, desc, first, launches, done, pred, se, aux, ws, R, T, buf, stream):
+        p2 = lambda ts: (ctypes.c_uint64 * 2)(*[t.data_ptr() for t in ts])   # noqa: E731
+        return lib.r4r_deepconnpp_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), p2(self.rows), self.n_users, self.n_items, ptr(ws), ws.numel(), T,
+            self.E, self.L, float(self.hp['dropout']), self.seed, self.offset, self._algo_req, buf, pred, se, aux, stream)
+
     ENTRY_SPEC = [(1, torch.int64), (1, torch.int64), (1, torch.float32)]   # uid, iid, d loss / d pred
 
     def _span_call_dp(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
@@ -1992,6 +2147,23 @@ class TransNetEngine(NarreEngine, _SweepSchedule):
 
     def _dp_blocks_fit(self, entries, desc):
         return not self.plus or entries <= self.BLOCKS_MAX_ENTRIES   # (_dp_rows' block form; plain TransNet: no rows)
+
+    SCORE_AUX = True             # score_split returns the per-rating (target SE, transform distance) pairs
+
+    def _score_doc(self, desc):
+        return (1, desc.doc_shape[0]) if desc.review and len(desc.doc_shape) == 1 else None
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        self.flush()                                         # a forward reads the tables: they catch up first
+        super()._score_span(desc, first, launches, pred, se, aux)
+
+    def _score_call(self, lib, desc, first, launches, done, pred, se, aux, ws, R, T, buf, stream):
+        p2 = lambda ts: (ctypes.c_uint64 * 2)(*[t.data_ptr() for t in ts]) if ts else None   # noqa: E731
+        return lib.r4r_transnet_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), ctypes.byref(desc.built), ctypes.byref(done),
+            ptr(self.table), self.V, ptr(self.flat_p), p2(self.rows), self.n_users, self.n_items, ptr(ws), ws.numel(), T,
+            self.E, self.L, self.plus, float(self.hp['dropout']), self.seed, self.offset, self._algo_req, buf, pred, se,
+            aux, stream)
 
     def _span_call_dp(self, lib, desc, first, steps, announce, done, pred, se, ws, R, T, draws, buf, ready, stream):
         inv, red, gat, comm, world, B_pad = self._span_dp_args(desc)
@@ -2358,6 +2530,24 @@ class IdNetEngine(_SweepSchedule, _Spans):
     # ------------------------------------------------------------------ spans (K steps per host call)
     def _span_ok(self, desc):
         return not desc.review and desc.batch_size <= self.MAX_TRAIN_BATCH
+
+    def _score_ok(self, desc):
+        return not desc.review
+
+    def _score_span(self, desc, first, launches, pred, se, aux):
+        """`launches` consecutive predict calls on the slices of `desc` as ONE C call (r4r_idnet_span_score)."""
+        self.flush()                                         # a forward reads the tables: they catch up first
+        n = desc.batch_size
+        ws = self._workspace(n)
+        done = ctypes.c_int64(0)
+        rc = _lib.lib().r4r_idnet_span_score(
+            desc.words, ptr(desc.nb_item), int(first), int(launches), None, ctypes.byref(done), self.variant,
+            ptr(self.flat_p), self._p6(self.rows), self.n_users, self.n_items, ptr(ws), ws.numel(), self.L,
+            float(self.hp['dropout']), self.seed, self.offset, ptr(pred) + 4 * first * n,
+            (ptr(se) + 4 * first * n) if se is not None else None, None, _lib.current_stream())
+        if int(done.value):
+            self._step_launched = True
+        _lib.check(rc, 'r4r_idnet_span_score')
 
     def _entry_spec(self):
         """_train_step_dp's gathered fields: uid, iid, d loss / d pred, the compact rows of every table."""

@@ -6,7 +6,14 @@ maps -- but keeps the per-example SE on the device during the pass, copies once 
 groups on the host with numpy instead of the reference's two scalar reads per example
 (eval.py:42-53).  ``eval_ranking`` is HR@1
 over negatives-shaped batches (eval.py:64-92).
+
+With a native engine and a device loader both passes run through the scoring spans (include/r4r.h, "Scoring
+spans"): the launches are enqueued from C, the per-rating values come back in one copy and everything
+the reference computes per slice is computed from them on the host.  ``R4R_SPANS=0`` or
+``hyper_params['eval_spans'] = False`` keeps the per-launch loops below.
 """
+import os
+
 import torch
 
 
@@ -52,9 +59,66 @@ def _launch_size(reader, hyper_params, engine, factor):
     return n
 
 
+def _spans_on(reader, hyper_params, engine):
+    """The spanned path: an engine with scoring spans, a loader on the device, and nobody switched them off."""
+    return (engine is not None and hasattr(engine, 'score_split') and hasattr(reader, 'score_descriptor')
+            and reader._on_device() and os.environ.get('R4R_SPANS', '1') != '0'
+            and hyper_params.get('eval_spans', True) is not False)
+
+
+def slice_means(values, bsz):
+    """Sum over the reference's slices of `bsz` ratings (the last one ragged) of the per-slice means of `values`
+    [N, ...] (float64), and the number of slices: what eval.py:33-35 accumulates batch by batch."""
+    import numpy as np
+    n = values.shape[0]
+    full = n // bsz
+    total = np.zeros(values.shape[1:], np.float64)
+    if full:
+        total = total + values[:full * bsz].reshape((full, bsz) + values.shape[1:]).mean(axis=1).sum(axis=0)
+    if n > full * bsz:
+        total = total + values[full * bsz:].mean(axis=0)
+    return total, full + int(n > full * bsz)
+
+
+def metrics_from_se(ses, aux, bsz):
+    """evaluate()'s metrics from the split's per-rating values on the host (float64): MSE = sum SE / N rounded to four
+    decimals (eval.py:59); with `aux` [N, 2] (TransNet: target SE, transform distance) MSE_right / MSE_transform = the
+    mean over the reference's slices of the per-slice means (eval.py:33-35, 60)."""
+    import numpy as np
+    ses = np.asarray(ses, np.float64)
+    metrics = {'MSE': round(float(ses.sum()) / float(len(ses)), 4)}       # no ratings: ZeroDivisionError, like eval.py:59
+    if aux is not None:
+        total, slices = slice_means(np.asarray(aux, np.float64), bsz)
+        metrics['MSE_right'] = round(float(total[0]) / float(slices), 4)
+        metrics['MSE_transform'] = round(float(total[1]) / float(slices), 4)
+    return metrics
+
+
+def _evaluate_spanned(reader, hyper_params, user_count, item_count, engine, n):
+    """evaluate() through engine.score_split: ONE device -> host copy of the SEs (and TransNet's pairs), the rest on
+    the host.  None: this reader / engine pair has no scoring-span form."""
+    out = engine.score_split(reader, reader.score_descriptor(n))
+    if out is None:
+        return None
+    _, se, aux = out
+    is_tn = hyper_params['model_type'] in ['transnet', 'transnet++']
+    if is_tn and aux is not None:                            # one copy: [N, 3] = SE | target SE | transform distance
+        both = torch.cat([se.reshape(-1, 1), aux], dim=1).double().cpu().numpy()
+        ses, aux = both[:, 0].copy(), both[:, 1:]
+    else:
+        ses, aux = se.double().cpu().numpy(), None
+    metrics = metrics_from_se(ses, aux, int(hyper_params['batch_size']))
+    return metrics, _count_maps(reader._u, ses, user_count), _count_maps(reader._i, ses, item_count)
+
+
 def evaluate(model, criterion, reader, hyper_params, user_count, item_count, review, engine=None):
     metrics = {}
     big = _launch_size(reader, hyper_params, engine, EVAL_LAUNCH)
+    if big and len(reader.data) and _spans_on(reader, hyper_params, engine):
+        model.eval()
+        done = _evaluate_spanned(reader, hyper_params, user_count, item_count, engine, big)
+        if done is not None:
+            return done
     batches = reader.iter(eval=True, batch=big) if big else reader.iter(eval=True)
     total_n, total_batches = 0.0, 0.0
     bsz = int(hyper_params['batch_size'])
@@ -110,6 +174,30 @@ def evaluate(model, criterion, reader, hyper_params, user_count, item_count, rev
     return metrics, _count_maps(users, ses, user_count), _count_maps(items, ses, item_count)
 
 
+def _rank_spanned(reader, review, engine, rows_per_launch):
+    """eval_ranking() through engine.score_split: the [rows, 6] scores stay on the device, r4r_rank_top1 counts the rows
+    whose positive beats every negative and the rows it cannot decide (an exact tie with the best negative, a NaN); ONE
+    copy of the two counters.  Any undecided row: the scores are copied and the batched host torch.topk decides, as the
+    per-launch path does -- ties keep resolving the way the reference's ATen call resolves them.  None: no
+    scoring-span form for this reader / engine pair."""
+    from . import _lib
+    if not reader.negs:                                      # no ranking rows: the loop below raises what it always raised
+        return None
+    out = engine.score_split(reader, reader.score_descriptor(6 * rows_per_launch, negs=True, review=review))
+    if out is None:
+        return None
+    scores = out[0].view(-1, 6)
+    rows = int(scores.shape[0])
+    counts = torch.zeros(2, dtype=torch.int64, device=scores.device)
+    _lib.check(_lib.lib().r4r_rank_top1(_lib.ptr(scores), rows, 6, _lib.ptr(counts), _lib.current_stream()),
+               'r4r_rank_top1')
+    hits, undecided = (int(c) for c in counts.cpu())
+    if undecided:
+        top = torch.topk(scores.float().cpu(), k=1, dim=-1, sorted=True).indices[:, 0]
+        hits = int((top == 0).sum())
+    return {'HR@1': round(100.0 * float(hits) / float(rows), 2)}     # no ranking rows: ZeroDivisionError, like eval.py:90
+
+
 def eval_ranking(model, reader, hyper_params, review=False, engine=None):
     """HR@1 (eval.py:64-92): % of ranking rows whose positive -- column 0 of the [B, 6] scores -- is what
     ``torch.topk(scores[row], k=1)`` returns.  The scores of the whole split stay on the device and are
@@ -119,6 +207,10 @@ def eval_ranking(model, reader, hyper_params, review=False, engine=None):
     parts = []
     is_tn = hyper_params['model_type'] in ['transnet', 'transnet++']
     big = _launch_size(reader, hyper_params, engine, RANK_LAUNCH)
+    if big and _spans_on(reader, hyper_params, engine):
+        done = _rank_spanned(reader, review, engine, big)
+        if done is not None:
+            return done
     with torch.no_grad():
         for data, y in (reader.iter_negs(review, batch=big) if big else reader.iter_negs(review)):
             if engine is not None:

@@ -47,6 +47,6 @@ def synthesize(ratings=300000, users=40000, items=15000, vocab=50002, test=0, ra
         if len(negs) == rank_users:
             break
         if u not in negs:
-            negs[u] = [[i], rng.integers(0, items, size=5).tolist()]
+            negs[u] = [[i], ((i + rng.integers(1, items, size=5)) % items).tolist()]   # (never the positive itself)
     return dict(train=train, test=held, user_reviews=user_reviews, item_reviews=item_reviews,
                 this_index_user_item=tiui, test_reviews=test_reviews, negs=negs)
