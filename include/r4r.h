@@ -1050,6 +1050,42 @@ int r4r_idnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t
                          float dropout_p, uint64_t seed, uint64_t offset, float *pred_out, float *se_out,
                          float *aux_out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Catalogue recommendation: the K best candidates of each query row.
+ * The reference has no such call: its ranking metric scores one positive against five sampled negatives, one forward
+ * per pair (eval.py:76).  Three of its models score a pair as a dot product of a per-user and a per-item vector plus a
+ * per-user and a per-item scalar, so a whole catalogue is ranked without a forward per pair:
+ *   MF_dot     MF.py:56-58     vectors = the embedding tables in place, scalars = the bias tables (+ global bias)
+ *   bias_only  MF.py:48-49     D = 0
+ *   deepconn   DeepCoNN.py:61-66 over the FM of common_pytorch_models.py:49-57: with cat = [a | c], V = [Vu ; Vi],
+ *              lin.weight = [wu | wi]:  fm(cat) = sum_f p_f q_f + [1/2 (sum_f p_f^2 - a^2 . Vu^2) + wu . a + lin.bias]
+ *              + [1/2 (sum_f q_f^2 - c^2 . Vi^2) + wi . c],  p = a Vu, q = c Vi  (rank 8)
+ *
+ * score(u, i) is ONE fixed fp32 expression:  dot = fmaf(q[u][j], c[i][j], dot) for j = 0 .. D-1 ascending from +0.0f,
+ * then (dot + c_bias[i]) + q_bias[u]; a NULL bias counts as 0.  v_mfma_f32_16x16x4_f32 computes exactly this chain,
+ * zero-padding D to a multiple of 4 changes no bit, and D = 0 is a pure bias ranking.
+ * Order: score descending, ties by ascending candidate id (a total order).  A candidate whose score is -inf or NaN
+ * is never returned (-inf in c_bias marks a row ineligible), nor one listed in the query's exclusion list; when fewer
+ * than K remain, the unused slots hold id -1 and score -inf.
+ * The result depends on the inputs only: not on `chunk`, the grid, or which other queries share the call -- query u
+ * answered alone and inside a batch gives the same ids and the same score bits.
+ *   q [n_q, D] dense, q_bias [n_q] or NULL;  c rows c_stride >= D floats apart, c_bias [n_c] or NULL
+ *   excl_off [n_q + 1], excl_ids: CSR per query row, ids strictly ascending; both NULL = no exclusions
+ *   chunk: candidates per partial list, 0 = the library's choice;  out_ids / out_scores [n_q, K]
+ * Limits: 0 <= D <= 256 (MF_dot's native limit), 1 <= K <= 128, n_q, n_c >= 0; n_q == 0 or n_c == 0 returns R4R_OK
+ * and enqueues nothing (the outputs are not touched).  Every refusal precedes the first launch; a short workspace is
+ * R4R_ERR_WORKSPACE.  Two launches (scan, merge), or one when the catalogue is a single chunk.
+ *
+ * r4r_pair_dot: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ * ---------------------------------------------------------------------- */
+size_t r4r_topk_dot_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
+int r4r_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, int D, const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk,
+                 void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_pair_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, int D, const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

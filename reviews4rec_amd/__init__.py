@@ -9,6 +9,7 @@ Layout
   pytorch_models/  drop-in Model(hyper_params) classes (same names as the reference)
   main.py eval.py loss.py data_fast.py hyper_params.py utils.py   host-surface counterparts
   dist.py          one-process-per-GPU data parallelism over RCCL
+  recommend.py     catalogue top-K lists (Catalogue, catalogue_limits, fold_fm) over csrc/topk.hip
 """
 __version__ = '0.1.0'
 
@@ -28,3 +29,6 @@ def get_model_class(model_type):
     else:
         raise ValueError('model_type %r is not on the accelerated path' % (model_type,))
     return Model
+
+
+from .recommend import Catalogue, catalogue_limits, fold_fm  # noqa: E402,F401

@@ -1,0 +1,411 @@
+// Catalogue top-K: r4r_topk_dot (include/r4r.h, "Catalogue recommendation").
+//
+// score(u, i) = (dot(q[u], c[i]) + c_bias[i]) + q_bias[u], dot an ascending fmaf chain from +0 -- computed by
+// v_mfma_f32_16x16x4_f32 (bitwise that chain; MFMA t sums j = 4t .. 4t+3 in order, lane l supplies j = 4t + (l >> 4)),
+// never written to memory: every score is compared in registers with its query's current K-th best and only the
+// survivors (of the order of K ln(chunk / K) per query and chunk) reach the sorted per-query list in LDS.
+//
+// Launch 1, topk_scan_kernel: one WAVE per workgroup = (query tile of 16 * NQ queries) x (chunk of candidates).  The
+// wave keeps its queries' A fragments in registers for the whole chunk, streams 16-candidate slabs (B fragments straight
+// from global memory: one dword per lane and MFMA, the four lanes of a candidate row read 16 contiguous bytes; the next
+// slab's loads are in flight across this slab's MFMAs) and owns its lists, so the kernel has no barrier.  Consecutive
+// workgroups are the query tiles of ONE chunk, so that the tiles of a chunk can share what the first of them fetched (the
+// intent; DESIGN.md 4.14 has what the counters show).  Measured there: the dword-granular loads, not HBM or the matrix
+// pipe, bound the scan.
+// Launch 2, topk_merge_kernel: one workgroup per query merges the chunks' partial lists (skipped for a single chunk:
+// launch 1 then writes the result itself).
+//
+// The order (score descending, id ascending; never -inf, NaN or an excluded id) is total and every score's bits depend
+// on its own (u, i) only, so the result does not depend on the chunking, the tile or the other queries of the call.
+#include <math.h>
+
+#include "common.h"
+
+namespace r4r {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int TOPK_MAX_K = 128;
+constexpr int TOPK_MAX_D = 256;
+constexpr int64_t TOPK_MAX_CHUNK = (int64_t)1 << 30;
+constexpr int TOPK_TARGET_WAVES = 4096;      // 256 CUs x 16 waves
+constexpr int64_t TOPK_MIN_CHUNK = 512;      // below this the partial lists cost more than the scan saves
+constexpr int MERGE_THREADS = 256;
+constexpr int64_t TOPK_WIDE_TILE_MIN_Q = 512;   // below this 16-query tiles alone fill the machine with fewer, longer chunks
+
+// 16-query sub-tiles per wave: four share every B fragment (the candidate matrix is re-read once per tile); above D = 128 the
+// A fragments of four no longer fit the registers
+inline int topk_nq(int64_t n_q, int D) { return (n_q >= TOPK_WIDE_TILE_MIN_Q && D <= 128) ? 4 : 1; }
+
+// the chunk the call runs with: the caller's, or one that gives every CU its waves
+inline int64_t topk_resolve_chunk(int64_t n_q, int64_t n_c, int64_t chunk) {
+    if (chunk > 0) return chunk;
+    // Not a function of D (r4r_topk_dot_ws_bytes has none): the tiles are counted as topk_nq counts them for D <= 128.  From
+    // 512 queries on with D > 128 the scan runs 16-query tiles over chunks sized for 64-query ones: four times the
+    // intended waves, the same result.
+    const int64_t tiles = cdiv(n_q, 16 * topk_nq(n_q, 0));
+    int64_t parts = cdiv(TOPK_TARGET_WAVES, tiles > 0 ? tiles : 1);
+    const int64_t most = cdiv(n_c, TOPK_MIN_CHUNK);
+    if (parts > most) parts = most;
+    if (parts < 1) parts = 1;
+    return cdiv(cdiv(n_c, parts), 64) * 64;
+}
+
+// a is ahead of b in the result order
+template <class IdT>
+__device__ __forceinline__ bool ahead(float sa, IdT ia, float sb, IdT ib) { return sa > sb || (sa == sb && ia < ib); }
+
+template <class IdT> struct fill_id;
+template <> struct fill_id<int> { static constexpr int value = 0x7fffffff; };
+template <> struct fill_id<int64_t> { static constexpr int64_t value = 0x7fffffffffffffffLL; };
+
+__device__ __forceinline__ float lane_value(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+// All 64 lanes of one wave insert (s, i) into the sorted list sc / id of K <= 128 slots (two per lane); unused slots hold
+// (-inf, fill_id): never ahead of a real entry, so the list needs no count and its K-th score -- what a newcomer has to
+// beat, -inf while there is room -- is sc[K - 1].  Returns that score as it is after the call.  One LDS round trip:
+// every lane reads its slots, a ballot gives the position, the tail moves up by one out of registers.
+template <class IdT>
+__device__ __forceinline__ float list_insert(float *sc, IdT *id, int K, float s, IdT i, int lane) {
+    const int p0 = lane, p1 = lane + 64;
+    float e0 = -INFINITY, e1 = -INFINITY;
+    IdT i0 = fill_id<IdT>::value, i1 = fill_id<IdT>::value;
+    if (p0 < K) { e0 = sc[p0]; i0 = id[p0]; }
+    if (p1 < K) { e1 = sc[p1]; i1 = id[p1]; }
+    const bool b0 = p0 < K && ahead<IdT>(e0, i0, s, i);
+    const bool b1 = p1 < K && ahead<IdT>(e1, i1, s, i);
+    const int pos = __popcll(__ballot(b0)) + __popcll(__ballot(b1));
+    if (pos >= K) return lane_value(K > 64 ? e1 : e0, (K - 1) & 63);          // (wave-uniform) not among the K best
+    wave_lds_fence();
+    if (p0 < K && !b0 && p0 + 1 < K) { sc[p0 + 1] = e0; id[p0 + 1] = i0; }
+    if (p1 < K && !b1 && p1 + 1 < K) { sc[p1 + 1] = e1; id[p1 + 1] = i1; }
+    if (lane == 0) { sc[pos] = s; id[pos] = i; }
+    wave_lds_fence();
+    if (pos == K - 1) return s;
+    return lane_value(K - 2 >= 64 ? e1 : e0, (K - 2) & 63);                     // the old entry K - 2 is the new K - 1
+}
+
+struct ScanArgs {
+    const float *q, *q_bias, *c, *c_bias;
+    const int64_t *excl_off, *excl_ids;
+    float *out_scores;        // [n_q, parts, K]
+    int64_t *out_ids;
+    int64_t n_q, n_c, c_stride, chunk, parts, tiles;
+    int D, K;
+};
+
+// KT: MFMAs per slab (D <= 4 KT), NQ: 16-query sub-tiles per wave, SL: slabs per iteration (loads in flight for small D)
+template <int KT, int NQ, int SL>
+__global__ __launch_bounds__(64) void topk_scan_kernel(ScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char topk_lds[];
+    constexpr int QT = 16 * NQ;
+    const int K = a.K, D = a.D;
+    float *sc = reinterpret_cast<float *>(topk_lds);          // [QT][K]
+    int *id = reinterpret_cast<int *>(sc + QT * K);            // [QT][K]  candidate - chunk begin
+
+    const int lane = threadIdx.x;
+    const int row = lane & 15, kq = lane >> 4;
+    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
+    const int64_t u0 = tile * QT;
+    const int64_t c_begin = part * a.chunk;
+    const int64_t c_end = (c_begin + a.chunk < a.n_c) ? c_begin + a.chunk : a.n_c;
+
+    for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
+
+    // A fragments: lane (row, kq) holds q[u0 + 16 s + row][4 t + kq]; zero beyond n_q and beyond D
+    float af[NQ][KT];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) {
+        const int64_t u = u0 + 16 * s + row;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            const int j = 4 * t + kq;
+            af[s][t] = (u < a.n_q && j < D) ? a.q[u * D + j] : 0.f;
+        }
+    }
+    // the accumulator layout: lane holds candidate `row` against queries 16 s + 4 kq + r
+    float qb[NQ][4], thr[NQ][4];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t u = u0 + 16 * s + 4 * kq + r;
+            qb[s][r] = (a.q_bias != nullptr && u < a.n_q) ? a.q_bias[u] : 0.f;
+            thr[s][r] = (u < a.n_q) ? -INFINITY : INFINITY;          // rows past n_q never survive
+        }
+    wave_lds_fence();
+
+    // B fragments: lane (row, kq) holds c[slab + row][4 t + kq].  The loads are unconditional and nothing reads their
+    // results before `take`, after the current slab's MFMAs and epilogue: the next slab's loads stay in flight across
+    // them.  A column past D reads column D - 1 and is zeroed in `take`, a row of the NEXT chunk is read and ignored,
+    // a row past the table reads the table's last row.
+    int jo[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) jo[t] = (4 * t + kq < D) ? 4 * t + kq : (D > 0 ? D - 1 : 0);
+    float bf[SL][KT], bn[SL][KT], cb[SL], cbn[SL];
+#pragma unroll
+    for (int l = 0; l < SL; ++l) {
+        cbn[l] = 0.f;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) bn[l][t] = 0.f;
+    }
+    auto load = [&](int64_t base) {
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            const int64_t i = base + 16 * l + row;
+            const int64_t ic = i < a.n_c ? i : a.n_c - 1;
+            const float *src = a.c + ic * a.c_stride;
+            if (D > 0) {
+#pragma unroll
+                for (int t = 0; t < KT; ++t) bn[l][t] = src[jo[t]];
+            }
+            if (a.c_bias != nullptr) cbn[l] = a.c_bias[ic];
+        }
+    };
+    auto take = [&]() {
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            cb[l] = cbn[l];
+#pragma unroll
+            for (int t = 0; t < KT; ++t) bf[l][t] = (4 * t + kq < D) ? bn[l][t] : 0.f;
+        }
+    };
+
+    constexpr int STEP = 16 * SL;
+    if (c_begin < c_end) load(c_begin);
+    take();
+    for (int64_t base = c_begin; base < c_end; base += STEP) {
+        if (base + STEP < c_end) load(base + STEP);
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            f32x4 acc[NQ];
+#pragma unroll
+            for (int s = 0; s < NQ; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int s = 0; s < NQ; ++s)
+                    acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][t], bf[l][t], acc[s], 0, 0, 0);
+            const int64_t cand = base + 16 * l + row;
+            const bool live = cand < c_end;
+            bool any = false;
+            float sv[NQ][4];
+#pragma unroll
+            for (int s = 0; s < NQ; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sv[s][r] = (acc[s][r] + cb[l]) + qb[s][r];
+                    any |= live && sv[s][r] > thr[s][r];
+                }
+            if (__ballot(any) == 0) continue;
+            // survivors, one at a time (wave-uniform control flow from here on)
+#pragma unroll
+            for (int s = 0; s < NQ; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    unsigned long long m = __ballot(live && sv[s][r] > thr[s][r]);
+                    while (m) {
+                        const int src = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const float v = lane_value(sv[s][r], src);
+                        const int ql = 16 * s + 4 * (src >> 4) + r;
+                        const int64_t ci = base + 16 * l + (src & 15);
+                        if (!(v > lane_value(thr[s][r], src))) continue;         // (an earlier survivor raised the bar)
+                        if (a.excl_off != nullptr) {
+                            int64_t lo = a.excl_off[u0 + ql], hi = a.excl_off[u0 + ql + 1];
+                            const int64_t end = hi;
+                            while (lo < hi) {
+                                const int64_t mid = lo + ((hi - lo) >> 1);
+                                if (a.excl_ids[mid] < ci) lo = mid + 1; else hi = mid;
+                            }
+                            if (lo < end && a.excl_ids[lo] == ci) continue;
+                        }
+                        const float bar = list_insert<int>(sc + ql * K, id + ql * K, K, v, (int)(ci - c_begin), lane);
+                        if (kq == (src >> 4)) thr[s][r] = bar;                   // the lanes that hold this query
+                    }
+                }
+        }
+        take();
+    }
+
+    // the partial lists, filled up with (-inf, -1)
+    for (int ql = 0; ql < QT; ++ql) {
+        const int64_t u = u0 + ql;
+        if (u >= a.n_q) break;
+        const int64_t o = (u * a.parts + part) * K;
+        for (int p = lane; p < K; p += 64) {
+            const int ci = id[ql * K + p];
+            a.out_scores[o + p] = sc[ql * K + p];                                 // (-inf in an unused slot)
+            a.out_ids[o + p] = ci != fill_id<int>::value ? c_begin + ci : (int64_t)-1;
+        }
+    }
+}
+
+// One workgroup per query: every wave merges a share of the parts * K partial entries into a list of its own, then
+// wave 0 merges the other waves' lists into its list and writes the result.
+__global__ __launch_bounds__(MERGE_THREADS) void topk_merge_kernel(const float *__restrict__ ps, const int64_t *__restrict__ pi,
+                                                                    int64_t parts, int K, int64_t *__restrict__ out_ids,
+                                                                    float *__restrict__ out_scores) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char topk_lds[];
+    constexpr int NW = MERGE_THREADS / 64;
+    int64_t *id = reinterpret_cast<int64_t *>(topk_lds);       // [NW][K]
+    float *sc = reinterpret_cast<float *>(id + NW * K);        // [NW][K]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t u = blockIdx.x;
+    const int64_t total = parts * K;
+    ps += u * total;
+    pi += u * total;
+    float *msc = sc + w * K;
+    int64_t *mid = id + w * K;
+    for (int p = lane; p < K; p += 64) { msc[p] = -INFINITY; mid[p] = fill_id<int64_t>::value; }
+    wave_lds_fence();
+    float bar = -INFINITY;                                     // this wave's K-th best (wave-uniform)
+    auto offer = [&](bool want, float s, int64_t i) {
+        unsigned long long m = __ballot(want);
+        while (m) {
+            const int src = __builtin_ctzll(m);
+            m &= m - 1;
+            const float v = lane_value(s, src);
+            const int64_t ci = __shfl(i, src);
+            if (v >= bar) bar = list_insert<int64_t>(msc, mid, K, v, ci, lane);
+        }
+    };
+    constexpr int UN = 4;
+    for (int64_t e0 = (int64_t)w * 64 * UN; e0 < total; e0 += (int64_t)MERGE_THREADS * UN) {
+        float s[UN];
+        int64_t i[UN];
+#pragma unroll
+        for (int k = 0; k < UN; ++k) {
+            const int64_t e = e0 + 64 * k + lane;
+            i[k] = e < total ? pi[e] : -1;
+            s[k] = e < total ? ps[e] : -INFINITY;
+        }
+#pragma unroll
+        for (int k = 0; k < UN; ++k) offer(i[k] >= 0 && s[k] >= bar, s[k], i[k]);
+    }
+    __syncthreads();
+    if (w == 0) {
+        for (int o = 1; o < NW; ++o)
+            for (int p0 = 0; p0 < K; p0 += 64) {
+                const int p = p0 + lane;
+                const float s = p < K ? sc[o * K + p] : -INFINITY;
+                const int64_t i = p < K ? id[o * K + p] : fill_id<int64_t>::value;
+                offer(i != fill_id<int64_t>::value && s >= bar, s, i);
+            }
+        for (int p = lane; p < K; p += 64) {
+            out_scores[u * K + p] = sc[p];
+            out_ids[u * K + p] = id[p] != fill_id<int64_t>::value ? id[p] : (int64_t)-1;
+        }
+    }
+}
+
+template <int KT, int NQ, int SL>
+int launch_scan(const ScanArgs &a, hipStream_t st) {
+    const size_t lds = (size_t)16 * NQ * (size_t)a.K * 8;
+    static_assert((size_t)16 * NQ * TOPK_MAX_K * 8 <= 65536, "the lists fit the LDS a launch gets without asking for more");
+    hipLaunchKernelGGL((topk_scan_kernel<KT, NQ, SL>), dim3((unsigned)(a.parts * a.tiles)), dim3(64), lds, st, a);
+    return check_launch("topk_scan_kernel");
+}
+
+template <int NQ>
+int launch_scan_d(const ScanArgs &a, hipStream_t st) {
+    // (slabs per iteration: a lone 16-query tile is bound by the stream and keeps more loads in flight)
+    if (a.D <= 8) return launch_scan<2, NQ, 4>(a, st);
+    if (a.D <= 16) return launch_scan<4, NQ, 4>(a, st);
+    if (a.D <= 32) return launch_scan<8, NQ, NQ == 1 ? 4 : 2>(a, st);
+    if (a.D <= 64) return launch_scan<16, NQ, NQ == 1 ? 2 : 1>(a, st);
+    if constexpr (NQ == 1) {                                    // (topk_nq: wider tiles stop at D = 128)
+        if (a.D > 128) return launch_scan<64, 1, 1>(a, st);
+    }
+    return launch_scan<32, NQ, 1>(a, st);
+}
+
+}  // namespace
+}  // namespace r4r
+
+using namespace r4r;
+
+extern "C" size_t r4r_topk_dot_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk) {
+    if (n_q <= 0 || n_c <= 0 || K < 1 || K > TOPK_MAX_K || chunk < 0) return 0;
+    const int64_t parts = cdiv(n_c, topk_resolve_chunk(n_q, n_c, chunk));
+    if (parts <= 1) return 0;
+    return (size_t)n_q * (size_t)parts * (size_t)K * (sizeof(float) + sizeof(int64_t));
+}
+
+extern "C" int r4r_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                            const float *c_bias, int D, const int64_t *excl_off, const int64_t *excl_ids, int K,
+                            int64_t chunk, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream) {
+    R4R_REQUIRE(K >= 1 && K <= TOPK_MAX_K, "topk_dot: K = %d outside 1 .. %d", K, TOPK_MAX_K);
+    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "topk_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
+    R4R_REQUIRE(n_q >= 0 && n_c >= 0, "topk_dot: negative n_q or n_c");
+    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "topk_dot: chunk = %lld outside 0 .. 2^30", (long long)chunk);
+    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "topk_dot: excl_off and excl_ids go together (both or neither)");
+    R4R_REQUIRE(n_q == 0 || (out_ids != nullptr && out_scores != nullptr), "topk_dot: null output");
+    R4R_REQUIRE(n_q < ((int64_t)1 << 31), "topk_dot: n_q = %lld too large", (long long)n_q);
+    R4R_REQUIRE(c_stride >= D, "topk_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
+    if (n_q == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
+    R4R_REQUIRE(D == 0 || (q != nullptr && c != nullptr), "topk_dot: null q or c with D > 0");
+    const int NQ = topk_nq(n_q, D);
+    ScanArgs a;
+    a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias;
+    a.excl_off = excl_off; a.excl_ids = excl_ids;
+    a.n_q = n_q; a.n_c = n_c; a.c_stride = c_stride; a.D = D; a.K = K;
+    a.chunk = topk_resolve_chunk(n_q, n_c, chunk);
+    a.parts = cdiv(n_c, a.chunk);
+    a.tiles = cdiv(n_q, 16 * NQ);
+    R4R_REQUIRE(a.parts * a.tiles < ((int64_t)1 << 31), "topk_dot: %lld chunks x %lld query tiles exceed the grid",
+                (long long)a.parts, (long long)a.tiles);
+    const size_t need = r4r_topk_dot_ws_bytes(n_q, n_c, K, chunk);
+    if (need > 0 && (ws == nullptr || ws_bytes < need)) {
+        set_error("topk_dot: workspace %zu < %zu bytes", ws_bytes, need);
+        return R4R_ERR_WORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    if (a.parts == 1) {
+        a.out_scores = out_scores;
+        a.out_ids = out_ids;
+    } else {
+        a.out_ids = reinterpret_cast<int64_t *>(ws);
+        a.out_scores = reinterpret_cast<float *>(a.out_ids + (size_t)n_q * a.parts * K);
+    }
+    const int rc = NQ == 4 ? launch_scan_d<4>(a, st) : launch_scan_d<1>(a, st);
+    if (rc != R4R_OK || a.parts == 1) return rc;
+    const size_t lds = (size_t)(MERGE_THREADS / 64) * (size_t)K * 12;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n_q), dim3(MERGE_THREADS), lds, st, a.out_scores, a.out_ids, a.parts, K,
+                       out_ids, out_scores);
+    return check_launch("topk_merge_kernel");
+}
+
+// score(u, i) of explicit pairs: the scalar form of the chain the matrix pipe computes
+namespace r4r {
+namespace {
+__global__ void pair_dot_kernel(const float *__restrict__ q, const float *__restrict__ q_bias, const float *__restrict__ c,
+                                int64_t c_stride, const float *__restrict__ c_bias, int D, const int64_t *__restrict__ qi,
+                                const int64_t *__restrict__ ci, int64_t n, float *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t u = qi[p], i = ci[p];
+    float dot = 0.f;
+    for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
+    out[p] = (dot + (c_bias ? c_bias[i] : 0.f)) + (q_bias ? q_bias[u] : 0.f);
+}
+}  // namespace
+}  // namespace r4r
+
+extern "C" int r4r_pair_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                            const float *c_bias, int D, const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out,
+                            void *stream) {
+    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "pair_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
+    R4R_REQUIRE(n >= 0 && n_q >= 0 && n_c >= 0, "pair_dot: negative size");
+    if (n == 0) return R4R_OK;
+    R4R_REQUIRE(n_q > 0 && n_c > 0, "pair_dot: pairs into an empty table");
+    R4R_REQUIRE(c_stride >= D, "pair_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
+    R4R_REQUIRE(q_idx != nullptr && c_idx != nullptr && out != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
+                "pair_dot: null pointer");
+    hipLaunchKernelGGL(pair_dot_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), q, q_bias, c, c_stride,
+                       c_bias, D, q_idx, c_idx, n, out);
+    return check_launch("pair_dot_kernel");
+}

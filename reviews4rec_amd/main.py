@@ -413,7 +413,9 @@ def main_NeuMF(hyper_params, readers=None, user_count=None, item_count=None, dp=
     (train, test, val) skips the loading (synthetic data); without it the dataset directory is read
     like the reference does."""
     from .pytorch_models.NeuMF import GMF, MLP, NeuMF
+    from .recommend import check_recommend_request
     from .utils import load_user_item_counts
+    check_recommend_request(hyper_params)                     # (NeuMF has no catalogue form: says so before training)
     if readers is None:
         user_count, item_count = load_user_item_counts(hyper_params)
         train_reader, test_reader, val_reader, ranking_reader, hyper_params = _load_readers(hyper_params, False)
@@ -458,7 +460,9 @@ def main_pytorch(hyper_params, readers=None, user_count=None, item_count=None, r
     loading (synthetic data); without it the dataset directory is read like the reference does:
     train-set counts, the three loaders, and the negatives reader for HR@1."""
     import reviews4rec_amd
+    from .recommend import check_recommend_request
     from .utils import load_user_item_counts
+    check_recommend_request(hyper_params)                     # (callers that come here directly, not through main())
     Model = reviews4rec_amd.get_model_class(hyper_params['model_type'])
     if review_based_model is None:
         review_based_model = hyper_params['model_type'] not in ['bias_only', 'MF', 'MF_dot', 'NeuMF']
@@ -485,6 +489,12 @@ def main_pytorch(hyper_params, readers=None, user_count=None, item_count=None, r
     if ranking_reader is not None:
         metrics.update(eval_ranking(model, ranking_reader, hyper_params, review=review_based_model, engine=engine))
     log_end_epoch(hyper_params, metrics, 'final', time.time() - start_time, metrics_on='(TEST)')
+    if hyper_params.get('recommend_k') and (dp is None or not dp.on or dp.rank == 0):
+        # every training user's top-K list over the catalogue (recommend.Catalogue), from the best-on-validation model,
+        # which every rank reloaded from the same file: rank 0 writes the one copy
+        from .recommend import write_recommendations
+        write_recommendations(hyper_params['recommend_path'], model, hyper_params, train_reader,
+                              hyper_params['recommend_k'], engine=engine)
     return metrics, user_count_mse_map, item_count_mse_map
 
 
@@ -496,6 +506,8 @@ def main(hyper_params, gpu_id=None):
     if mt in ['SVD', 'kNN', 'NMF', 'SVD++', 'baseline', 'HFT', 'MPCN']:
         raise ValueError('model_type %r (Surprise / HFT / MPCN) is outside the accelerated path; run it with the '
                          'reference' % (mt,))
+    from .recommend import check_recommend_request
+    check_recommend_request(hyper_params)                     # refuse before any training, with the reason
     method = main_NeuMF if mt == 'NeuMF' else main_pytorch
     metrics, user_count_mse_map, item_count_mse_map = method(hyper_params, gpu_id=gpu_id)
     return metrics

@@ -1,0 +1,284 @@
+"""Catalogue top-K recommendation: which K items does a trained model recommend to user u?
+
+The reference has no such call (its ranking metric scores one positive against five sampled negatives,
+eval.py:64-92).  Three of its models score a pair as
+
+    score(u, i) = <user vector, item vector> + user scalar + item scalar
+
+so a whole catalogue is ranked by one fused kernel (r4r_topk_dot, csrc/topk.hip) over cached per-item vectors,
+with no forward per pair:
+
+    bias_only (MF.py:48-49)   vectors of width 0
+    MF_dot    (MF.py:56-58)   the embedding tables in place
+    deepconn  (DeepCoNN.py:57-66)   the FM over [user tower | item tower] separates (``fold_fm``): one tower
+                              forward per ITEM (cached by ``Catalogue.refresh``), one per requested user, and a
+                              rank-8 dot per pair.
+
+Every other model type has a ReLU layer or an FM over a per-pair transform between the two sides and is refused
+with the reason (``catalogue_limits``).  There is no torch fallback: the order (score descending, ties by
+ascending item id, include/r4r.h) has one definition, the kernel's.
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import ptr
+
+SUPPORTED = ('bias_only', 'MF_dot', 'deepconn')
+MAX_D, MAX_K, FM_RANK = 256, 128, 8
+
+_REFUSED = {
+    'deepconn++': 'its head is Linear -> ReLU over [user | item] (DeepCoNN.py:68-72): the pair score is not bilinear',
+    'NARRE': 'its review attention weighs every review by the OTHER side\'s id embedding (NARRE.py): no per-item vector exists',
+    'transnet': 'its score is an FM over a ReLU transform of the pair\'s joint document (TransNet.py): not bilinear',
+    'transnet++': 'its score is an FM over a ReLU transform of the pair\'s joint document (TransNet.py): not bilinear',
+    'MF': 'its head is Linear -> ReLU over [user | item] before the FM (MF.py:60-66): the pair score is not bilinear',
+    'NeuMF': 'its MLP branch is Linear -> ReLU over [user | item] (NeuMF.py): the pair score is not bilinear',
+}
+
+
+def _latent_size(hyper_params):
+    return int(hyper_params.get('latent_size', 10))        # (the default of main.native_step_limits)
+
+
+def catalogue_limits(hyper_params):
+    """None when ``Catalogue`` can rank this configuration, else the reason it cannot."""
+    mt = hyper_params['model_type']
+    if mt in _REFUSED:
+        return 'model_type %r has no catalogue form: %s' % (mt, _REFUSED[mt])
+    if mt not in SUPPORTED:
+        return 'model_type %r has no catalogue form' % (mt,)
+    if mt == 'MF_dot' and _latent_size(hyper_params) > MAX_D:
+        return 'latent_size %d > %d' % (_latent_size(hyper_params), MAX_D)
+    return None
+
+
+def fold_fm(V, lin_w, lin_b, global_bias, latent, side, dtype=torch.float32):
+    """One side of DeepCoNN's FM head (common_pytorch_models.py:49-57) over cat = [a | c] as (vec [n, 8], bias [n]):
+
+        fm(cat) + g = sum_f p_f q_f + [1/2 (sum_f p_f^2 - a^2 . Vu^2) + wu . a + lin.bias + g]      (user)
+                                    + [1/2 (sum_f q_f^2 - c^2 . Vi^2) + wi . c]                     (item)
+
+    with V = [Vu ; Vi], lin.weight = [wu | wi], p = a Vu, q = c Vi.  ``latent`` [n, L] is a (side 'user') or c
+    ('item').  Plain torch on whatever device the inputs live on, computed in float64 and rounded once to ``dtype``:
+    it runs once per refresh, and its own rounding stays out of the score."""
+    if side not in ('user', 'item'):
+        raise ValueError("fold_fm: side must be 'user' or 'item', got %r" % (side,))
+    x = latent.detach().to(torch.float64)
+    L = x.shape[1]
+    V64, w64 = V.detach().to(torch.float64), lin_w.detach().to(torch.float64).reshape(-1)
+    if V64.shape[0] != 2 * L or w64.numel() != 2 * L:
+        raise ValueError('fold_fm: V %s / lin.weight %s do not match latent width %d' % (tuple(V.shape), tuple(lin_w.shape), L))
+    rows = slice(0, L) if side == 'user' else slice(L, 2 * L)
+    Vs, ws = V64[rows], w64[rows]
+    vec = x @ Vs
+    bias = 0.5 * ((vec * vec).sum(1) - ((x * x) @ (Vs * Vs)).sum(1)) + x @ ws
+    if side == 'user':
+        bias = bias + lin_b.detach().to(torch.float64).reshape(()) + global_bias.detach().to(torch.float64).reshape(())
+    return vec.to(dtype), bias.to(dtype)
+
+
+def eligible_items(hyper_params, train_reader, candidates=None):
+    """Sorted int64 ids a list may contain: ``candidates``, or every item with a training rating (the keys of
+    ``train_reader.item_count``).  The padding rows total_items and total_items + 1 are never eligible."""
+    n_items = int(hyper_params['total_items'])
+    if candidates is None:
+        ids = np.fromiter((int(i) for i in train_reader.item_count), dtype=np.int64, count=len(train_reader.item_count))
+    else:
+        ids = np.asarray(candidates, dtype=np.int64).reshape(-1)
+    ids = np.unique(ids)
+    if len(ids) and (ids[0] < 0 or ids[-1] >= n_items):
+        raise ValueError('catalogue: candidate ids must lie in [0, total_items = %d)' % n_items)
+    return ids
+
+
+def seen_csr(train_reader, n_users):
+    """(off int64 [n_users + 1], ids int64): per user the distinct items of its training ratings, ascending."""
+    data = train_reader.data
+    if len(data) == 0:
+        return np.zeros(n_users + 1, np.int64), np.zeros(0, np.int64)
+    u, i = data[:, 0].astype(np.int64), data[:, 1].astype(np.int64)
+    if u.min() < 0 or u.max() >= n_users:
+        raise ValueError('catalogue: training user id outside [0, %d)' % n_users)
+    pairs = np.unique(np.stack([u, i], 1), axis=0)             # sorted by user, then item; distinct
+    off = np.zeros(n_users + 1, np.int64)
+    np.cumsum(np.bincount(pairs[:, 0], minlength=n_users), out=off[1:])
+    return off, np.ascontiguousarray(pairs[:, 1])
+
+
+class Catalogue:
+    """Per-item vectors and scalars of one trained model, and the top-K lists over them.
+
+    ``refresh()`` recomputes everything cached from the model's CURRENT weights (call it again after more
+    training); ``recommend`` / ``score_pairs`` read the cache.  ``engine``: the native engine training the model,
+    if any -- its pending table updates are flushed first (MFEngine's blocked sweeps); the model's Parameters are
+    the engines' buffers, so nothing else is read back.  A pass leaves the training state where it found it: no
+    dropout draw, no step count, no conv-rule step, no token buffer of the engine is touched."""
+
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
+        why = catalogue_limits(hyper_params)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
+        self.mt = hyper_params['model_type']
+        self.tower_batch = int(tower_batch)
+        self.dev = next(model.parameters()).device
+        if self.dev.type != 'cuda':
+            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
+                               'CPU fallback')
+        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
+        self.eligible = eligible_items(hyper_params, train_reader, candidates)
+        self.D = {'bias_only': 0, 'MF_dot': _latent_size(hyper_params), 'deepconn': FM_RANK}[self.mt]
+        # candidate rows the kernel walks: the item tables as they are (MF: total_items + 1 rows), or one per item id
+        self.n_c = int(model.item_bias.numel()) if self.mt != 'deepconn' else self.n_items
+        self._seen = None
+        self.refresh()
+
+    # ------------------------------------------------------------------ the cache
+    def _tower(self, tower, idx):
+        """Eval-mode forward of a TextCNN tower (no dropout draw, no autograd): idx [n, T] -> latent [n, L]."""
+        with torch.no_grad():
+            conv = tower.convs[0]
+            pooled, _ = ops.textcnn_fwd_raw(idx, self.model.word2vec.weight, conv.weight.detach(), conv.bias.detach())
+            return ops.linear(pooled, tower.fc.weight.detach(), tower.fc.bias.detach())
+
+    def _documents(self, pool, ids):
+        """The documents ratings outside the training split are scored with (data.py:240-246): every review of the
+        owner, nothing removed, cut / zero padded to input_length."""
+        from .data import _np_docs
+        ids = np.asarray(ids, dtype=np.int64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
+            raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        docs = _np_docs(pool.tok, pool.rev_off, pool.first[ids], pool.first[ids + 1], np.full(len(ids), -1, np.int64),
+                        int(self.hp['input_length']))
+        return torch.from_numpy(docs).to(self.dev)
+
+    def _fold(self, latent, side):
+        fm, m = self.model.fm, self.model
+        return fold_fm(fm.V, fm.lin.weight, fm.lin.bias, m.global_bias, latent, side)
+
+    def refresh(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+        m = self.model
+        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
+        elig = torch.from_numpy(self.eligible).to(self.dev)
+        mask[elig] = True
+        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            if self.mt != 'deepconn':
+                self.c = m.item_embedding.weight.detach() if self.mt == 'MF_dot' else None      # in place, not copied
+                self.c_bias = torch.where(mask, m.item_bias.detach(), ninf)
+                return
+            c = torch.zeros((self.n_c, FM_RANK), dtype=torch.float32, device=self.dev)
+            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
+                ids = self.eligible[s:s + self.tower_batch]                                       # dropped chunk by chunk
+                vec, bias = self._fold(self._tower(m.item_conv, self._documents(self.reader.store.items, ids)), 'item')
+                c[elig[s:s + self.tower_batch]] = vec
+                ninf[elig[s:s + self.tower_batch]] = bias
+            self.c, self.c_bias = c, ninf
+
+    # ------------------------------------------------------------------ the query side
+    def _users(self, users):
+        """``users`` (a list, an array or a tensor on any device) as a host int64 tensor: the documents and the
+        exclusion lists are looked up on the host."""
+        u = torch.as_tensor(users, dtype=torch.int64).reshape(-1).cpu()
+        if u.numel() and (int(u.min()) < 0 or int(u.max()) >= self.n_users):
+            raise ValueError('catalogue: user ids must lie in [0, total_users = %d)' % self.n_users)
+        return u
+
+    def _queries(self, u_host):
+        """(q [n, D] or None, q_bias [n]) of the requested users from the current weights."""
+        m = self.model
+        u = u_host.to(self.dev)
+        with torch.no_grad():
+            if self.mt != 'deepconn':
+                q = m.user_embedding.weight.detach()[u].contiguous() if self.mt == 'MF_dot' else None
+                return q, (m.user_bias.detach()[u] + m.global_bias.detach()).contiguous()
+            q = torch.empty((u.numel(), FM_RANK), dtype=torch.float32, device=self.dev)
+            qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+            ids = u_host.numpy()
+            for s in range(0, len(ids), self.tower_batch):
+                docs = self._documents(self.reader.store.users, ids[s:s + self.tower_batch])
+                q[s:s + self.tower_batch], qb[s:s + self.tower_batch] = self._fold(self._tower(m.user_conv, docs), 'user')
+            return q, qb
+
+    @property
+    def seen(self):
+        """(off, ids): the CSR of every user's distinct training items, built once."""
+        if self._seen is None:
+            self._seen = seen_csr(self.reader, self.n_users)
+        return self._seen
+
+    def _exclusions(self, u_host):
+        off, ids = self.seen
+        u = u_host.numpy()
+        lens = off[u + 1] - off[u]
+        sub_off = np.zeros(len(u) + 1, np.int64)
+        np.cumsum(lens, out=sub_off[1:])
+        take = np.repeat(off[u] - sub_off[:-1], lens) + np.arange(sub_off[-1], dtype=np.int64)
+        sub_ids = ids[take] if len(take) else np.zeros(1, np.int64)            # (one spare entry: never a null pointer)
+        return torch.from_numpy(sub_off).to(self.dev), torch.from_numpy(np.ascontiguousarray(sub_ids)).to(self.dev)
+
+    # ------------------------------------------------------------------ the calls
+    def recommend(self, users, k=10, exclude_seen=True):
+        """``users``: ids as a list, a numpy array or a tensor on any device.
+        -> (items int64 [n, k], scores float32 [n, k]) on the device: per user the k best eligible items, score
+        descending, ties by ascending id; unused slots hold (-1, -inf)."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
+        u = self._users(users)
+        n = int(u.numel())
+        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return items, scores
+        q, qb = self._queries(u)
+        eo, ei = self._exclusions(u) if exclude_seen else (None, None)
+        lib = _lib.lib()
+        ws = ops._workspace(lib.r4r_topk_dot_ws_bytes(n, self.n_c, k, 0), self.dev)
+        _lib.call('r4r_topk_dot', ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), self.D,
+                  ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items), ptr(scores))
+        return items, scores
+
+    def score_pairs(self, users, items):
+        """The fp32 score ``recommend`` ranks by, for explicit (user, item) pairs (lists, arrays or tensors on any
+        device, equally long) -> float32 [n] on the device (-inf where the item is not eligible)."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+        if u.numel() == 0:
+            return out
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_pair_dot', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
+                  self.D, ptr(qi), ptr(ci), int(u.numel()), ptr(out))
+        return out
+
+
+def check_recommend_request(hyper_params):
+    """main's hook asked for (hyper_params['recommend_k'])?  Then refuse, BEFORE any training, a model type without a
+    catalogue form and a request without a file to write."""
+    if not hyper_params.get('recommend_k'):
+        return
+    why_not = catalogue_limits(hyper_params)
+    if why_not is not None:
+        raise RuntimeError("hyper_params['recommend_k']: " + why_not)
+    if not hyper_params.get('recommend_path'):
+        raise RuntimeError("hyper_params['recommend_k'] needs hyper_params['recommend_path'] (the .npz to write)")
+
+
+def write_recommendations(path, model, hyper_params, train_reader, k, engine=None):
+    """main.main's hook: the top-k list of every user with a training rating -> an .npz of users / items / scores."""
+    cat = Catalogue(model, hyper_params, train_reader, engine=engine)
+    users = np.array(sorted(int(u) for u in train_reader.user_count), dtype=np.int64)
+    items, scores = cat.recommend(users, k=int(k))
+    with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
+        np.savez(f, users=users, items=items.cpu().numpy(), scores=scores.cpu().numpy())
+    return path
