@@ -97,6 +97,16 @@ int r4r_gemm_math(int mode, float table_maxabs, float weight_maxabs);
  * unset: form 4 for word_embed_size <= 64, form 3 above). */
 int r4r_gemm_form(int balanced);
 
+/* Schedule of the gather-add-max inside the fused DeepCoNN step (A/B runs and tests; results are bit-identical).
+ * 1 (default): a step that is given the next batch (same shape) also flags, on its head launch, which 128-position
+ * segments of that batch are live -- not one repeated row, i.e. not the zero padding of data.py:198-199 -- and, on its
+ * backward launch, writes the stable partition "live segments first" as a plan next to that batch's token state; the
+ * next step's gather (tokens_ready = 1) then hands every workgroup one live and one uniform segment instead of two
+ * neighbours.  The plan is used only where it applies: an even number of segments per document, at most 4,096 segments
+ * per tower, at least an eighth of them uniform; everywhere else, and with 0, the gather keeps its mapping by position.
+ * Process-wide, like r4r_gemm_form.  Returns the previous setting. */
+int r4r_gather_plan(int on);
+
 /* Backward of the tower w.r.t. conv weight and bias (the word table is frozen:
  * Embedding.from_pretrained, DeepCoNN.py:15 -- no dgrad exists).
  * Replaces  convolution_backward / max_pool2d_with_indices_backward /
@@ -332,7 +342,9 @@ int r4r_deepconn_nparam(void);
 int r4r_deepconn_layout(int E, int L, int64_t *offsets, int64_t *sizes, int64_t *total);
 size_t r4r_deepconn_ws_bytes(int64_t B, int T, int E, int L, int64_t V);
 size_t r4r_deepconn_ws_mult_offset(int64_t B, int T, int E, int L, int64_t V);   /* [B,2L] dropout multipliers (tests) */
-size_t r4r_deepconn_ws_count_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer);   /* token counter of (tower, token buffer): int[0] live count, int[1] the count the last gather consumed */
+size_t r4r_deepconn_ws_count_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer);   /* token counter of (tower, token buffer): int[0] live count, int[1] the count the last gather consumed, int[2] whether the last gather that was given a segment plan followed it */
+size_t r4r_deepconn_ws_partials_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int which);   /* (tests) the tower's conv partials [B, tiles, 112]: which = 0 pmax, 1 parg */
+size_t r4r_deepconn_ws_plan_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer, int which);   /* (tests) the gather's segment plan (r4r_gather_plan) of (tower, token buffer): which = 0 perm int[B tiles], 1 plan_ready int[1], 2 live */
 int r4r_deepconn_step(const float *table, int64_t V, const int64_t *user_idx, const int64_t *item_idx,
                       const float *y, float *flat_p, float *flat_g,
                       float *pred, float *se, float *sse_accum,

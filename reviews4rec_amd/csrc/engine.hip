@@ -72,6 +72,10 @@ struct HeadArgs {
     int L, tiles, training, want_grad;
     float p_drop, inv_denom;
     uint64_t seed, offset;
+    // segment plan of the gather (tokens_device.h): the flag role for the NEXT batch rides behind the rating workgroups
+    // (plan.units > 0), and rating 0 withdraws the plan this step's gather has just used (plan_spent, nullable)
+    PlanArgs plan;
+    int *plan_spent[2];
 };
 
 
@@ -89,6 +93,14 @@ constexpr int HEAD_MAX_TILES = 8;
 HEAD_TRACE_DEFINE(r4r_debug_dc_head_trace)
 template <int ML>
 __global__ __launch_bounds__(256) void deepconn_head_wg_kernel(HeadArgs a) {
+    // the segment-flag role: workgroups B .. of the grid, one wave per segment of the next batch; it touches none of the
+    // head's LDS stages (this launch runs B workgroups on 256 CUs: the role fills idle ones).  (Its workgroups still
+    // RESERVE the instantiation's static LDS: 13 KB at latent_size <= 16, several per CU; at 65 .. 128 -- 115 KB -- one
+    // per CU, where the role would queue behind the ratings.  Measured at the headline's latent size only.)
+    if ((int64_t)blockIdx.x >= a.B) {
+        segment_flags_wave(a.plan, ((int)blockIdx.x - (int)a.B) * 4 + (int)(threadIdx.x >> 6));
+        return;
+    }
     HEAD_STAMP(0)
     constexpr int N2 = 2 * ML, PARTS = 256 / N2;      // FC outputs (both towers); threads per output: 8 | 4
     __shared__ float sw[2][ML][F_CONV + 1];            // FC weights, +1 pad
@@ -123,6 +135,8 @@ __global__ __launch_bounds__(256) void deepconn_head_wg_kernel(HeadArgs a) {
     float vreg[VREGS];
 #pragma unroll
     for (int k = 0; k < VREGS; ++k) vreg[k] = a.V[min(tid + 256 * k, n * FM_K - 1)];
+    // (the gather before this launch read plan_ready in every workgroup: it cannot reset the word itself)
+    if (b == 0 && tid < 2 && SEL2(a.plan_spent, tid)) SEL2(a.plan_spent, tid)[0] = 0;
 
     // ---- pool finish of (tower t, filter f): max over the tiles, relu, first argmax
     {
@@ -388,12 +402,14 @@ struct DcBackwardArgs {
     HeadGradArgs h;
     int hg_blocks;
     TokenArgs nx;
+    PlanArgs plan;               // units > 0: the first two workgroups of the marks slice write the towers' segment plans
 };
 __global__ __launch_bounds__(WG_THREADS, 8) void deepconn_backward_kernel(DcBackwardArgs) {
     const DcBackwardArgs &A = kernel_args<DcBackwardArgs>();   // (each role's fields loaded in its own branch: common.h)
     const WgradArgs &w = A.w;
     const HeadGradArgs &h = A.h;
     const TokenArgs &nx = A.nx;
+    const PlanArgs &plan = A.plan;
     const int hg_blocks = A.hg_blocks;
     BWD_STAMP(0, wall_clock64())
     BWD_STAMP(2, (unsigned long long)blockIdx.z + 1)
@@ -407,7 +423,11 @@ __global__ __launch_bounds__(WG_THREADS, 8) void deepconn_backward_kernel(DcBack
             __syncthreads();
         }
     } else {
-        token_mark_block(nx, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y, WG_THREADS);
+        // marks of the next batch's tokens; in front of them, one workgroup per tower turns the segment flags the head
+        // launch of this step left into the gather's plan (a 4,096-entry scan: no longer than a marks workgroup)
+        const int np = plan.units > 0 ? 2 : 0, blk = blockIdx.y * gridDim.x + blockIdx.x;
+        if (blk < np) segment_plan_block<WG_THREADS>(plan, blk);
+        else token_mark_block(nx, blk - np, gridDim.x * gridDim.y - np, WG_THREADS);
     }
 #ifdef R4R_TRACE
     __syncthreads();                                        // the workgroup's end, not thread 0's
@@ -478,6 +498,7 @@ struct StepWs {
     // project-then-gather: token state is double buffered ([buffer][tower]) so batch k+1's
     // compaction can run while step k computes; the projected rows are per tower
     int *flags[2][2], *slot[2][2], *list[2][2], *count[2][2]; float *ptab[2];
+    int *live[2][2], *perm[2][2], *plan_ready[2][2];          // the gather's segment plan, [buffer][tower] likewise
     float *pooled[2]; int *argmax[2]; float *g_pooled[2];
     float *mult, *x, *s, *g, *gz;
     float *part_w[2], *part_b[2];
@@ -512,6 +533,12 @@ static StepWs carve(void *ws, int64_t B, int T, int E, int L, int64_t V) {
     w.gz = reinterpret_cast<float *>(take((size_t)B * 2 * L * 4));
     w.s = reinterpret_cast<float *>(take((size_t)B * FM_K * 4));
     w.g = reinterpret_cast<float *>(take((size_t)B * 4));
+    for (int t = 0; t < 2; ++t)                             // (behind everything else: the other regions stay where they were)
+        for (int bf = 0; bf < 2; ++bf) {
+            w.live[bf][t] = reinterpret_cast<int *>(take((size_t)PLAN_MAX_UNITS * 4));
+            w.perm[bf][t] = reinterpret_cast<int *>(take((size_t)PLAN_MAX_UNITS * 4));
+            w.plan_ready[bf][t] = reinterpret_cast<int *>(take(256));
+        }
     w.bytes = (size_t)(p - static_cast<char *>(ws));
     return w;
 }
@@ -549,6 +576,29 @@ extern "C" size_t r4r_deepconn_ws_count_offset(int64_t B, int T, int E, int L, i
     return (size_t)(reinterpret_cast<char *>(w.count[buffer & 1][tower & 1]) - base);
 }
 
+// Byte offsets inside the workspace that tests read back: a tower's conv partials (which = 0 pmax, 1 parg) ...
+extern "C" size_t r4r_deepconn_ws_partials_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int which) {
+    char base[1];
+    const StepWs w = carve(base, B, T, E, L, V);
+    const void *at = which ? static_cast<const void *>(w.parg[tower & 1]) : w.pmax[tower & 1];
+    return (size_t)(static_cast<const char *>(at) - base);
+}
+// ... and the gather's segment plan of (tower, token buffer): which = 0 perm, 1 plan_ready, 2 live.
+extern "C" size_t r4r_deepconn_ws_plan_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer, int which) {
+    char base[1];
+    const StepWs w = carve(base, B, T, E, L, V);
+    const int t = tower & 1, bf = buffer & 1;
+    const void *at[3] = {w.perm[bf][t], w.plan_ready[bf][t], w.live[bf][t]};
+    return (which < 0 || which > 2) ? 0 : (size_t)(static_cast<const char *>(at[which]) - base);
+}
+
+// Whether a step of this shape may deal its gather by a segment plan: the switch (r4r_gather_plan), whole segment pairs
+// per document, and few enough segments for the one-workgroup scan.
+static bool plan_applies(int64_t B, int T) {
+    const int tiles = proj_tiles(T);
+    return proj_gather_plan() && (tiles & 1) == 0 && B * tiles <= PLAN_MAX_UNITS;
+}
+
 // Token compaction of a batch into token-state buffer `token_buffer` (project-then-gather only;
 // a no-op for configurations that run the direct conv).  Depends only on the indices: run it for
 // batch k+1 on a side stream while step k computes, then pass tokens_ready = 1 to that step.
@@ -564,7 +614,10 @@ extern "C" int r4r_deepconn_tokens(const int64_t *user_idx, const int64_t *item_
     if (B == 0 || textcnn_pick_algo(conv_algo, B, T, E, F_CONV) != R4R_CONV_PROJECT) return R4R_OK;
     const StepWs w = carve(ws, B, T, E, L, V);
     if (discard) {                                          // drop a prepared-but-unused token state
-        for (int t = 0; t < 2; ++t) (void)hipMemsetAsync(w.count[token_buffer][t], 0, sizeof(int), as_stream(stream));
+        for (int t = 0; t < 2; ++t) {
+            (void)hipMemsetAsync(w.count[token_buffer][t], 0, sizeof(int), as_stream(stream));
+            (void)hipMemsetAsync(w.plan_ready[token_buffer][t], 0, sizeof(int), as_stream(stream));   // ... and its plan
+        }
         return check_launch("deepconn_tokens(discard)");
     }
     ProjTower pt[2];
@@ -632,6 +685,10 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
             pt[t].flags = w.flags[token_buffer][t]; pt[t].slot = w.slot[token_buffer][t];
             pt[t].list = w.list[token_buffer][t]; pt[t].count = w.count[token_buffer][t];
             pt[t].ptab = w.ptab[t]; pt[t].pmax = w.pmax[t]; pt[t].parg = w.parg[t]; pt[t].wimg = w.wp[t];
+            // the plan an earlier step's launches prepared with this batch's token state, if any (plan_ready says)
+            if (tokens_ready && plan_applies(B, T)) {
+                pt[t].perm = w.perm[token_buffer][t]; pt[t].plan_ready = w.plan_ready[token_buffer][t];
+            }
         }
         if (!tokens_ready)
             if (int rc = textcnn_proj_tokens_launch(V, pt, 2, B, T, /*zero_state=*/false, st)) return rc;
@@ -661,10 +718,24 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
     h.pred = pred; h.se = se;
     h.B = B; h.L = L; h.tiles = tiles; h.training = training; h.want_grad = flat_g != nullptr;
     h.p_drop = dropout_p; h.inv_denom = inv_denom; h.seed = seed; h.offset = offset;
-    if (L <= 16) deepconn_head_wg_kernel<16><<<(unsigned)B, 256, 0, st>>>(h);
-    else if (L <= 32) deepconn_head_wg_kernel<32><<<(unsigned)B, 256, 0, st>>>(h);
-    else if (L <= 64) deepconn_head_wg_kernel<64><<<(unsigned)B, 256, 0, st>>>(h);     // (hyper_params.py:63 has no bound)
-    else deepconn_head_wg_kernel<128><<<(unsigned)B, 256, 0, st>>>(h);    // latent_size 65 .. 128: 115 KB of the CU's 160 KB of LDS
+    // segment flags of the next batch (same B, T) for the OTHER token buffer, under the conditions of `prefetch` below
+    const bool planning = next_user_idx && flat_g && algo == R4R_CONV_PROJECT && plan_applies(B, T);
+    PlanArgs plan{};
+    if (planning) {
+        const int ob = token_buffer ^ 1;
+        plan.idx[0] = next_user_idx; plan.idx[1] = next_item_idx;
+        for (int t = 0; t < 2; ++t) {
+            plan.live[t] = w.live[ob][t]; plan.perm[t] = w.perm[ob][t]; plan.plan_ready[t] = w.plan_ready[ob][t];
+        }
+        plan.T = T; plan.tiles = proj_tiles(T); plan.units = (int)(B * plan.tiles);
+    }
+    h.plan = plan;
+    for (int t = 0; t < 2; ++t) h.plan_spent[t] = algo == R4R_CONV_PROJECT ? w.plan_ready[token_buffer][t] : nullptr;
+    const unsigned head_wgs = (unsigned)B + (unsigned)cdiv(2 * (int64_t)plan.units, 4);
+    if (L <= 16) deepconn_head_wg_kernel<16><<<head_wgs, 256, 0, st>>>(h);
+    else if (L <= 32) deepconn_head_wg_kernel<32><<<head_wgs, 256, 0, st>>>(h);
+    else if (L <= 64) deepconn_head_wg_kernel<64><<<head_wgs, 256, 0, st>>>(h);     // (hyper_params.py:63 has no bound)
+    else deepconn_head_wg_kernel<128><<<head_wgs, 256, 0, st>>>(h);    // latent_size 65 .. 128: 115 KB of the CU's 160 KB of LDS
 
     if (!flat_g) {
         if (y && sse_accum) sse_only_kernel<<<1, 256, 0, st>>>(se, sse_accum, B);
@@ -714,7 +785,7 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
     }
     {
         ScopedTiming tm(R4R_TIMING_TEXTCNN_WGRAD, st);
-        deepconn_backward_kernel<<<dim3(F_CONV, wa.nsplit, prefetch ? 4 : 3), WG_THREADS, 0, st>>>(DcBackwardArgs{wa, hg, hg_blocks, nx});
+        deepconn_backward_kernel<<<dim3(F_CONV, wa.nsplit, prefetch ? 4 : 3), WG_THREADS, 0, st>>>(DcBackwardArgs{wa, hg, hg_blocks, nx, plan});
     }
     // 6: wgrad partial reduce -> flat gradient buffer (+ compaction of the next batch's tokens)
     const int red_blocks = (F_CONV * 3 * E + F_CONV + RED_THREADS - 1) / RED_THREADS;

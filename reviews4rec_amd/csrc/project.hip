@@ -1283,14 +1283,28 @@ __global__ __launch_bounds__(256) void proj_gather_max_kernel(ProjArgs a) {
     // segment, 4-7 its second -- of the same document, or (odd tile counts, e.g. NARRE's one-tile reviews) the first of
     // the next one
     const unsigned units = (unsigned)(a.N * a.tiles);
-    auto unit_of = [&](int h) -> unsigned { return bx * GSPW + h; };
-    const unsigned unit = unit_of(worker / GWPS);
-    const unsigned udoc = unit < units ? unit / (unsigned)a.tiles : 0u;
-    const int64_t doc = udoc;
-    const int seg = unit < units ? (int)(unit - udoc * (unsigned)a.tiles) : a.tiles;     // a.tiles: no such segment
+    const int half = worker / GWPS;                         // (32-position slices: = threadIdx.x >> 7, the merge's half -- a thread merges its own unit)
+    unsigned unit = bx * GSPW + half;
     const int T = a.T, P = T + 2;
     const bool act = wl < PF / 4;
     const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // With a plan (tokens_device.h; the fused DeepCoNN step prepares it with the token state) workgroup b takes perm[b]
+    // and perm[units - 1 - b] instead: `perm` lists the live segments first, so that is one live and one uniform segment
+    // while both kinds last -- every CU gets its share of the walks instead of 0 to 8 of them by chance.  The plan words
+    // are requested HERE, in front of the token ids of today's mapping, and looked at after those are on their way:
+    // a launch without a usable plan waits for nothing it did not wait for before; a planned one pays one round trip
+    // for its own ids.  Outputs stay indexed by the true unit, so which workgroup walks what changes no result.
+    int plan_word = 0;
+    unsigned punit = 0;
+    if (GSPW == 2 && tw.perm) {
+        // (through a vector register: as a scalar load hipcc waited for the word at once, a round trip in front of the ids)
+        // (and known to be global memory: a flat load is also counted by the waits for the scalar loads that follow)
+        typedef const int __attribute__((address_space(1))) *global_int;
+        global_int ready = (global_int)tw.plan_ready;
+        asm volatile("" : "+v"(ready));
+        plan_word = ready[0];
+        punit = (unsigned)tw.perm[half ? units - 1 - blockIdx.x : blockIdx.x];
+    }
     if (blockIdx.x == 0 && threadIdx.x == 0) {              // consumed by the GEMM launch before this one
         tw.count[1] = tw.count[0];                          // ... but remembered: the host's measured conv rule reads it
         tw.count[0] = 0;
@@ -1304,23 +1318,42 @@ __global__ __launch_bounds__(256) void proj_gather_max_kernel(ProjArgs a) {
 #ifndef R4R_GATHER_EVEN_SLICES
 #define R4R_GATHER_EVEN_SLICES 1
 #endif
-    const int seg_len = min(SEG, P - seg * SEG);
-    const int slen = (R4R_GATHER_EVEN_SLICES && seg_len > 0 && seg_len < SEG) ? (seg_len + GWPS - 1) / GWPS : SLICE;
-    const int p_lo = seg * SEG + (worker % GWPS) * slen;
-    const int p_hi = min(min(P, (seg + 1) * SEG), p_lo + slen);
-    const int t_lo = p_lo - 2;
-    const int ntok = (seg < a.tiles && p_hi > p_lo) ? p_hi - t_lo : 0;     // tokens t_lo .. p_hi-1
+    int64_t doc;
+    int p_lo, p_hi, t_lo, ntok;
+    bool va, vb;
+    int64_t ia, ib;
+    // where `unit` lies, and its slice's token ids: lane wl takes token wl and (wl < 2) token 32 + wl of the slice's at
+    // most SLICE + 2 = 34, both requested together -- as a loop the second pass (two lanes) was two more dependent round trips
+    auto place = [&]() {
+        const unsigned udoc = unit < units ? unit / (unsigned)a.tiles : 0u;
+        doc = udoc;
+        const int seg = unit < units ? (int)(unit - udoc * (unsigned)a.tiles) : a.tiles;     // a.tiles: no such segment
+        const int seg_len = min(SEG, P - seg * SEG);
+        const int slen = (R4R_GATHER_EVEN_SLICES && seg_len > 0 && seg_len < SEG) ? (seg_len + GWPS - 1) / GWPS : SLICE;
+        p_lo = seg * SEG + (worker % GWPS) * slen;
+        p_hi = min(min(P, (seg + 1) * SEG), p_lo + slen);
+        t_lo = p_lo - 2;
+        ntok = (seg < a.tiles && p_hi > p_lo) ? p_hi - t_lo : 0;     // tokens t_lo .. p_hi-1
+        const int ta = t_lo + wl, tb = t_lo + 32 + wl;        // (SLICE 16: 18 tokens, the second request is idle)
+        va = wl < ntok && ta >= 0 && ta < T; vb = 32 + wl < ntok && tb >= 0 && tb < T;
+        ia = tw.idx[doc * T + (va ? ta : 0)]; ib = tw.idx[doc * T + (vb ? tb : 0)];
+        // (both ids requested before either slot: hipcc had ordered id a, slot a, id b, slot b -- three round trips; and
+        // today's ids requested in front of the branch on the plan word, not sunk behind it)
+        asm volatile("" : "+v"(ia), "+v"(ib));
+    };
+    place();
+    const int planned = __builtin_amdgcn_readfirstlane(plan_word);
+    if (planned) {                                          // uniform over the launch
+        unit = punit;
+        place();
+    }
+    // (which mapping a launch that was given a plan took, next to the token counter: tests and A/B runs read it back)
+    if (blockIdx.x == 0 && threadIdx.x == 0 && tw.perm) tw.count[2] = planned ? 1 : 0;
     // stage the slice's slots; at the same time find out whether all its tokens are the SAME row
     // (typically the zero-padded tail of a document, data.py:198-199): then every position of the
     // slice has the same window sum and its first position decides the slice (first-max wins).
     bool same = true;
     {
-        // a slice is at most SLICE + 2 = 34 tokens: lane wl takes token wl and (wl < 2) token 32 + wl, both
-        // requested together -- as a loop the second pass (two lanes) was two more dependent round trips
-        const int ta = t_lo + wl, tb = t_lo + 32 + wl;        // (SLICE 16: 18 tokens, the second request is idle)
-        const bool va = wl < ntok && ta >= 0 && ta < T, vb = 32 + wl < ntok && tb >= 0 && tb < T;
-        int64_t ia = tw.idx[doc * T + (va ? ta : 0)], ib = tw.idx[doc * T + (vb ? tb : 0)];
-        asm volatile("" : "+v"(ia), "+v"(ib));                // (both ids requested before either slot: hipcc had ordered id a, slot a, id b, slot b -- three round trips)
         const int sa = tw.slot[ia], sb = tw.slot[ib];
         if (wl < ntok) sl[worker][wl] = va ? sa : -1;
         if (32 + wl < ntok) sl[worker][32 + wl] = vb ? sb : -1;
@@ -1394,15 +1427,15 @@ __global__ __launch_bounds__(256) void proj_gather_max_kernel(ProjArgs a) {
     __syncthreads();
     HEAD_STAMP(2)
     // merge the 4 slices of each segment in position order; thread f (< 100) of each half
-    const int half = threadIdx.x >> 7, f = threadIdx.x & 127;
-    const unsigned ounit = unit_of(half);
-    if (f < PF && ounit < units && half < GSPW) {
-        float mb = sbest[half * GWPS][f];
-        int mp = sbp[half * GWPS][f];
+    const int mhalf = threadIdx.x >> 7, f = threadIdx.x & 127;
+    const unsigned ounit = unit;                            // (threads 128 .. 255 of a one-segment workgroup -- 16-position slices -- merge nothing)
+    if (f < PF && ounit < units && mhalf < GSPW) {
+        float mb = sbest[mhalf * GWPS][f];
+        int mp = sbp[mhalf * GWPS][f];
 #pragma unroll
         for (int w = 1; w < GWPS; ++w) {
-            const float v = sbest[half * GWPS + w][f];
-            if (v > mb) { mb = v; mp = sbp[half * GWPS + w][f]; }
+            const float v = sbest[mhalf * GWPS + w][f];
+            if (v > mb) { mb = v; mp = sbp[mhalf * GWPS + w][f]; }
         }
         const size_t o = (size_t)ounit * NP + f;           // [doc][tile][NP]
         tw.pmax[o] = mb;
@@ -1536,6 +1569,9 @@ int textcnn_proj_compute_launch(const float *table, int64_t V, const ProjTower *
     return check_launch("textcnn_proj_fwd");
 }
 
+static int g_gather_plan = 1;          // 1: the fused DeepCoNN step prepares and uses the gather's segment plan (default); 0: never
+void proj_gather_set_plan(int on) { g_gather_plan = on ? 1 : 0; }
+int proj_gather_plan() { return g_gather_plan; }
 void proj_gemm_set_form(int balanced) { g_gemm_balanced = balanced; }
 int proj_gemm_math_mode() { return g_gemm_math; }
 void proj_gemm_set_math(int mode, float table_maxabs, float weight_maxabs) {

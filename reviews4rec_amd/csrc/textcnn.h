@@ -41,6 +41,8 @@ struct ProjTower {
     int *parg;
     float *wimg = nullptr;       // optional scratch of textcnn_wp_floats(E) floats (the direct conv's weight-image region):
                                  // the fp16-split GEMM packs its B operand there; absent -> fp32 GEMM
+    const int *perm = nullptr;   // optional [N * tiles] segment plan of the gather (tokens_device.h): live segments first;
+    const int *plan_ready = nullptr;   // [1] non-zero: `perm` is worth using.  Null (both): today's mapping
 };
 int proj_tiles(int T);
 int64_t proj_row_capacity(int64_t N, int T, int64_t V);
@@ -54,6 +56,8 @@ int textcnn_proj_compute_launch(const float *table, int64_t V, const ProjTower *
                                 int64_t N, int T, int E, int F, hipStream_t st);
 void proj_gemm_set_math(int mode, float table_maxabs, float weight_maxabs);
 int proj_gemm_math_mode();   // 0: fp32 MFMA (default), 1: fp16-split operands, fp32 accumulate
+void proj_gather_set_plan(int on);               // 1: the fused DeepCoNN step deals the gather's segments by a prefetched plan (default), 0: never
+int proj_gather_plan();
 void proj_gemm_set_form(int balanced);          // 1: balanced 7-row-tile form where it applies (default), 0: tile form, 2: tile form with whole tiles only, -1: env
 // R4R_CONV_AUTO / _DIRECT / _PROJECT (include/r4r.h) -> the algorithm to run; honours R4R_CONV_ALGO
 int textcnn_pick_algo(int requested, int64_t N, int T, int E, int F);

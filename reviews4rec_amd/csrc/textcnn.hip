@@ -525,6 +525,12 @@ extern "C" int r4r_gemm_form(int balanced) {
     return R4R_OK;
 }
 
+extern "C" int r4r_gather_plan(int on) {
+    const int before = proj_gather_plan();
+    proj_gather_set_plan(on);
+    return before;
+}
+
 extern "C" int r4r_textcnn_wgrad(const float *table, int64_t V, const int64_t *idx,
                                  const float *g_pooled, const int32_t *argmax,
                                  float *d_conv_w, float *d_conv_b,
