@@ -1089,6 +1089,24 @@ int r4r_idnet_span_score(const uint64_t *loader, const int64_t *nb_item, int64_t
  * R4R_ERR_WORKSPACE.  Two launches (scan, merge), or one when the catalogue is a single chunk.
  *
  * r4r_pair_dot: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ *
+ * r4r_rank_dot: the rank of explicit targets in that order, the count full-catalogue HR@K / NDCG@K / MRR are made of.
+ * It generalises the reference's only ranking call site, eval.py:64-92 (one positive against five sampled negatives),
+ * to the positive against every candidate.  Pair p = (query row q_idx[p], target candidate t_idx[p]); several pairs may
+ * share a query row and a pair may appear twice.
+ *   out_score[p] = score(q_idx[p], t_idx[p]), the bits of r4r_pair_dot
+ *   out_rank[p]  = the number of candidates j in [0, n_c) whose score is neither -inf nor NaN, that are not in the
+ *                  exclusion list of query row q_idx[p], and that are AHEAD of the target t:
+ *                  s_j > s_t || (s_j == s_t && j < t).  The target never counts against itself, excluded or not.
+ *                  A target whose own score is -inf or NaN gets rank -1.
+ *   excl_off [n_q + 1] is over query ROWS (not pairs), ids ascending; both NULL = no exclusions
+ *   chunk: candidates per workgroup pass, 0 = the library's choice
+ * The rank is an integer summed by integer atomics: the same for every `chunk`, every tiling and every grouping of the
+ * pairs into calls.  Limits: 0 <= D <= 256, c_stride >= D, n_q, n_c, n_p >= 0, 0 <= chunk <= 2^30; q_idx / t_idx out
+ * of range is the caller's error, as in r4r_pair_dot.  n_p == 0 or n_c == 0 returns R4R_OK and enqueues nothing (the
+ * outputs are not touched).  Every refusal precedes the first launch.  No workspace.  Three launches: targets, the
+ * fused MFMA scan with counters in place of lists, and -- only with exclusions -- a correction that recomputes the
+ * excluded ids' scalar chains (exact: a score's bits depend on its own pair only).
  * ---------------------------------------------------------------------- */
 size_t r4r_topk_dot_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
 int r4r_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
@@ -1096,6 +1114,10 @@ int r4r_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *
                  void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
 int r4r_pair_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                  const float *c_bias, int D, const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out,
+                 void *stream);
+int r4r_rank_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, int D, const int64_t *q_idx, const int64_t *t_idx, int64_t n_p,
+                 const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score,
                  void *stream);
 
 #ifdef __cplusplus

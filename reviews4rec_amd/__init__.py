@@ -9,7 +9,8 @@ Layout
   pytorch_models/  drop-in Model(hyper_params) classes (same names as the reference)
   main.py eval.py loss.py data_fast.py hyper_params.py utils.py   host-surface counterparts
   dist.py          one-process-per-GPU data parallelism over RCCL
-  recommend.py     catalogue top-K lists (Catalogue, catalogue_limits, fold_fm) over csrc/topk.hip
+  recommend.py     catalogue top-K lists and full-catalogue ranks (Catalogue, catalogue_limits, fold_fm,
+                   ranking_metrics) over csrc/topk.hip
 """
 __version__ = '0.1.0'
 
@@ -31,4 +32,5 @@ def get_model_class(model_type):
     return Model
 
 
-from .recommend import Catalogue, catalogue_limits, fold_fm  # noqa: E402,F401
+from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
+from .eval import eval_catalogue  # noqa: E402,F401

@@ -17,6 +17,8 @@
 //
 // The order (score descending, id ascending; never -inf, NaN or an excluded id) is total and every score's bits depend
 // on its own (u, i) only, so the result does not depend on the chunking, the tile or the other queries of the call.
+//
+// r4r_rank_dot, at the end of the file: the same stream with counters in place of lists -- the rank of explicit targets.
 #include <math.h>
 
 #include "common.h"
@@ -408,4 +410,273 @@ extern "C" int r4r_pair_dot(const float *q, int64_t n_q, const float *q_bias, co
     hipLaunchKernelGGL(pair_dot_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), q, q_bias, c, c_stride,
                        c_bias, D, q_idx, c_idx, n, out);
     return check_launch("pair_dot_kernel");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// r4r_rank_dot: the rank of explicit targets.  Pair p = (query row q_idx[p], target t_idx[p]); its rank is the number of
+// candidates ahead of the target in the order above -- a count, so the scan's lists, survivors and merge fall away.
+//   A  rank_target_kernel   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for a target
+//                           whose own score is -inf or NaN (never touched again)
+//   B  rank_scan_kernel     the scan's stream over a tile of 16 * NQ PAIRS (A fragments gathered through q_idx) and a
+//                           chunk of candidates; the epilogue compares every sum with the pair's target in registers
+//                           and counts; one 64-bit integer atomic per (pair, chunk)
+//   C  rank_excl_kernel     only with exclusions: B counted the excluded ids too; one wave per pair recomputes the
+//                           scalar chain of its query row's excluded ids and subtracts those that were ahead.  Exact,
+//                           because a score's bits depend on its own pair only (MFMA chain == scalar chain).
+// Integer atomics only: the result depends on no order, no chunking, no tiling and no grouping of the pairs.
+namespace r4r {
+namespace {
+
+#ifndef RANK_WIDE_TILE_MIN_P
+#define RANK_WIDE_TILE_MIN_P TOPK_WIDE_TILE_MIN_Q      // (the scan's threshold; DESIGN.md 4.15 has the A/B that argues for less)
+#endif
+
+struct RankArgs {
+    const float *q, *q_bias, *c, *c_bias;
+    const int64_t *q_idx, *t_idx;
+    const float *t_score;     // out_score, written by launch A
+    int64_t *out_rank;
+    int64_t n_p, n_c, c_stride, chunk, tiles;
+    int D;
+};
+
+__global__ void rank_target_kernel(const float *__restrict__ q, const float *__restrict__ q_bias, const float *__restrict__ c,
+                                   int64_t c_stride, const float *__restrict__ c_bias, int D, const int64_t *__restrict__ qi,
+                                   const int64_t *__restrict__ ti, int64_t n, float *__restrict__ out_score,
+                                   int64_t *__restrict__ out_rank) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t u = qi[p], i = ti[p];
+    float dot = 0.f;
+    for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
+    const float s = (dot + (c_bias ? c_bias[i] : 0.f)) + (q_bias ? q_bias[u] : 0.f);
+    out_score[p] = s;
+    out_rank[p] = s > -INFINITY ? 0 : -1;                      // (false for NaN)
+}
+
+// KT, NQ, SL as in topk_scan_kernel; the streaming loop is that kernel's, kept apart from it on purpose
+template <int KT, int NQ, int SL>
+__global__ __launch_bounds__(64) void rank_scan_kernel(RankArgs a) {
+    constexpr int PT = 16 * NQ;
+    const int D = a.D;
+    const int lane = threadIdx.x;
+    const int row = lane & 15, kq = lane >> 4;
+    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
+    const int64_t p0 = tile * PT;
+    const int64_t c_begin = part * a.chunk;
+    const int64_t c_end = (c_begin + a.chunk < a.n_c) ? c_begin + a.chunk : a.n_c;
+    const int c_len = (int)(c_end - c_begin);                  // (chunk <= 2^30)
+
+    // Everything the wave keeps for the chunk is loaded UNCONDITIONALLY from clamped addresses and selected afterwards (a
+    // pair past n_p reads pair n_p - 1, a column past D reads column D - 1): a guard per load makes hipcc branch around
+    // each and wait for every dependent chain in turn, which costs a short chunk more than its stream.
+    const int64_t p_last = a.n_p - 1;
+    int jo[KT];
+#pragma unroll
+    for (int t = 0; t < KT; ++t) jo[t] = (4 * t + kq < D) ? 4 * t + kq : (D > 0 ? D - 1 : 0);
+    // A fragments: lane (row, kq) holds q[q_idx[p0 + 16 s + row]][4 t + kq]; zero beyond n_p and beyond D
+    float af[NQ][KT];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) {
+        const int64_t p = p0 + 16 * s + row;
+        const float *src = a.q + a.q_idx[p < a.n_p ? p : p_last] * D;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) af[s][t] = 0.f;
+        if (D > 0) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t) af[s][t] = src[jo[t]];
+        }
+#pragma unroll
+        for (int t = 0; t < KT; ++t) af[s][t] = (p < a.n_p && 4 * t + kq < D) ? af[s][t] : 0.f;
+    }
+    // the accumulator layout: lane holds candidate `row` against pairs 16 s + 4 kq + r.  Of each pair: its query bias, its
+    // target's score and its target's id relative to the chunk (-1: before it, so no tie is ahead; INT_MAX: behind it, so
+    // every tie is).  A pair past n_p or at -1 waits for a score above +inf with an id below -1: it counts nothing.
+    float qb[NQ][4], ts[NQ][4];
+    int trel[NQ][4], cnt[NQ][4];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t p = p0 + 16 * s + 4 * kq + r;
+            const int64_t pc = p < a.n_p ? p : p_last;
+            const float st = a.t_score[pc];
+            const int64_t d = a.t_idx[pc] - c_begin;
+            qb[s][r] = a.q_bias != nullptr ? a.q_bias[a.q_idx[pc]] : 0.f;
+            const bool ranked = p < a.n_p && st > -INFINITY;   // (false for NaN)
+            ts[s][r] = ranked ? st : INFINITY;
+            trel[s][r] = !ranked || d < 0 ? -1 : (d > 0x7fffffff ? 0x7fffffff : (int)d);
+            cnt[s][r] = 0;
+        }
+
+    // B fragments: lane (row, kq) holds c[slab + row][4 t + kq].  The loads are unconditional and nothing reads their
+    // results before `take`, after the current slab's MFMAs and epilogue.  A column past D reads column D - 1 and is
+    // zeroed in `take`, a row of the NEXT chunk is read and ignored, a row past the table reads the table's last row.
+    float bf[SL][KT], bn[SL][KT], cb[SL], cbn[SL];
+#pragma unroll
+    for (int l = 0; l < SL; ++l) {
+        cbn[l] = 0.f;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) bn[l][t] = 0.f;
+    }
+    auto load = [&](int64_t base) {
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            const int64_t i = base + 16 * l + row;
+            const int64_t ic = i < a.n_c ? i : a.n_c - 1;
+            const float *src = a.c + ic * a.c_stride;
+            if (D > 0) {
+#pragma unroll
+                for (int t = 0; t < KT; ++t) bn[l][t] = src[jo[t]];
+            }
+            if (a.c_bias != nullptr) cbn[l] = a.c_bias[ic];
+        }
+    };
+    auto take = [&]() {
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            cb[l] = cbn[l];
+#pragma unroll
+            for (int t = 0; t < KT; ++t) bf[l][t] = (4 * t + kq < D) ? bn[l][t] : 0.f;
+        }
+    };
+
+    constexpr int STEP = 16 * SL;
+    if (c_begin < c_end) load(c_begin);
+    take();
+    for (int64_t base = c_begin; base < c_end; base += STEP) {
+        if (base + STEP < c_end) load(base + STEP);
+#pragma unroll
+        for (int l = 0; l < SL; ++l) {
+            f32x4 acc[NQ];
+#pragma unroll
+            for (int s = 0; s < NQ; ++s) acc[s] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int t = 0; t < KT; ++t)
+#pragma unroll
+                for (int s = 0; s < NQ; ++s)
+                    acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s][t], bf[l][t], acc[s], 0, 0, 0);
+            const int rel = (int)(base - c_begin) + 16 * l + row;
+            const bool live = rel < c_len;
+#pragma unroll
+            for (int s = 0; s < NQ; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float sv = (acc[s][r] + cb[l]) + qb[s][r];
+                    cnt[s][r] += (live && ahead<int>(sv, rel, ts[s][r], trel[s][r])) ? 1 : 0;       // (false for a NaN sum)
+                }
+        }
+        take();
+    }
+
+    // the 16 lanes of one kq hold one pair's counters: sum over the low four lane bits, then lane row = 4 s + r adds pair
+    // 16 s + 4 kq + r's count to its rank -- one atomic instruction per wave
+    int mine = 0;
+#pragma unroll
+    for (int s = 0; s < NQ; ++s)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int v = cnt[s][r];
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
+            if (row == 4 * s + r) mine = v;
+        }
+    if (row < 4 * NQ && mine > 0) {
+        const int64_t p = p0 + 16 * (row >> 2) + 4 * kq + (row & 3);
+        // (mine > 0 only for a pair below n_p whose target is ranked: the others wait for +inf)
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.out_rank + p), (unsigned long long)mine);
+    }
+}
+
+// One wave per pair over the exclusion list of its query row
+__global__ __launch_bounds__(256) void rank_excl_kernel(const float *__restrict__ q, const float *__restrict__ q_bias,
+                                                        const float *__restrict__ c, int64_t n_c, int64_t c_stride,
+                                                        const float *__restrict__ c_bias, int D,
+                                                        const int64_t *__restrict__ qi, const int64_t *__restrict__ ti,
+                                                        int64_t n_p, const int64_t *__restrict__ excl_off,
+                                                        const int64_t *__restrict__ excl_ids,
+                                                        const float *__restrict__ t_score, int64_t *out_rank) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (p >= n_p) return;
+    const float st = t_score[p];
+    if (!(st > -INFINITY)) return;                            // a pair at -1 keeps its -1
+    const int64_t u = qi[p], t = ti[p];
+    const int64_t lo = excl_off[u], hi = excl_off[u + 1];
+    const float qb = q_bias ? q_bias[u] : 0.f;
+    int n = 0;
+    for (int64_t e0 = lo; e0 < hi; e0 += 64) {
+        const int64_t e = e0 + lane;
+        if (e >= hi) continue;
+        const int64_t i = excl_ids[e];
+        if (i < 0 || i >= n_c || i == t) continue;
+        float dot = 0.f;
+        for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
+        const float s = (dot + (c_bias ? c_bias[i] : 0.f)) + qb;
+        n += ahead<int64_t>(s, i, st, t) ? 1 : 0;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
+    if (lane == 0 && n > 0)
+        atomicAdd(reinterpret_cast<unsigned long long *>(out_rank + p), (unsigned long long)(-(int64_t)n));
+}
+
+inline int rank_nq(int64_t n_p, int D) { return (n_p >= RANK_WIDE_TILE_MIN_P && D <= 128) ? 4 : 1; }
+
+template <int KT, int NQ, int SL>
+int launch_rank(const RankArgs &a, int64_t parts, hipStream_t st) {
+    hipLaunchKernelGGL((rank_scan_kernel<KT, NQ, SL>), dim3((unsigned)(parts * a.tiles)), dim3(64), 0, st, a);
+    return check_launch("rank_scan_kernel");
+}
+
+template <int NQ>
+int launch_rank_d(const RankArgs &a, int64_t parts, hipStream_t st) {
+    // (KT and SL by D and NQ exactly as launch_scan_d picks them)
+    if (a.D <= 8) return launch_rank<2, NQ, 4>(a, parts, st);
+    if (a.D <= 16) return launch_rank<4, NQ, 4>(a, parts, st);
+    if (a.D <= 32) return launch_rank<8, NQ, NQ == 1 ? 4 : 2>(a, parts, st);
+    if (a.D <= 64) return launch_rank<16, NQ, NQ == 1 ? 2 : 1>(a, parts, st);
+    if constexpr (NQ == 1) {
+        if (a.D > 128) return launch_rank<64, 1, 1>(a, parts, st);
+    }
+    return launch_rank<32, NQ, 1>(a, parts, st);
+}
+
+}  // namespace
+}  // namespace r4r
+
+extern "C" int r4r_rank_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                            const float *c_bias, int D, const int64_t *q_idx, const int64_t *t_idx, int64_t n_p,
+                            const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank,
+                            float *out_score, void *stream) {
+    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "rank_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
+    R4R_REQUIRE(n_p >= 0 && n_q >= 0 && n_c >= 0, "rank_dot: negative n_p, n_q or n_c");
+    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "rank_dot: chunk = %lld outside 0 .. 2^30", (long long)chunk);
+    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "rank_dot: excl_off and excl_ids go together (both or neither)");
+    R4R_REQUIRE(c_stride >= D, "rank_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
+    R4R_REQUIRE(n_p == 0 || (out_rank != nullptr && out_score != nullptr), "rank_dot: null output");
+    if (n_p == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
+    R4R_REQUIRE(n_q > 0, "rank_dot: pairs into an empty query table");
+    R4R_REQUIRE(q_idx != nullptr && t_idx != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
+                "rank_dot: null pointer (q_idx, t_idx, or q / c with D > 0)");
+    const int NQ = rank_nq(n_p, D);
+    RankArgs a;
+    a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias; a.q_idx = q_idx; a.t_idx = t_idx;
+    a.t_score = out_score; a.out_rank = out_rank;
+    a.n_p = n_p; a.n_c = n_c; a.c_stride = c_stride; a.D = D;
+    a.chunk = topk_resolve_chunk(n_p, n_c, chunk);
+    a.tiles = cdiv(n_p, 16 * NQ);
+    const int64_t parts = cdiv(n_c, a.chunk);
+    R4R_REQUIRE(parts * a.tiles < ((int64_t)1 << 31) && cdiv(n_p, 4) < ((int64_t)1 << 31),
+                "rank_dot: %lld chunks x %lld pair tiles exceed the grid", (long long)parts, (long long)a.tiles);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(rank_target_kernel, dim3((unsigned)cdiv(n_p, 256)), dim3(256), 0, st, q, q_bias, c, c_stride, c_bias, D,
+                       q_idx, t_idx, n_p, out_score, out_rank);
+    int rc = check_launch("rank_target_kernel");
+    if (rc != R4R_OK) return rc;
+    rc = NQ == 4 ? launch_rank_d<4>(a, parts, st) : launch_rank_d<1>(a, parts, st);
+    if (rc != R4R_OK || excl_off == nullptr) return rc;
+    hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)cdiv(n_p, 4)), dim3(256), 0, st, q, q_bias, c, n_c, c_stride, c_bias, D,
+                       q_idx, t_idx, n_p, excl_off, excl_ids, (const float *)out_score, out_rank);
+    return check_launch("rank_excl_kernel");
 }

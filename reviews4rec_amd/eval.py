@@ -225,3 +225,25 @@ def eval_ranking(model, reader, hyper_params, review=False, engine=None):
     top = torch.topk(scores, k=1, dim=-1, sorted=True).indices[:, 0]
     hits, total = float((top == 0).sum()), float(scores.shape[0])
     return {'HR@1': round(100.0 * hits / total, 2)}        # no ranking rows: ZeroDivisionError, like eval.py:90
+
+
+def eval_catalogue(model, train_reader, test_reader, hyper_params, ks=(1, 5, 10), engine=None, catalogue=None):
+    """Full-catalogue ranking metrics: every row (u, i) of ``test_reader.data`` is placed in u's ranking over ALL
+    eligible items, u's training items left out (recommend.Catalogue.rank: one fused pass on the device, one copy of
+    the ranks) -- what eval.py:64-92 does against five sampled negatives, done against the catalogue.
+    -> {'cat_HR@k', 'cat_NDCG@k', 'cat_MRR'} as percentages rounded to two places like HR@1, and 'cat_ranked' /
+    'cat_unranked': a row whose item has no training rating cannot be ranked; it is counted, not averaged.  No
+    ranked row: ZeroDivisionError, like eval.py:90."""
+    import numpy as np
+    from .recommend import Catalogue, ranking_metrics
+    cat = catalogue if catalogue is not None else Catalogue(model, hyper_params, train_reader, engine=engine)
+    data = np.asarray(test_reader.data)
+    if len(data):
+        users, items = data[:, 0].astype(np.int64), data[:, 1].astype(np.int64)
+    else:
+        users = items = np.zeros(0, np.int64)
+    ranks, _ = cat.rank(users, items, exclude_seen=True)
+    m = ranking_metrics(ranks, ks)
+    out = {'cat_' + k: round(100.0 * v, 2) for k, v in m.items() if k not in ('ranked', 'unranked')}
+    out['cat_ranked'], out['cat_unranked'] = m['ranked'], m['unranked']
+    return out

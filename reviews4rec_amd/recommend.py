@@ -261,6 +261,70 @@ class Catalogue:
                   self.D, ptr(qi), ptr(ci), int(u.numel()), ptr(out))
         return out
 
+    def rank(self, users, items, exclude_seen=True):
+        """The place of item ``items[p]`` in the list ``recommend`` would give user ``users[p]`` if K were the whole
+        catalogue (lists, arrays or tensors on any device, equally long)
+        -> (ranks int64 [n], scores float32 [n]) on the device: the number of eligible items ahead of the item (score
+        descending, ties by ascending id; with ``exclude_seen`` the user's training items are not counted, the item
+        itself never is), -1 where the item is not eligible; the scores are ``score_pairs``' bits.  One r4r_rank_dot
+        call: no list, no sort."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        n = int(u.numel())
+        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return ranks, scores
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
+        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_rank_dot', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
+                  self.D, ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0, ptr(ranks), ptr(scores))
+        return ranks, scores
+
+
+def ranking_metrics(ranks, ks):
+    """Full-catalogue metrics of 0-based ``ranks`` (``Catalogue.rank``; -1 = the item cannot be ranked: no training
+    rating, so the catalogue does not hold it), on the host in float64, nothing rounded:
+
+        HR@k = mean(rank < k)    NDCG@k = mean(1 / log2(rank + 2) where rank < k, else 0)    MRR = mean(1 / (rank + 1))
+
+    over the ranked pairs only; ``ranked`` / ``unranked`` report both counts.  No ranked pair: ZeroDivisionError."""
+    r = ranks.detach().cpu().numpy() if isinstance(ranks, torch.Tensor) else np.asarray(ranks)
+    r = r.reshape(-1).astype(np.int64)
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError('ranking_metrics: every k must be positive, got %r' % (ks,))
+    ok = r[r >= 0].astype(np.float64)
+    n = int(len(ok))
+    out = {'ranked': n, 'unranked': int(len(r)) - n}
+    gain = 1.0 / np.log2(ok + 2.0)
+    for k in ks:
+        hit = ok < k
+        out['HR@%d' % k] = float(hit.sum()) / n                # (n == 0: ZeroDivisionError, like eval.py:90)
+        out['NDCG@%d' % k] = float(gain[hit].sum()) / n
+    out['MRR'] = float((1.0 / (ok + 1.0)).sum()) / n
+    return out
+
+
+def check_catalogue_metrics_request(hyper_params):
+    """main's hook asked for (hyper_params['catalogue_metrics_k'])?  Then refuse, BEFORE anything is loaded, a list that
+    is not a non-empty list of positive ints and a model type without a catalogue form (``catalogue_limits``' reason)."""
+    if hyper_params.get('catalogue_metrics_k') is None:
+        return
+    ks = hyper_params['catalogue_metrics_k']
+    if (not isinstance(ks, (list, tuple)) or len(ks) == 0 or
+            any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks)):
+        raise RuntimeError("hyper_params['catalogue_metrics_k'] must be a non-empty list of positive ints, got %r" % (ks,))
+    why_not = catalogue_limits(hyper_params)
+    if why_not is not None:
+        raise RuntimeError("hyper_params['catalogue_metrics_k']: " + why_not)
+
 
 def check_recommend_request(hyper_params):
     """main's hook asked for (hyper_params['recommend_k'])?  Then refuse, BEFORE any training, a model type without a
