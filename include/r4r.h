@@ -1120,6 +1120,55 @@ int r4r_rank_dot(const float *q, int64_t n_q, const float *q_bias, const float *
                  const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score,
                  void *stream);
 
+/* ------------------------------------------------------------------------
+ * Catalogue recommendation: ReLU-sum heads.  The same lists, pair scores and ranks for the models whose head is
+ * Linear -> ReLU -> (linear down to one scalar) over [user | item].  The first Linear separates over the
+ * concatenation, W [x_u ; x_i] + b = (W_u x_u + b) + W_i x_i, and everything after the ReLU is linear, so with per-user
+ * rows q = [qa | qp], per-item rows c = [ca | cp] and one weight vector w:
+ *   deepconn++  DeepCoNN.py:68-72    H = L, P = 0: qa = W0[:, :L] zu + b0, ca = W0[:, L:] zi, w = final.3.weight
+ *   NeuMF       NeuMF.py:25-38       stage GMF: H = 0, P = L: qp = user_embedding * final.weight, cp = item_embedding
+ *               NeuMF.py:60-74       stage MLP: H = L, P = 0: qa = W1[:, :L] ue + b1, ca = W1[:, L:] ie, w = f W3
+ *               NeuMF.py:120-143     stage NeuMF: H = L, P = L: both of the above on the mlp_* / gmf_* tables
+ * (the remaining scalars go to q_bias / c_bias; reviews4rec_amd.recommend.fold_relu_head has the table).
+ *
+ * score(u, i) is ONE fixed fp32 expression, both chains ascending in j from +0.0f:
+ *   h = fmaf(w[j], fmaxf(q[u][j] + c[i][j], 0.f), h)        j = 0 .. H-1
+ *   d = fmaf(q[u][H + j], c[i][H + j], d)                   j = 0 .. P-1
+ *   score = ((h + d) + c_bias[i]) + q_bias[u]               a NULL bias counts as 0
+ * fmaxf is C's: a NaN sum in a hidden column counts as 0 (mark a row ineligible through c_bias, not through NaN columns
+ * of the hidden part).  With H = 0 this is r4r_topk_dot's expression at D = P, bit for bit.
+ *   q [n_q, H + P] dense, q_bias [n_q] or NULL;  c rows c_stride >= H + P floats apart (the pad is never read),
+ *   c_bias [n_c] or NULL;  w [H]
+ * Everything else is r4r_topk_dot's contract: score descending, ties by ascending candidate id; a candidate whose score
+ * is -inf or NaN is never returned (-inf in c_bias marks a row ineligible), nor one on the query's ascending CSR
+ * exclusion list (excl_off [n_q + 1], excl_ids; both NULL = none); unused slots hold id -1 and score -inf.  The order
+ * is total and a score's bits depend on its own pair only: the result does not depend on `chunk`, the grid, or how
+ * queries and pairs are grouped into calls.
+ * Limits: 0 <= H <= 128, 0 <= P <= 128, 1 <= K <= 128, 0 <= chunk <= 2^30 (0 = the library's choice), c_stride >= H + P,
+ * w non-NULL when H > 0, q and c non-NULL when H + P > 0, excl_off and excl_ids both or neither.  n_q == 0, n_c == 0 or
+ * n_p == 0 returns R4R_OK, enqueues nothing and leaves the outputs untouched.  Every refusal precedes the first launch
+ * and the first dereference; a short workspace is R4R_ERR_WORKSPACE.  Nothing allocates, nothing synchronises.
+ *
+ * r4r_topk_relu: out_ids / out_scores [n_q, K].  Two launches (a VALU scan, lane = candidate; r4r_topk_dot's merge), or
+ * one when the catalogue is a single chunk.  The workspace holds the chunks' partial lists in r4r_topk_dot's layout.
+ * r4r_pair_relu: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ * r4r_rank_relu: r4r_rank_dot's semantics exactly -- the full-catalogue generalisation of eval.py:64-92.  out_score[p]
+ *   has r4r_pair_relu's bits; out_rank[p] counts the candidates ahead of target t_idx[p] for query row q_idx[p] that
+ *   are neither -inf / NaN nor on that ROW's exclusion list; the target never counts against itself; a target whose own
+ *   score is -inf or NaN gets -1.  Integer atomics only: equal for every chunk, tiling and grouping.  No workspace.
+ * ---------------------------------------------------------------------- */
+size_t r4r_topk_relu_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
+int r4r_topk_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *w, int H, int P, const int64_t *excl_off, const int64_t *excl_ids,
+                  int K, int64_t chunk, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_pair_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *c_idx,
+                  int64_t n, float *out, void *stream);
+int r4r_rank_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *t_idx,
+                  int64_t n_p, const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank,
+                  float *out_score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ Layout
   main.py eval.py loss.py data_fast.py hyper_params.py utils.py   host-surface counterparts
   dist.py          one-process-per-GPU data parallelism over RCCL
   recommend.py     catalogue top-K lists and full-catalogue ranks (Catalogue, catalogue_limits, fold_fm,
-                   ranking_metrics) over csrc/topk.hip
+                   ranking_metrics) over csrc/topk.hip; the same for the ReLU-sum heads of deepconn++ and NeuMF
+                   (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip
 """
 __version__ = '0.1.0'
 
@@ -33,4 +34,5 @@ def get_model_class(model_type):
 
 
 from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
+from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
 from .eval import eval_catalogue  # noqa: E402,F401

@@ -494,8 +494,10 @@ def main_pytorch(hyper_params, readers=None, user_count=None, item_count=None, r
         # HR@k / NDCG@k / MRR of every test rating against the whole catalogue (eval.eval_catalogue); every rank
         # reloaded the same best-on-validation model: rank 0 ranks and logs
         from .eval import eval_catalogue
+        from .recommend import make_catalogue
         metrics.update(eval_catalogue(model, train_reader, test_reader, hyper_params,
-                                      ks=hyper_params['catalogue_metrics_k'], engine=engine))
+                                      ks=hyper_params['catalogue_metrics_k'], engine=engine,
+                                      catalogue=make_catalogue(model, hyper_params, train_reader, engine=engine)))
     log_end_epoch(hyper_params, metrics, 'final', time.time() - start_time, metrics_on='(TEST)')
     if hyper_params.get('recommend_k') and (dp is None or not dp.on or dp.rank == 0):
         # every training user's top-K list over the catalogue (recommend.Catalogue), from the best-on-validation model,

@@ -15,8 +15,24 @@ with no forward per pair:
                               rank-8 dot per pair.
 
 Every other model type has a ReLU layer or an FM over a per-pair transform between the two sides and is refused
-with the reason (``catalogue_limits``).  There is no torch fallback: the order (score descending, ties by
-ascending item id, include/r4r.h) has one definition, the kernel's.
+by ``Catalogue`` with the reason (``catalogue_limits``).  Two of them are served by ``ReluCatalogue``: the first
+Linear of a Linear -> ReLU head over [user | item] separates, W [x_u ; x_i] + b = (W_u x_u + b) + W_i x_i, and
+everything after the ReLU is linear down to one scalar, so
+
+    score(u, i) = sum_j w_j relu(qa[u][j] + ca[i][j]) + <qp[u], cp[i]> + user scalar + item scalar
+
+    deepconn++ (DeepCoNN.py:68-72)                     one tower forward per item (cached), one per requested user
+    NeuMF      (NeuMF.py:25-38 / 60-74 / 120-143)      stages GMF, MLP and NeuMF: the embedding tables through one
+                                                       small matmul
+
+ranked by r4r_topk_relu / r4r_rank_relu (csrc/topk_relu.hip; ``fold_relu_head`` has the table, ``relu_catalogue_limits``
+the limits).  ``main``'s hooks (``recommend_k``, ``catalogue_metrics_k``) build whichever class serves the model
+through ``make_catalogue``; they accept deepconn++ and still refuse NeuMF, which is served through the class and
+``eval.eval_catalogue(catalogue=ReluCatalogue(...))`` only.  MF, NARRE and the TransNets need an O(L^2) product per
+pair between the two sides and stay refused.
+
+There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
+definition, the kernels'.
 """
 import numpy as np
 import torch
@@ -288,6 +304,269 @@ class Catalogue:
         return ranks, scores
 
 
+RELU_MAX_L = 128                    # r4r_topk_relu: H <= 128, P <= 128
+_NEUMF_STAGES = ('GMF', 'MLP', 'NeuMF')
+
+
+def relu_catalogue_limits(hyper_params):
+    """None when ``ReluCatalogue`` can rank this configuration, else the reason it cannot."""
+    mt = hyper_params['model_type']
+    if mt in SUPPORTED:
+        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
+    if mt not in ('deepconn++', 'NeuMF'):
+        why = _REFUSED.get(mt)
+        return 'model_type %r has no ReLU-sum form%s' % (mt, ': ' + why if why else '')
+    if mt == 'NeuMF' and hyper_params.get('neumf_stage', 'NeuMF') not in _NEUMF_STAGES:
+        return 'neumf_stage %r is none of %r' % (hyper_params.get('neumf_stage'), _NEUMF_STAGES)
+    if _latent_size(hyper_params) > RELU_MAX_L:
+        return 'latent_size %d > %d' % (_latent_size(hyper_params), RELU_MAX_L)
+    return None
+
+
+def _relu_kind(hyper_params):
+    mt = hyper_params['model_type']
+    return 'deepconn++' if mt == 'deepconn++' else hyper_params.get('neumf_stage', 'NeuMF')
+
+
+def fold_relu_head(params, hyper_params, side, x=None, gx=None, bias=None, dtype=torch.float32):
+    """One side of a Linear -> ReLU -> linear head over [user | item] as the rows of the ReLU-sum (include/r4r.h):
+
+        score(u, i) = sum_{j<H} w_j relu(qa[u][j] + ca[i][j]) + sum_{j<P} qp[u][j] cp[i][j] + q_bias[u] + c_bias[i]
+
+        kind        H  P  qa[u]               ca[i]           w         qp[u] / cp[i]                    q_bias[u]
+        deepconn++  L  0  W0[:, :L] zu + b0   W0[:, L:] zi    final.3.weight[0]   -                      ub + g + final.3.bias
+        MLP         L  0  W1[:, :L] ue + b1   W1[:, L:] ie    f W3      -                                ub + g + final.bias + f . b3
+        NeuMF       L  L  as MLP (mlp_* tables, f = final.weight[0, L:])  gmf_ue * final.weight[0, :L] / gmf_ie   as MLP
+        GMF         0  L  -                   -               -         ue * final.weight[0] / ie        ub + g + final.bias
+
+    (W0 = final.0.weight; W1, b1, W3, b3 = project.1 / project.3; c_bias[i] is item_bias[i]; dropout is the identity in
+    eval mode.)  ``params``: the model's parameters by state_dict key; the kind is hyper_params' model_type and, for
+    NeuMF, neumf_stage.  ``x`` [n, L]: the side's tower latents (deepconn++) or MLP embedding rows; ``gx`` [n, L]: its
+    GMF embedding rows (GMF: the only table); ``bias`` [n]: its rows of user_bias / item_bias.
+    -> side 'user': (rows [n, H + P], q_bias [n], w [H]);  side 'item': (rows [n, H + P], c_bias [n]).
+    Plain torch on whatever device the inputs live on, computed in float64 and rounded once to ``dtype``."""
+    if side not in ('user', 'item'):
+        raise ValueError("fold_relu_head: side must be 'user' or 'item', got %r" % (side,))
+    kind = _relu_kind(hyper_params)
+    if kind not in ('deepconn++',) + _NEUMF_STAGES:
+        raise ValueError('fold_relu_head: no ReLU-sum form for %r' % (kind,))
+    f64 = lambda t: t.detach().to(torch.float64)
+    need_x, need_g = kind != 'GMF', kind in ('GMF', 'NeuMF')
+    if (x is None) == need_x or (gx is None) == need_g or bias is None:
+        raise ValueError('fold_relu_head: %s takes %s' % (kind, ' and '.join(
+            n for n, on in (('x', need_x), ('gx', need_g), ('bias', True)) if on)))
+    ref = x if need_x else gx
+    if ref.dim() != 2 or bias.dim() != 1 or bias.shape[0] != ref.shape[0] or (need_x and need_g and gx.shape != x.shape):
+        raise ValueError('fold_relu_head: x / gx [n, L] and bias [n] do not match')
+    n, L = ref.shape
+    user = side == 'user'
+    b = f64(bias)
+    if user:
+        b = b + f64(params['global_bias']).reshape(())
+    parts, w = [], torch.zeros(0, dtype=torch.float64, device=ref.device)
+    if need_x:
+        if kind == 'deepconn++':
+            W, b_in, out_w, out_b = (params[k] for k in ('final.0.weight', 'final.0.bias', 'final.3.weight', 'final.3.bias'))
+            if tuple(W.shape) != (L, 2 * L) or out_w.numel() != L:
+                raise ValueError('fold_relu_head: final.0.weight %s / final.3.weight %s do not match latent width %d'
+                                 % (tuple(W.shape), tuple(out_w.shape), L))
+            w, extra = f64(out_w).reshape(-1), f64(out_b).reshape(())
+        else:
+            W, b_in, W3, b3, fin, fin_b = (params[k] for k in ('project.1.weight', 'project.1.bias', 'project.3.weight',
+                                                               'project.3.bias', 'final.weight', 'final.bias'))
+            width = 2 * L if kind == 'NeuMF' else L
+            if tuple(W.shape) != (L, 2 * L) or tuple(W3.shape) != (L, L) or tuple(fin.shape) != (1, width):
+                raise ValueError('fold_relu_head: project / final %s %s %s do not match latent width %d'
+                                 % (tuple(W.shape), tuple(W3.shape), tuple(fin.shape), L))
+            f = f64(fin)[0, width - L:]
+            w, extra = f @ f64(W3), f64(fin_b).reshape(()) + f @ f64(b3)
+        Ws = f64(W)[:, :L] if user else f64(W)[:, L:]
+        a = f64(x) @ Ws.T
+        if user:
+            a, b = a + f64(b_in), b + extra
+        parts.append(a)
+    if need_g:
+        fin = params['final.weight']
+        if tuple(fin.shape) != (1, 2 * L if kind == 'NeuMF' else L):
+            raise ValueError('fold_relu_head: final.weight %s does not match latent width %d' % (tuple(fin.shape), L))
+        g = f64(gx)
+        if user:
+            g = g * f64(fin)[0, :L]
+            if kind == 'GMF':
+                b = b + f64(params['final.bias']).reshape(())
+        parts.append(g)
+    rows = torch.cat(parts, 1) if len(parts) > 1 else parts[0]
+    return (rows.to(dtype), b.to(dtype), w.to(dtype)) if user else (rows.to(dtype), b.to(dtype))
+
+
+class ReluCatalogue(Catalogue):
+    """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
+    (-1, -inf) fill and argument checks) for the ReLU-sum families: deepconn++ and the three NeuMF stages
+    (``fold_relu_head``), ranked by r4r_topk_relu / r4r_pair_relu / r4r_rank_relu.
+
+    ``refresh()`` flushes the engine's pending table updates and caches the item side (``c``, ``c_bias`` with -inf in
+    ineligible rows, ``w``): deepconn++ runs the item documents through the tower ``tower_batch`` at a time, NeuMF
+    takes the embedding tables through one small matmul.  The query side is computed per call from the current
+    weights.  A pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks reach this
+    class for deepconn++ only; NeuMF is served here and through ``eval_catalogue(catalogue=ReluCatalogue(...))``."""
+
+    _entry = dict(ws='r4r_topk_relu_ws_bytes', topk='r4r_topk_relu', pair='r4r_pair_relu', rank='r4r_rank_relu')
+
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
+        why = relu_catalogue_limits(hyper_params)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
+        self.mt = hyper_params['model_type']
+        self.kind = _relu_kind(hyper_params)
+        self.tower_batch = int(tower_batch)
+        self.dev = next(model.parameters()).device
+        if self.dev.type != 'cuda':
+            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
+                               'CPU fallback')
+        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
+        self.eligible = eligible_items(hyper_params, train_reader, candidates)
+        L = _latent_size(hyper_params)
+        self.H, self.P = {'deepconn++': (L, 0), 'MLP': (L, 0), 'NeuMF': (L, L), 'GMF': (0, L)}[self.kind]
+        self.D = self.H + self.P
+        # candidate rows the kernel walks: one per item id (deepconn++), or the item tables as they are (total_items + 1)
+        self.n_c = self.n_items if self.kind == 'deepconn++' else int(model.item_bias.numel())
+        self._seen = None
+        self.refresh()
+
+    def _params(self):
+        return {k: v.detach() for k, v in self.model.named_parameters()}
+
+    def _tables(self, side):
+        m = self.model
+        if self.kind == 'NeuMF':
+            return getattr(m, 'mlp_%s_embedding' % side).weight.detach(), getattr(m, 'gmf_%s_embedding' % side).weight.detach()
+        t = getattr(m, '%s_embedding' % side).weight.detach()
+        return (None, t) if self.kind == 'GMF' else (t, None)
+
+    def refresh(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+        m, P = self.model, self._params()
+        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
+        elig = torch.from_numpy(self.eligible).to(self.dev)
+        mask[elig] = True
+        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            if self.kind != 'deepconn++':
+                x, gx = self._tables('item')
+                c, cb = fold_relu_head(P, self.hp, 'item', x=x, gx=gx, bias=m.item_bias.detach())
+                self.c, self.c_bias = c.contiguous(), torch.where(mask, cb, ninf)
+            else:
+                c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
+                for s in range(0, len(self.eligible), self.tower_batch):                          # token documents are
+                    ids = self.eligible[s:s + self.tower_batch]                                   # dropped chunk by chunk
+                    sel = elig[s:s + self.tower_batch]
+                    z = self._tower(m.item_conv, self._documents(self.reader.store.items, ids))
+                    c[sel], ninf[sel] = fold_relu_head(P, self.hp, 'item', x=z, bias=m.item_bias.detach()[sel])
+                self.c, self.c_bias = c, ninf
+            # w is the user side's; the fold of zero user rows yields it without a tower forward
+            L = _latent_size(self.hp)
+            none = torch.zeros((0, L), dtype=torch.float32, device=self.dev)
+            self.w = fold_relu_head(P, self.hp, 'user', x=none if self.kind != 'GMF' else None,
+                                    gx=none if self.kind in ('GMF', 'NeuMF') else None, bias=none[:, 0])[2].contiguous()
+            if self.w.numel() == 0:
+                self.w = torch.zeros(1, dtype=torch.float32, device=self.dev)          # (H = 0: never read, never null)
+
+    def _queries(self, u_host):
+        """(q [n, H + P], q_bias [n]) of the requested users from the current weights."""
+        m, P = self.model, self._params()
+        u = u_host.to(self.dev)
+        with torch.no_grad():
+            ub = m.user_bias.detach()[u]
+            if self.kind != 'deepconn++':
+                x, gx = self._tables('user')
+                q, qb, _ = fold_relu_head(P, self.hp, 'user', x=None if x is None else x[u], gx=None if gx is None else gx[u],
+                                          bias=ub)
+                return q.contiguous(), qb.contiguous()
+            q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
+            qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+            ids = u_host.numpy()
+            for s in range(0, len(ids), self.tower_batch):
+                z = self._tower(m.user_conv, self._documents(self.reader.store.users, ids[s:s + self.tower_batch]))
+                q[s:s + self.tower_batch], qb[s:s + self.tower_batch], _ = fold_relu_head(
+                    P, self.hp, 'user', x=z, bias=ub[s:s + self.tower_batch])
+            return q, qb
+
+    def recommend(self, users, k=10, exclude_seen=True):
+        """``Catalogue.recommend``'s contract over the ReLU-sum (one r4r_topk_relu call)."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
+        u = self._users(users)
+        n = int(u.numel())
+        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return items, scores
+        q, qb = self._queries(u)
+        eo, ei = self._exclusions(u) if exclude_seen else (None, None)
+        lib = _lib.lib()
+        ws = ops._workspace(lib.r4r_topk_relu_ws_bytes(n, self.n_c, k, 0), self.dev)
+        _lib.call('r4r_topk_relu', ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.w),
+                  self.H, self.P, ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items), ptr(scores))
+        return items, scores
+
+    def score_pairs(self, users, items):
+        """``Catalogue.score_pairs``' contract over the ReLU-sum (one r4r_pair_relu call)."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+        if u.numel() == 0:
+            return out
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_pair_relu', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
+                  ptr(self.w), self.H, self.P, ptr(qi), ptr(ci), int(u.numel()), ptr(out))
+        return out
+
+    def rank(self, users, items, exclude_seen=True):
+        """``Catalogue.rank``'s contract over the ReLU-sum (one r4r_rank_relu call: no list, no sort)."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        n = int(u.numel())
+        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return ranks, scores
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
+        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_rank_relu', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
+                  ptr(self.w), self.H, self.P, ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0, ptr(ranks), ptr(scores))
+        return ranks, scores
+
+
+def hook_limits(hyper_params):
+    """None when ``make_catalogue`` can serve main's hooks for this configuration, else the reason: ``catalogue_limits``'
+    for every type but deepconn++, which ``ReluCatalogue`` serves (NeuMF goes through the class, not through main)."""
+    why = catalogue_limits(hyper_params)
+    if why is None or hyper_params['model_type'] != 'deepconn++':
+        return why
+    return relu_catalogue_limits(hyper_params)
+
+
+def make_catalogue(model, hyper_params, train_reader, engine=None):
+    """The class that serves main's hooks: ``Catalogue`` where ``catalogue_limits`` accepts, else ``ReluCatalogue``."""
+    cls = Catalogue if catalogue_limits(hyper_params) is None else ReluCatalogue
+    return cls(model, hyper_params, train_reader, engine=engine)
+
+
 def ranking_metrics(ranks, ks):
     """Full-catalogue metrics of 0-based ``ranks`` (``Catalogue.rank``; -1 = the item cannot be ranked: no training
     rating, so the catalogue does not hold it), on the host in float64, nothing rounded:
@@ -321,7 +600,7 @@ def check_catalogue_metrics_request(hyper_params):
     if (not isinstance(ks, (list, tuple)) or len(ks) == 0 or
             any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1 for k in ks)):
         raise RuntimeError("hyper_params['catalogue_metrics_k'] must be a non-empty list of positive ints, got %r" % (ks,))
-    why_not = catalogue_limits(hyper_params)
+    why_not = hook_limits(hyper_params)
     if why_not is not None:
         raise RuntimeError("hyper_params['catalogue_metrics_k']: " + why_not)
 
@@ -331,7 +610,7 @@ def check_recommend_request(hyper_params):
     catalogue form and a request without a file to write."""
     if not hyper_params.get('recommend_k'):
         return
-    why_not = catalogue_limits(hyper_params)
+    why_not = hook_limits(hyper_params)
     if why_not is not None:
         raise RuntimeError("hyper_params['recommend_k']: " + why_not)
     if not hyper_params.get('recommend_path'):
@@ -340,7 +619,7 @@ def check_recommend_request(hyper_params):
 
 def write_recommendations(path, model, hyper_params, train_reader, k, engine=None):
     """main.main's hook: the top-k list of every user with a training rating -> an .npz of users / items / scores."""
-    cat = Catalogue(model, hyper_params, train_reader, engine=engine)
+    cat = make_catalogue(model, hyper_params, train_reader, engine=engine)
     users = np.array(sorted(int(u) for u in train_reader.user_count), dtype=np.int64)
     items, scores = cat.recommend(users, k=int(k))
     with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
