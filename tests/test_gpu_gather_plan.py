@@ -9,7 +9,11 @@ that was followed from one that was ignored, so the gather leaves a word next to
 a launch that was given a plan took: it must be 1 exactly in the steps whose batch had a plan raised for it.  (A
 document's first and last segment hold tokens outside the document and are live by the rule, so the two-tile case never
 gets a plan: an eighth of its segments would have to be uniform.  The short last segment UNDER a plan has a case of its
-own, T = 450.)"""
+own, T = 450.)
+
+The cases of this file run at B = 4 -- 8 to 32 segments per tower, inside the first two threads of the plan's scan --
+and once over the limit of 4,096.  tests/test_gpu_gather_plan_scan.py runs the same checks, with the helpers of this
+file, at 1,024 .. 4,096 segments, where the scan's prefix crosses lanes and waves."""
 import numpy as np
 import pytest
 import torch
