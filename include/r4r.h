@@ -1169,6 +1169,64 @@ int r4r_rank_relu(const float *q, int64_t n_q, const float *q_bias, const float 
                   int64_t n_p, const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank,
                   float *out_score, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Catalogue recommendation: product-MLP heads.  The same lists, pair scores and ranks for a model whose head is
+ * Linear -> ReLU -> Linear over the ELEMENTWISE PRODUCT of a per-user and a per-item vector:
+ *   NARRE   NARRE.py:38-43,121-124   final = Dropout, Linear(L, L), ReLU, Linear(L, 1) over (user + user_vec) * (item + item_vec)
+ *           NARRE.py:53-64,110-119   the user-side attention reads the embeddings of the items the user's OWN reviews are
+ *                                    about (reviewed_items), the item side those of the users who reviewed the item
+ *                                    (users_who_reviewed): neither reads the other member of the pair
+ *           data.py:240-246          for a rating outside the training split nothing is removed from either side
+ * so both attended vectors are functions of one side only: q[u] = attention_user(u) + user_embedding[u], c[i] =
+ * attention_item(i) + item_embedding[i], W = final.1.weight, b = final.1.bias, w = final.3.weight, and the remaining
+ * scalars go to q_bias / c_bias (reviews4rec_amd.recommend.NarreCatalogue).
+ *
+ * score(u, i) is ONE fixed fp32 expression:
+ *   x_m = q[u][m] * c[i][m]                                   one fp32 multiply, m = 0 .. D-1
+ *   y_j = fmaf(W[j][m], x_m, y_j)                             m ascending from +0.0f, j = 0 .. H-1
+ *   z_j = fmaxf(y_j + b[j], 0.f)                              C's fmaxf: a NaN sum counts as 0, as in r4r_topk_relu
+ *   h_g = fmaf(w[j], z_j, h_g)                                over the j with ((j >> 2) & 3) == g, ascending from +0.0f, g = 0 .. 3
+ *   score = ((((h_0 + h_1) + (h_2 + h_3)) + c_bias[i]) + q_bias[u])
+ * The four-way split of the last sum is the accumulator layout of v_mfma_f32_16x16x4_f32 with rows = hidden units: lane
+ * group l >> 4 holds rows 4 g + r of every 16, so the epilogue is four chains and two cross-lane adds.  A NULL b, q_bias
+ * or c_bias counts as 0.  Zero-padding D to a multiple of 4 and H to a multiple of 16 changes no bit: a pad column
+ * multiplies 0 by 0, a pad row of W gives z = 0, and the pad entries of b and w are zero.  (A NaN anywhere in a
+ * candidate's row makes every y NaN, every z 0 and the score the sum of the biases: mark a row ineligible through c_bias.)
+ *   q [n_q, D] dense, q_bias [n_q] or NULL;  c rows c_stride >= D floats apart (the pad is never read), c_bias [n_c] or
+ *   NULL;  W [H, D] dense, row-major;  b [H] or NULL;  w [H]
+ * Everything else is r4r_topk_dot's contract: score descending, ties by ascending candidate id; a candidate whose score
+ * is -inf or NaN is never returned (-inf in c_bias marks a row ineligible), nor one on the query's ascending CSR
+ * exclusion list (excl_off [n_q + 1], excl_ids; both NULL = none); unused slots hold id -1 and score -inf.  The order
+ * is total and a score's bits depend on its own pair only: the result does not depend on `chunk`, the grid, or how
+ * queries and pairs are grouped into calls.
+ * Limits: 0 <= D <= 64, 0 <= H <= 64 (the native limit of NARRE's engine), 1 <= K <= 128, 0 <= chunk <= 2^30 (0 = the
+ * library's choice), c_stride >= D, w and W non-NULL when H > 0, q and c non-NULL when D > 0, excl_off and excl_ids both
+ * or neither.  n_q == 0, n_c == 0 or n_p == 0 returns R4R_OK, enqueues nothing and leaves the outputs untouched.  Every
+ * refusal precedes the first launch and the first dereference; a short workspace is R4R_ERR_WORKSPACE.  Nothing
+ * allocates, nothing synchronises.
+ *
+ * r4r_topk_hmlp: out_ids / out_scores [n_q, K].  Two launches (an MFMA scan whose A operand is W and whose B operand is
+ *   q * c formed in registers; r4r_topk_dot's merge), or one when the catalogue is a single chunk.  The workspace holds
+ *   the chunks' partial lists in r4r_topk_dot's layout.
+ * r4r_pair_hmlp: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ * r4r_rank_hmlp: r4r_rank_dot's semantics exactly.  out_score[p] has r4r_pair_hmlp's bits; out_rank[p] counts the
+ *   candidates ahead of target t_idx[p] for query row q_idx[p] that are neither -inf / NaN nor on that ROW's exclusion
+ *   list; the target never counts against itself; a target whose own score is -inf or NaN gets -1.  Integer atomics
+ *   only: equal for every chunk, tiling and grouping.  No workspace.
+ * ---------------------------------------------------------------------- */
+size_t r4r_topk_hmlp_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
+int r4r_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                  const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes,
+                  int64_t *out_ids, float *out_scores, void *stream);
+int r4r_pair_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                  const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream);
+int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                  const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                  const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
+                  const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

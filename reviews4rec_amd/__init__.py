@@ -11,7 +11,8 @@ Layout
   dist.py          one-process-per-GPU data parallelism over RCCL
   recommend.py     catalogue top-K lists and full-catalogue ranks (Catalogue, catalogue_limits, fold_fm,
                    ranking_metrics) over csrc/topk.hip; the same for the ReLU-sum heads of deepconn++ and NeuMF
-                   (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip
+                   (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip, and for NARRE's
+                   product-MLP head (NarreCatalogue, narre_catalogue_limits) over csrc/topk_hmlp.hip
 """
 __version__ = '0.1.0'
 
@@ -35,4 +36,5 @@ def get_model_class(model_type):
 
 from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
 from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
+from .recommend import NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
 from .eval import eval_catalogue  # noqa: E402,F401

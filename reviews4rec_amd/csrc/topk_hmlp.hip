@@ -1,0 +1,586 @@
+// Catalogue top-K and ranks over a product-MLP head: r4r_topk_hmlp / r4r_pair_hmlp / r4r_rank_hmlp (include/r4r.h,
+// "Catalogue recommendation: product-MLP heads").
+//
+//   x_m = q[u][m] * c[i][m]            y_j = fmaf(W[j][m], x_m, y_j)   m ascending       z_j = fmaxf(y_j + b[j], 0)
+//   h_g = fmaf(w[j], z_j, h_g)   over the j with ((j >> 2) & 3) == g, ascending
+//   score(u, i) = ((((h_0 + h_1) + (h_2 + h_3)) + c_bias[i]) + q_bias[u])
+//
+// The ReLU sits behind an H x D matrix product per pair: matrix-core work, but not topk.hip's shape.  Here the A operand
+// of v_mfma_f32_16x16x4_f32 is the head's matrix W, shared by every pair, and the B operand is formed in registers:
+// rows = hidden units, columns = 16 candidates, k = the input width.
+// Launch 1, hmlp_scan_kernel: one WAVE per workgroup = (tile of HMLP_QT queries) x (chunk of candidates), no barrier.
+//   A  lane l supplies W[16 ht + (l & 15)][4 t + (l >> 4)] for MFMA (ht, t): loaded once, kept for the whole chunk.
+//   B  lane l loads c[slab + (l & 15)][4 t + (l >> 4)] (one dword per lane and t, as topk.hip does and for its reason) and
+//      multiplies it by its query's q[u][4 t + (l >> 4)]: x, one v_mul_f32 per B fragment.  The tile's queries reuse the
+//      slab's c registers; the next slab's loads are issued before this slab's MFMAs.
+//   C  lane l holds y of hidden units 16 ht + 4 (l >> 4) + r, r = 0 .. 3, for candidate l & 15: the epilogue adds b, takes
+//      fmaxf and runs the h_g chain of ITS lane group g = l >> 4 over (ht, r); two cross-lane adds (xor 16, xor 32: both
+//      orders of either add give the same bits) finish the sum, then the two biases.
+// Scores are never written: each is compared with its query's K-th best, survivors go through topk_device.h's
+// list_insert, the partial lists have r4r_topk_dot's workspace layout and topk.hip's merge kernel finishes (skipped for a
+// single chunk).  r4r_rank_hmlp: the same stream over a tile of PAIRS with counters in place of lists.
+// The scalar kernels (pairs, rank targets, the exclusion correction) compute hmlp_pair_score: the chain above written
+// out.  v_mfma_f32_16x16x4_f32 is bitwise that chain over m (topk.hip), zero rows of W give z = 0 and w = 0 adds
+// nothing, so a score's bits depend on its own pair only.
+#include <math.h>
+
+#include "common.h"
+#include "topk_device.h"
+
+namespace r4r {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int HMLP_MAX_D = 64;
+constexpr int HMLP_MAX_H = 64;
+constexpr int HMLP_QT = 4;         // queries (pairs, for the rank) per wave
+
+// the chunk the call runs with: the caller's, or one that gives every CU its waves (topk_resolve_chunk's rule over
+// this file's query tile)
+inline int64_t hmlp_resolve_chunk(int64_t n_q, int64_t n_c, int64_t chunk) {
+    if (chunk > 0) return chunk;
+    const int64_t tiles = cdiv(n_q, HMLP_QT);
+    int64_t parts = cdiv(TOPK_TARGET_WAVES, tiles > 0 ? tiles : 1);
+    const int64_t most = cdiv(n_c, TOPK_MIN_CHUNK);
+    if (parts > most) parts = most;
+    if (parts < 1) parts = 1;
+    return cdiv(cdiv(n_c, parts), 64) * 64;
+}
+
+// the scalar chain of one pair: q, c point at the pair's rows.  (g is a compile-time index: h stays in registers.)
+__device__ __forceinline__ float hmlp_pair_score(const float *q, const float *c, const float *W, const float *b, const float *w,
+                                                 int D, int H, float cb, float qb) {
+    float h[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int j0 = 0; j0 < H; j0 += 16) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            for (int r = 0; r < 4; ++r) {
+                const int j = j0 + 4 * g + r;
+                if (j >= H) break;
+                const float *Wj = W + (size_t)j * D;
+                float y = 0.f;
+                for (int m = 0; m < D; ++m) {
+                    const float x = q[m] * c[m];
+                    y = __builtin_fmaf(Wj[m], x, y);
+                }
+                const float z = __builtin_fmaxf(y + (b != nullptr ? b[j] : 0.f), 0.f);
+                h[g] = __builtin_fmaf(w[j], z, h[g]);
+            }
+        }
+    }
+    return (((h[0] + h[1]) + (h[2] + h[3])) + cb) + qb;
+}
+
+struct HmlpHead {
+    const float *q, *q_bias, *c, *c_bias, *W, *b, *w;
+    int64_t n_c, c_stride;
+    int D, H;
+};
+
+// What a wave keeps for its whole chunk: the head (A fragments; b and w in the accumulator layout) and the column of
+// each B fragment.  KT: MFMAs over the input width (D <= 4 KT), HT: 16-row tiles of hidden units (H <= 16 HT).
+template <int KT, int HT>
+struct HmlpWave {
+    float wf[HT][KT];          // W[16 ht + row][4 t + kq]; zero beyond H and beyond D
+    float bj[HT][4], wj[HT][4];// b / w of hidden unit 16 ht + 4 kq + r; zero beyond H (and for a NULL b)
+    int jo[KT];                // the column lane (., kq) reads for MFMA t, clamped into the row
+    int row, kq;
+
+    __device__ __forceinline__ void init(const HmlpHead &a, int lane) {
+        row = lane & 15;
+        kq = lane >> 4;
+        const int D = a.D, H = a.H;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) jo[t] = (4 * t + kq < D) ? 4 * t + kq : (D > 0 ? D - 1 : 0);
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            const int j = 16 * ht + row;
+            const int jc = j < H ? j : (H > 0 ? H - 1 : 0);
+#pragma unroll
+            for (int t = 0; t < KT; ++t) wf[ht][t] = 0.f;
+            if (D > 0 && H > 0) {
+#pragma unroll
+                for (int t = 0; t < KT; ++t) wf[ht][t] = a.W[(size_t)jc * D + jo[t]];
+            }
+#pragma unroll
+            for (int t = 0; t < KT; ++t) wf[ht][t] = (j < H && 4 * t + kq < D) ? wf[ht][t] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int e = 16 * ht + 4 * kq + r;
+                const int ec = e < H ? e : (H > 0 ? H - 1 : 0);
+                float bv = 0.f, wv = 0.f;
+                if (H > 0) {
+                    wv = a.w[ec];
+                    if (a.b != nullptr) bv = a.b[ec];
+                }
+                bj[ht][r] = e < H ? bv : 0.f;
+                wj[ht][r] = e < H ? wv : 0.f;
+            }
+        }
+    }
+
+    // the query row `src` as B-fragment multipliers: q[.][4 t + kq], zero beyond D (and for a row that does not exist)
+    __device__ __forceinline__ void query(const HmlpHead &a, const float *src, bool exists, float (&qf)[KT]) const {
+#pragma unroll
+        for (int t = 0; t < KT; ++t) qf[t] = 0.f;
+        if (a.D > 0) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t) qf[t] = src[jo[t]];
+        }
+#pragma unroll
+        for (int t = 0; t < KT; ++t) qf[t] = (exists && 4 * t + kq < a.D) ? qf[t] : 0.f;
+    }
+
+    // The slab's c registers against HMLP_QT queries -> sv[s], the score of candidate `row` for query s (the same in all
+    // four lanes of a candidate), without the query's bias.
+    __device__ __forceinline__ void scores(const float (&bf)[KT], const float (&qf)[HMLP_QT][KT], float cb,
+                                           float (&sv)[HMLP_QT]) const {
+        f32x4 acc[HMLP_QT][HT];
+#pragma unroll
+        for (int s = 0; s < HMLP_QT; ++s)
+#pragma unroll
+            for (int ht = 0; ht < HT; ++ht) acc[s][ht] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // every accumulator sees t ascending; the HMLP_QT * HT chains are independent and interleave in the matrix pipe
+#pragma unroll
+        for (int t = 0; t < KT; ++t)
+#pragma unroll
+            for (int s = 0; s < HMLP_QT; ++s) {
+                const float x = bf[t] * qf[s][t];
+#pragma unroll
+                for (int ht = 0; ht < HT; ++ht)
+                    acc[s][ht] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[ht][t], x, acc[s][ht], 0, 0, 0);
+            }
+#pragma unroll
+        for (int s = 0; s < HMLP_QT; ++s) {
+            float h = 0.f;                                     // h_g of this lane's group g = kq
+#pragma unroll
+            for (int ht = 0; ht < HT; ++ht)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    h = __builtin_fmaf(wj[ht][r], __builtin_fmaxf(acc[s][ht][r] + bj[ht][r], 0.f), h);
+            h = h + __shfl_xor(h, 16);                         // h_0 + h_1 | h_2 + h_3
+            h = h + __shfl_xor(h, 32);                         // (h_0 + h_1) + (h_2 + h_3)
+            sv[s] = h + cb;
+        }
+    }
+};
+
+// the B fragments of one slab in flight: c[slab + row][4 t + kq] and the row's bias
+template <int KT>
+struct HmlpSlab {
+    float bn[KT], cbn;
+
+    __device__ __forceinline__ void clear() {
+        cbn = 0.f;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) bn[t] = 0.f;
+    }
+    // Unconditional loads from clamped addresses: a column past D reads column D - 1 and is zeroed in `take`, a row of
+    // the NEXT chunk is read and ignored, a row past the table reads the table's last row.
+    __device__ __forceinline__ void load(const HmlpHead &a, const int (&jo)[KT], int64_t i) {
+        const int64_t ic = i < a.n_c ? i : a.n_c - 1;
+        const float *src = a.c + ic * a.c_stride;
+        if (a.D > 0) {
+#pragma unroll
+            for (int t = 0; t < KT; ++t) bn[t] = src[jo[t]];
+        }
+        if (a.c_bias != nullptr) cbn = a.c_bias[ic];
+    }
+    __device__ __forceinline__ void take(int D, int kq, float (&bf)[KT], float &cb) const {
+        cb = cbn;
+#pragma unroll
+        for (int t = 0; t < KT; ++t) bf[t] = (4 * t + kq < D) ? bn[t] : 0.f;
+    }
+};
+
+struct HmlpScanArgs {
+    HmlpHead h;
+    const int64_t *excl_off, *excl_ids;
+    float *out_scores;        // [n_q, parts, K]
+    int64_t *out_ids;
+    int64_t n_q, chunk, parts, tiles;
+    int K;
+};
+
+template <int KT, int HT>
+__global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char hmlp_lds[];
+    constexpr int QT = HMLP_QT;
+    const int K = a.K, D = a.h.D;
+    float *sc = reinterpret_cast<float *>(hmlp_lds);           // [QT][K]
+    int *id = reinterpret_cast<int *>(sc + QT * K);            // [QT][K]  candidate - chunk begin
+
+    const int lane = threadIdx.x;
+    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
+    const int64_t u0 = tile * QT;
+    const int64_t c_begin = part * a.chunk;
+    const int64_t c_end = (c_begin + a.chunk < a.h.n_c) ? c_begin + a.chunk : a.h.n_c;
+
+    for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
+
+    HmlpWave<KT, HT> wv;
+    wv.init(a.h, lane);
+    const int row = wv.row, kq = wv.kq;
+    float qf[QT][KT], qb[QT], thr[QT];                         // qb, thr: wave-uniform
+#pragma unroll
+    for (int s = 0; s < QT; ++s) {
+        const int64_t u = u0 + s;
+        const bool exists = u < a.n_q;
+        const int64_t uc = exists ? u : a.n_q - 1;
+        wv.query(a.h, a.h.q + uc * D, exists, qf[s]);
+        qb[s] = a.h.q_bias != nullptr ? a.h.q_bias[uc] : 0.f;
+        thr[s] = exists ? -INFINITY : INFINITY;                // rows past n_q never survive
+    }
+    wave_lds_fence();
+
+    HmlpSlab<KT> nx;
+    float bf[KT], cb;
+    nx.clear();
+    if (c_begin < c_end) nx.load(a.h, wv.jo, c_begin + row);
+    nx.take(D, kq, bf, cb);
+    for (int64_t base = c_begin; base < c_end; base += 16) {
+        if (base + 16 < c_end) nx.load(a.h, wv.jo, base + 16 + row);
+        float sv[QT];
+        wv.scores(bf, qf, cb, sv);
+        const bool live = kq == 0 && base + row < c_end;       // one lane per candidate offers it
+        bool any = false;
+#pragma unroll
+        for (int s = 0; s < QT; ++s) {
+            sv[s] = sv[s] + qb[s];
+            any |= live && sv[s] > thr[s];
+        }
+        if (__ballot(any) != 0) {
+            // survivors, one at a time (wave-uniform control flow from here on)
+#pragma unroll
+            for (int s = 0; s < QT; ++s) {
+                unsigned long long m = __ballot(live && sv[s] > thr[s]);
+                while (m) {
+                    const int src = __builtin_ctzll(m);
+                    m &= m - 1;
+                    const float v = lane_value(sv[s], src);
+                    const int64_t ci = base + src;             // (src < 16: a lane of kq == 0)
+                    if (!(v > thr[s])) continue;               // (an earlier survivor raised the bar)
+                    if (a.excl_off != nullptr) {
+                        int64_t lo = a.excl_off[u0 + s], hi = a.excl_off[u0 + s + 1];
+                        const int64_t end = hi;
+                        while (lo < hi) {
+                            const int64_t mid = lo + ((hi - lo) >> 1);
+                            if (a.excl_ids[mid] < ci) lo = mid + 1; else hi = mid;
+                        }
+                        if (lo < end && a.excl_ids[lo] == ci) continue;
+                    }
+                    thr[s] = list_insert<int>(sc + s * K, id + s * K, K, v, (int)(ci - c_begin), lane);
+                }
+            }
+        }
+        nx.take(D, kq, bf, cb);
+    }
+
+    // the partial lists, filled up with (-inf, -1)
+    for (int ql = 0; ql < QT; ++ql) {
+        const int64_t u = u0 + ql;
+        if (u >= a.n_q) break;
+        const int64_t o = (u * a.parts + part) * K;
+        for (int p = lane; p < K; p += 64) {
+            const int ci = id[ql * K + p];
+            a.out_scores[o + p] = sc[ql * K + p];              // (-inf in an unused slot)
+            a.out_ids[o + p] = ci != fill_id<int>::value ? c_begin + ci : (int64_t)-1;
+        }
+    }
+}
+
+__global__ void pair_hmlp_kernel(HmlpHead a, const int64_t *__restrict__ qi, const int64_t *__restrict__ ci, int64_t n,
+                                 float *__restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t u = qi[p], i = ci[p];
+    out[p] = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H, a.c_bias ? a.c_bias[i] : 0.f,
+                             a.q_bias ? a.q_bias[u] : 0.f);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// r4r_rank_hmlp: r4r_rank_dot's three launches over this file's chain.
+//   A  rank_hmlp_target_kernel   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for a
+//                                target whose own score is -inf or NaN (never touched again)
+//   B  rank_hmlp_scan_kernel     the scan's stream over a tile of HMLP_QT PAIRS (query rows gathered through q_idx) and a
+//                                chunk of candidates; every score is compared with the pair's target in registers and
+//                                counted; one 64-bit integer atomic per (pair, chunk)
+//   C  rank_hmlp_excl_kernel     only with exclusions: B counted the excluded ids too; one wave per pair recomputes the
+//                                scalar chain of its query row's excluded ids and subtracts those that were ahead
+struct HmlpRankArgs {
+    HmlpHead h;
+    const int64_t *q_idx, *t_idx;
+    const float *t_score;     // out_score, written by launch A
+    int64_t *out_rank;
+    int64_t n_p, chunk, tiles;
+};
+
+__global__ void rank_hmlp_target_kernel(HmlpHead a, const int64_t *__restrict__ qi, const int64_t *__restrict__ ti, int64_t n,
+                                        float *__restrict__ out_score, int64_t *__restrict__ out_rank) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const int64_t u = qi[p], i = ti[p];
+    const float s = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H,
+                                    a.c_bias ? a.c_bias[i] : 0.f, a.q_bias ? a.q_bias[u] : 0.f);
+    out_score[p] = s;
+    out_rank[p] = s > -INFINITY ? 0 : -1;                      // (false for NaN)
+}
+
+template <int KT, int HT>
+__global__ __launch_bounds__(64) void rank_hmlp_scan_kernel(HmlpRankArgs a) {
+    constexpr int PT = HMLP_QT;
+    const int D = a.h.D;
+    const int lane = threadIdx.x;
+    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
+    const int64_t p0 = tile * PT;
+    const int64_t c_begin = part * a.chunk;
+    const int64_t c_end = (c_begin + a.chunk < a.h.n_c) ? c_begin + a.chunk : a.h.n_c;
+    const int c_len = (int)(c_end - c_begin);                  // (chunk <= 2^30)
+
+    HmlpWave<KT, HT> wv;
+    wv.init(a.h, lane);
+    const int row = wv.row, kq = wv.kq;
+    // Of each pair: its query row, its query bias, its target's score and its target's id relative to the chunk (-1:
+    // before it, so no tie is ahead; INT_MAX: behind it, so every tie is).  A pair past n_p or at -1 waits for a score
+    // above +inf: it counts nothing.  (All wave-uniform.)
+    float qf[PT][KT], qb[PT], ts[PT];
+    int trel[PT], cnt[PT];
+#pragma unroll
+    for (int s = 0; s < PT; ++s) {
+        const int64_t p = p0 + s;
+        const bool exists = p < a.n_p;
+        const int64_t pc = exists ? p : a.n_p - 1;
+        const int64_t u = a.q_idx[pc];
+        wv.query(a.h, a.h.q + u * D, exists, qf[s]);
+        qb[s] = a.h.q_bias != nullptr ? a.h.q_bias[u] : 0.f;
+        const float st = a.t_score[pc];
+        const int64_t d = a.t_idx[pc] - c_begin;
+        const bool ranked = exists && st > -INFINITY;          // (false for NaN)
+        ts[s] = ranked ? st : INFINITY;
+        trel[s] = !ranked || d < 0 ? -1 : (d > 0x7fffffff ? 0x7fffffff : (int)d);
+        cnt[s] = 0;
+    }
+
+    HmlpSlab<KT> nx;
+    float bf[KT], cb;
+    nx.clear();
+    if (c_begin < c_end) nx.load(a.h, wv.jo, c_begin + row);
+    nx.take(D, kq, bf, cb);
+    for (int64_t base = c_begin; base < c_end; base += 16) {
+        if (base + 16 < c_end) nx.load(a.h, wv.jo, base + 16 + row);
+        float sv[PT];
+        wv.scores(bf, qf, cb, sv);
+        const int rel = (int)(base - c_begin) + row;
+        const bool live = kq == 0 && rel < c_len;              // one lane per candidate counts it
+#pragma unroll
+        for (int s = 0; s < PT; ++s)
+            cnt[s] += (live && ahead<int>(sv[s] + qb[s], rel, ts[s], trel[s])) ? 1 : 0;     // (false for a NaN score)
+        nx.take(D, kq, bf, cb);
+    }
+
+    // lane s adds pair s's count over the wave to its rank -- one atomic instruction per wave
+    int mine = 0;
+#pragma unroll
+    for (int s = 0; s < PT; ++s) {
+        int v = cnt[s];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+        if (lane == s) mine = v;
+    }
+    // (mine > 0 only for a pair below n_p whose target is ranked: the others wait for +inf)
+    if (lane < PT && mine > 0)
+        atomicAdd(reinterpret_cast<unsigned long long *>(a.out_rank + p0 + lane), (unsigned long long)mine);
+}
+
+// One wave per pair over the exclusion list of its query row
+__global__ __launch_bounds__(256) void rank_hmlp_excl_kernel(HmlpHead a, const int64_t *__restrict__ qi,
+                                                             const int64_t *__restrict__ ti, int64_t n_p,
+                                                             const int64_t *__restrict__ excl_off,
+                                                             const int64_t *__restrict__ excl_ids,
+                                                             const float *__restrict__ t_score, int64_t *out_rank) {
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    if (p >= n_p) return;
+    const float st = t_score[p];
+    if (!(st > -INFINITY)) return;                            // a pair at -1 keeps its -1
+    const int64_t u = qi[p], t = ti[p];
+    const int64_t lo = excl_off[u], hi = excl_off[u + 1];
+    const float qb = a.q_bias ? a.q_bias[u] : 0.f;
+    int n = 0;
+    for (int64_t e0 = lo; e0 < hi; e0 += 64) {
+        const int64_t e = e0 + lane;
+        if (e >= hi) continue;
+        const int64_t i = excl_ids[e];
+        if (i < 0 || i >= a.n_c || i == t) continue;
+        const float s = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H,
+                                        a.c_bias ? a.c_bias[i] : 0.f, qb);
+        n += ahead<int64_t>(s, i, st, t) ? 1 : 0;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
+    if (lane == 0 && n > 0)
+        atomicAdd(reinterpret_cast<unsigned long long *>(out_rank + p), (unsigned long long)(-(int64_t)n));
+}
+
+template <int KT, int HT>
+int launch_hmlp_scan(const HmlpScanArgs &a, hipStream_t st) {
+    const size_t lds = (size_t)HMLP_QT * (size_t)a.K * 8;
+    hipLaunchKernelGGL((hmlp_scan_kernel<KT, HT>), dim3((unsigned)(a.parts * a.tiles)), dim3(64), lds, st, a);
+    return check_launch("hmlp_scan_kernel");
+}
+
+template <int KT, int HT>
+int launch_hmlp_rank(const HmlpRankArgs &a, int64_t parts, hipStream_t st) {
+    hipLaunchKernelGGL((rank_hmlp_scan_kernel<KT, HT>), dim3((unsigned)(parts * a.tiles)), dim3(64), 0, st, a);
+    return check_launch("rank_hmlp_scan_kernel");
+}
+
+// KT by D (2, 4, 8, 16 MFMAs over the input width), HT by H (1 .. 4 tiles of 16 hidden units)
+#define HMLP_DISPATCH(FN, D, H, ...)                                                   \
+    do {                                                                               \
+        const int kt_ = (D) <= 8 ? 2 : (D) <= 16 ? 4 : (D) <= 32 ? 8 : 16;             \
+        const int ht_ = (H) <= 16 ? 1 : (H) <= 32 ? 2 : (H) <= 48 ? 3 : 4;             \
+        switch (kt_ * 8 + ht_) {                                                       \
+        case 2 * 8 + 1: return FN<2, 1>(__VA_ARGS__);                                  \
+        case 2 * 8 + 2: return FN<2, 2>(__VA_ARGS__);                                  \
+        case 2 * 8 + 3: return FN<2, 3>(__VA_ARGS__);                                  \
+        case 2 * 8 + 4: return FN<2, 4>(__VA_ARGS__);                                  \
+        case 4 * 8 + 1: return FN<4, 1>(__VA_ARGS__);                                  \
+        case 4 * 8 + 2: return FN<4, 2>(__VA_ARGS__);                                  \
+        case 4 * 8 + 3: return FN<4, 3>(__VA_ARGS__);                                  \
+        case 4 * 8 + 4: return FN<4, 4>(__VA_ARGS__);                                  \
+        case 8 * 8 + 1: return FN<8, 1>(__VA_ARGS__);                                  \
+        case 8 * 8 + 2: return FN<8, 2>(__VA_ARGS__);                                  \
+        case 8 * 8 + 3: return FN<8, 3>(__VA_ARGS__);                                  \
+        case 8 * 8 + 4: return FN<8, 4>(__VA_ARGS__);                                  \
+        case 16 * 8 + 1: return FN<16, 1>(__VA_ARGS__);                                \
+        case 16 * 8 + 2: return FN<16, 2>(__VA_ARGS__);                                \
+        case 16 * 8 + 3: return FN<16, 3>(__VA_ARGS__);                                \
+        default: return FN<16, 4>(__VA_ARGS__);                                        \
+        }                                                                              \
+    } while (0)
+
+int dispatch_hmlp_scan(const HmlpScanArgs &a, hipStream_t st) { HMLP_DISPATCH(launch_hmlp_scan, a.h.D, a.h.H, a, st); }
+int dispatch_hmlp_rank(const HmlpRankArgs &a, int64_t parts, hipStream_t st) {
+    HMLP_DISPATCH(launch_hmlp_rank, a.h.D, a.h.H, a, parts, st);
+}
+
+inline HmlpHead hmlp_head(const float *q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                          const float *c_bias, const float *W, const float *b, const float *w, int D, int H) {
+    HmlpHead h;
+    h.q = q; h.q_bias = q_bias; h.c = c; h.c_bias = c_bias; h.W = W; h.b = b; h.w = w;
+    h.n_c = n_c; h.c_stride = c_stride; h.D = D; h.H = H;
+    return h;
+}
+
+}  // namespace
+}  // namespace r4r
+
+using namespace r4r;
+
+extern "C" size_t r4r_topk_hmlp_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk) {
+    if (n_q <= 0 || n_c <= 0 || K < 1 || K > TOPK_MAX_K || chunk < 0) return 0;
+    const int64_t parts = cdiv(n_c, hmlp_resolve_chunk(n_q, n_c, chunk));
+    if (parts <= 1) return 0;
+    return (size_t)n_q * (size_t)parts * (size_t)K * (sizeof(float) + sizeof(int64_t));
+}
+
+extern "C" int r4r_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                             const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                             const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes,
+                             int64_t *out_ids, float *out_scores, void *stream) {
+    R4R_REQUIRE(K >= 1 && K <= TOPK_MAX_K, "topk_hmlp: K = %d outside 1 .. %d", K, TOPK_MAX_K);
+    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "topk_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
+    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "topk_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
+    R4R_REQUIRE(n_q >= 0 && n_c >= 0, "topk_hmlp: negative n_q or n_c");
+    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "topk_hmlp: chunk = %lld outside 0 .. 2^30", (long long)chunk);
+    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "topk_hmlp: excl_off and excl_ids go together (both or neither)");
+    R4R_REQUIRE(n_q == 0 || (out_ids != nullptr && out_scores != nullptr), "topk_hmlp: null output");
+    R4R_REQUIRE(n_q < ((int64_t)1 << 31), "topk_hmlp: n_q = %lld too large", (long long)n_q);
+    R4R_REQUIRE(c_stride >= D, "topk_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
+    if (n_q == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
+    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "topk_hmlp: null w or W with H > 0");
+    R4R_REQUIRE(D == 0 || (q != nullptr && c != nullptr), "topk_hmlp: null q or c with D > 0");
+    HmlpScanArgs a;
+    a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    a.excl_off = excl_off; a.excl_ids = excl_ids;
+    a.n_q = n_q; a.K = K;
+    a.chunk = hmlp_resolve_chunk(n_q, n_c, chunk);
+    a.parts = cdiv(n_c, a.chunk);
+    a.tiles = cdiv(n_q, HMLP_QT);
+    R4R_REQUIRE(a.parts * a.tiles < ((int64_t)1 << 31), "topk_hmlp: %lld chunks x %lld query tiles exceed the grid",
+                (long long)a.parts, (long long)a.tiles);
+    const size_t need = r4r_topk_hmlp_ws_bytes(n_q, n_c, K, chunk);
+    if (need > 0 && (ws == nullptr || ws_bytes < need)) {
+        set_error("topk_hmlp: workspace %zu < %zu bytes", ws_bytes, need);
+        return R4R_ERR_WORKSPACE;
+    }
+    hipStream_t st = as_stream(stream);
+    if (a.parts == 1) {
+        a.out_scores = out_scores;
+        a.out_ids = out_ids;
+    } else {
+        a.out_ids = reinterpret_cast<int64_t *>(ws);
+        a.out_scores = reinterpret_cast<float *>(a.out_ids + (size_t)n_q * a.parts * K);
+    }
+    const int rc = dispatch_hmlp_scan(a, st);
+    if (rc != R4R_OK || a.parts == 1) return rc;
+    return topk_launch_merge(a.out_scores, a.out_ids, n_q, a.parts, K, out_ids, out_scores, st);
+}
+
+extern "C" int r4r_pair_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                             const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                             const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream) {
+    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "pair_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
+    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "pair_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
+    R4R_REQUIRE(n >= 0 && n_q >= 0 && n_c >= 0, "pair_hmlp: negative size");
+    if (n == 0) return R4R_OK;
+    R4R_REQUIRE(n_q > 0 && n_c > 0, "pair_hmlp: pairs into an empty table");
+    R4R_REQUIRE(c_stride >= D, "pair_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
+    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "pair_hmlp: null w or W with H > 0");
+    R4R_REQUIRE(q_idx != nullptr && c_idx != nullptr && out != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
+                "pair_hmlp: null pointer");
+    R4R_REQUIRE(cdiv(n, 256) < ((int64_t)1 << 31), "pair_hmlp: n = %lld exceeds the grid", (long long)n);
+    const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    hipLaunchKernelGGL(pair_hmlp_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), h, q_idx, c_idx, n, out);
+    return check_launch("pair_hmlp_kernel");
+}
+
+extern "C" int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                             const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                             const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
+                             const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream) {
+    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "rank_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
+    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "rank_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
+    R4R_REQUIRE(n_p >= 0 && n_q >= 0 && n_c >= 0, "rank_hmlp: negative n_p, n_q or n_c");
+    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "rank_hmlp: chunk = %lld outside 0 .. 2^30", (long long)chunk);
+    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "rank_hmlp: excl_off and excl_ids go together (both or neither)");
+    R4R_REQUIRE(c_stride >= D, "rank_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
+    R4R_REQUIRE(n_p == 0 || (out_rank != nullptr && out_score != nullptr), "rank_hmlp: null output");
+    if (n_p == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
+    R4R_REQUIRE(n_q > 0, "rank_hmlp: pairs into an empty query table");
+    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "rank_hmlp: null w or W with H > 0");
+    R4R_REQUIRE(q_idx != nullptr && t_idx != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
+                "rank_hmlp: null pointer (q_idx, t_idx, or q / c with D > 0)");
+    HmlpRankArgs a;
+    a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    a.q_idx = q_idx; a.t_idx = t_idx;
+    a.t_score = out_score; a.out_rank = out_rank;
+    a.n_p = n_p;
+    a.chunk = hmlp_resolve_chunk(n_p, n_c, chunk);
+    a.tiles = cdiv(n_p, HMLP_QT);
+    const int64_t parts = cdiv(n_c, a.chunk);
+    R4R_REQUIRE(parts * a.tiles < ((int64_t)1 << 31) && cdiv(n_p, 4) < ((int64_t)1 << 31),
+                "rank_hmlp: %lld chunks x %lld pair tiles exceed the grid", (long long)parts, (long long)a.tiles);
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(rank_hmlp_target_kernel, dim3((unsigned)cdiv(n_p, 256)), dim3(256), 0, st, a.h, q_idx, t_idx, n_p,
+                       out_score, out_rank);
+    int rc = check_launch("rank_hmlp_target_kernel");
+    if (rc != R4R_OK) return rc;
+    rc = dispatch_hmlp_rank(a, parts, st);
+    if (rc != R4R_OK || excl_off == nullptr) return rc;
+    hipLaunchKernelGGL(rank_hmlp_excl_kernel, dim3((unsigned)cdiv(n_p, 4)), dim3(256), 0, st, a.h, q_idx, t_idx, n_p, excl_off,
+                       excl_ids, (const float *)out_score, out_rank);
+    return check_launch("rank_hmlp_excl_kernel");
+}

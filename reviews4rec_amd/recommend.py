@@ -28,8 +28,18 @@ everything after the ReLU is linear down to one scalar, so
 ranked by r4r_topk_relu / r4r_rank_relu (csrc/topk_relu.hip; ``fold_relu_head`` has the table, ``relu_catalogue_limits``
 the limits).  ``main``'s hooks (``recommend_k``, ``catalogue_metrics_k``) build whichever class serves the model
 through ``make_catalogue``; they accept deepconn++ and still refuse NeuMF, which is served through the class and
-``eval.eval_catalogue(catalogue=ReluCatalogue(...))`` only.  MF, NARRE and the TransNets need an O(L^2) product per
-pair between the two sides and stay refused.
+``eval.eval_catalogue(catalogue=ReluCatalogue(...))`` only.
+
+NARRE's head is Linear -> ReLU -> Linear over the ELEMENTWISE PRODUCT of the two sides, and each side's attention reads
+only that side's own neighbours (NARRE.py:110-113; nothing is removed for a rating outside the training split,
+data.py:240-246), so per-user and per-item vectors exist and
+
+    score(u, i) = sum_j w_j relu(<W_j, au[u] * ai[i]> + b_j) + user scalar + item scalar
+
+is ranked by r4r_topk_hmlp / r4r_rank_hmlp (csrc/topk_hmlp.hip: an MFMA scan whose A operand is W) through
+``NarreCatalogue`` (``narre_catalogue_limits`` has the limits) and ``eval.eval_catalogue(catalogue=NarreCatalogue(...))``;
+``main``'s hooks still refuse it.  MF and the TransNets need an FM over a per-pair transform of the two sides and stay
+refused.
 
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
@@ -45,7 +55,7 @@ MAX_D, MAX_K, FM_RANK = 256, 128, 8
 
 _REFUSED = {
     'deepconn++': 'its head is Linear -> ReLU over [user | item] (DeepCoNN.py:68-72): the pair score is not bilinear',
-    'NARRE': 'its review attention weighs every review by the OTHER side\'s id embedding (NARRE.py): no per-item vector exists',
+    'NARRE': 'its head is Linear -> ReLU over the elementwise product of the two sides (NARRE.py:38-43,121-123): the pair score is not bilinear',
     'transnet': 'its score is an FM over a ReLU transform of the pair\'s joint document (TransNet.py): not bilinear',
     'transnet++': 'its score is an FM over a ReLU transform of the pair\'s joint document (TransNet.py): not bilinear',
     'MF': 'its head is Linear -> ReLU over [user | item] before the FM (MF.py:60-66): the pair score is not bilinear',
@@ -549,6 +559,183 @@ class ReluCatalogue(Catalogue):
         qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
         _lib.call('r4r_rank_relu', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
                   ptr(self.w), self.H, self.P, ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0, ptr(ranks), ptr(scores))
+        return ranks, scores
+
+
+HMLP_MAX_L = 64                     # r4r_topk_hmlp: D <= 64, H <= 64
+
+
+def narre_catalogue_limits(hyper_params):
+    """None when ``NarreCatalogue`` can rank this configuration, else the reason it cannot."""
+    from .data import NEIGHBOURS
+    mt = hyper_params['model_type']
+    if mt in SUPPORTED:
+        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
+    if mt in ('deepconn++', 'NeuMF'):
+        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
+    if mt != 'NARRE':
+        why = _REFUSED.get(mt)
+        return 'model_type %r has no product-MLP form%s' % (mt, ': ' + why if why else '')
+    if _latent_size(hyper_params) > HMLP_MAX_L:
+        return 'latent_size %d > %d' % (_latent_size(hyper_params), HMLP_MAX_L)
+    R = int(hyper_params.get('narre_num_reviews', NEIGHBOURS))
+    if R != NEIGHBOURS:
+        return ('narre_num_reviews %d is not the width of the neighbour lists, %d (NARRE.py:56 concatenates the two)'
+                % (R, NEIGHBOURS))
+    return None
+
+
+class NarreCatalogue(Catalogue):
+    """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
+    (-1, -inf) fill and argument checks) for NARRE, ranked by r4r_topk_hmlp / r4r_pair_hmlp / r4r_rank_hmlp.
+
+    NARRE's attention weighs the reviews of one side by the id embeddings of THAT side's neighbours -- the items a
+    user's own reviews are about, the users who reviewed an item (NARRE.py:110-113) -- and a rating outside the training
+    split removes nothing from either list (data.py:240-246).  So
+
+        au[u] = attention_user(zu[u, 0..R), item_embedding[reviewed_items[u]]) + user_embedding[u]        per user
+        ai[i] = attention_item(zi[i, 0..R), user_embedding[users_who_reviewed[i]]) + item_embedding[i]    per item, cached
+        score(u, i) = final.3(relu(final.1(au[u] * ai[i]))) + user_bias[u] + item_bias[i] + global_bias
+
+    ``refresh()`` flushes the engine's pending row updates and caches the item side (``c`` = ai, ``c_bias`` = item_bias
+    with -inf in ineligible rows, ``W``, ``b``, ``w`` from final.1 / final.3), ``tower_batch`` items at a time: one tower
+    forward per review and the eval-mode attention.  The query side is computed per call from the current weights.  A
+    pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks do not reach this
+    class; NARRE is served here and through ``eval_catalogue(catalogue=NarreCatalogue(...))``."""
+
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
+        why = narre_catalogue_limits(hyper_params)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
+        self.mt = hyper_params['model_type']
+        self.tower_batch = int(tower_batch)
+        self.dev = next(model.parameters()).device
+        if self.dev.type != 'cuda':
+            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
+                               'CPU fallback')
+        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
+        self.eligible = eligible_items(hyper_params, train_reader, candidates)
+        self.D = self.H = _latent_size(hyper_params)
+        self.n_c = self.n_items                                # candidate rows the kernel walks: one per item id
+        self._seen = None
+        self.refresh()
+
+    def _attended(self, side, ids):
+        """au (side 'user') or ai ('item') [n, L] of the owners ``ids`` (a host int64 array) from the current weights:
+        every review of the owner and its neighbour ids with nothing removed (data.py:240-246; pad id total + 1 of
+        the OTHER side, data.py:275-276), one eval-mode tower forward per review, the eval-mode attention, the owner's
+        id embedding."""
+        from .data import _np_neighbours, _np_reviews
+        m, hp = self.model, self.hp
+        user = side == 'user'
+        pool = self.reader.store.users if user else self.reader.store.items
+        ids = np.asarray(ids, dtype=np.int64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
+            raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        R, Wd = int(hp['narre_num_reviews']), int(hp['narre_num_words'])
+        rb, re = pool.first[ids], pool.first[ids + 1]
+        none = np.full(len(ids), -1, np.int64)
+        reviews = _np_reviews(pool.tok, pool.rev_off, rb, re, none, R, Wd)
+        pad = (self.n_items if user else self.n_users) + 1
+        nb = torch.from_numpy(_np_neighbours(pool.nb, rb, re, none, pad)).to(self.dev)
+        conv, scorer = (m.user_conv, m.attention_scorer_user) if user else (m.item_conv, m.attention_scorer_item)
+        own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
+        with torch.no_grad():
+            z = self._tower(conv, torch.from_numpy(reviews.reshape(len(ids) * R, Wd)).to(self.dev)).view(len(ids), R, -1)
+            att = ops.narre_attention(z, other.weight.detach()[nb].contiguous(), scorer[0].weight.detach(),
+                                      scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach(),
+                                      0.0, False, None)
+            return att + own.weight.detach()[torch.from_numpy(ids).to(self.dev)]
+
+    def refresh(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+        m = self.model
+        elig = torch.from_numpy(self.eligible).to(self.dev)
+        c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
+        cb = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
+                sel = elig[s:s + self.tower_batch]                                                # dropped chunk by chunk
+                c[sel] = self._attended('item', self.eligible[s:s + self.tower_batch])
+            cb[elig] = m.item_bias.detach()[elig]
+            self.c, self.c_bias = c, cb
+            self.W = m.final[1].weight.detach().to(torch.float32).contiguous().clone()
+            self.b = m.final[1].bias.detach().to(torch.float32).contiguous().clone()
+            self.w = m.final[3].weight.detach().to(torch.float32).reshape(-1).contiguous().clone()
+
+    def _queries(self, u_host):
+        """(q [n, L], q_bias [n]) of the requested users from the current weights."""
+        m = self.model
+        u = u_host.to(self.dev)
+        ids = u_host.numpy()
+        q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            for s in range(0, len(ids), self.tower_batch):
+                q[s:s + self.tower_batch] = self._attended('user', ids[s:s + self.tower_batch])
+            qb = (m.user_bias.detach()[u] + m.global_bias.detach()) + m.final[3].bias.detach().reshape(())
+        return q, qb.contiguous()
+
+    def _head(self, q, n, qb):
+        return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.w),
+                self.D, self.H)
+
+    def recommend(self, users, k=10, exclude_seen=True):
+        """``Catalogue.recommend``'s contract over the product-MLP head (one r4r_topk_hmlp call)."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
+        u = self._users(users)
+        n = int(u.numel())
+        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return items, scores
+        q, qb = self._queries(u)
+        eo, ei = self._exclusions(u) if exclude_seen else (None, None)
+        lib = _lib.lib()
+        ws = ops._workspace(lib.r4r_topk_hmlp_ws_bytes(n, self.n_c, k, 0), self.dev)
+        _lib.call('r4r_topk_hmlp', *self._head(q, n, qb), ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items),
+                  ptr(scores))
+        return items, scores
+
+    def score_pairs(self, users, items):
+        """``Catalogue.score_pairs``' contract over the product-MLP head (one r4r_pair_hmlp call)."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+        if u.numel() == 0:
+            return out
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_pair_hmlp', *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ci), int(u.numel()), ptr(out))
+        return out
+
+    def rank(self, users, items, exclude_seen=True):
+        """``Catalogue.rank``'s contract over the product-MLP head (one r4r_rank_hmlp call: no list, no sort)."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        n = int(u.numel())
+        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return ranks, scores
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
+        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_rank_hmlp', *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0,
+                  ptr(ranks), ptr(scores))
         return ranks, scores
 
 
