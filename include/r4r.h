@@ -666,7 +666,9 @@ int r4r_deepconnpp_rows_apply(const int64_t *uid_all, const int64_t *iid_all, co
  * holds per rating (r4r_transnet_ws_offset which = 3) the target prediction, its squared error and
  * ||s_ir - t_ir||^2.  Dropout draws per rating at Philox counter offset + b*(5L+10) + k:
  * source.user_conv.dropout [L], source.item_conv.dropout [L], target.conv.dropout [L],
- * source.dropout [L], target.dropout [L], dropout.user [5], dropout.item [5]. */
+ * source.dropout [L], target.dropout [L], dropout.user [5], dropout.item [5] (plain TransNet has no ID
+ * vectors: its last ten positions are drawn and recorded in the workspace's [B, 5L+10] multipliers like
+ * the others, and no site consumes them). */
 int r4r_transnet_nparam(void);
 int r4r_transnet_layout(int E, int L, int plus, int64_t *offsets, int64_t *sizes, int64_t *total);
 size_t r4r_transnet_ws_bytes(int64_t B, int T, int E, int L, int plus, int64_t V, int64_t n_users, int64_t n_items);

@@ -243,6 +243,10 @@ __global__ __launch_bounds__(256) void tn_head_kernel(TnHead a) {
         const float m = draw(5 * L + k);
         finm[k] = m;
         fin[k] = idv * m;
+    } else if (!a.plus && tid >= 64 && tid < 64 + 2 * TN_ID) {
+        // plain TransNet has no ID vectors, but a rating still owns 5L + 10 stream positions (r4r.h): the last ten are
+        // recorded like the others -- the [B, 5L + 10] block is the whole counter range -- and nothing consumes them
+        draw(5 * L + (tid - 64));
     }
     __syncthreads();
     HEAD_STAMP(1)
