@@ -303,7 +303,7 @@ int r4r_peer_wait(const uint32_t *flags, int world, uint32_t epoch, uint32_t *ti
 /* ------------------------------------------------------------------------
  * Fused DeepCoNN step ('deepconn' mode): the whole of DeepCoNN.forward
  * (DeepCoNN.py:37-66) + MSELoss/mean (loss.py:7-11, main.py:56-58) + backward in
- * ONE call that enqueues 6 kernels (both towers share the conv launch).
+ * ONE call that enqueues 4 or 5 kernels (both towers share every launch; r4r_deepconn_tail).
  * Replaces, per training step, every ATen op main.py:32,56-59 dispatches.
  *
  * The trainable parameters of this mode live in ONE flat fp32 buffer; slot i of
@@ -324,9 +324,12 @@ int r4r_peer_wait(const uint32_t *flags, int world, uint32_t epoch, uint32_t *ti
  *   tokens_ready   : != 0 when that buffer already holds this batch's compacted tokens
  *                    (prepared by r4r_deepconn_tokens or by the previous step, below)
  *   next_user_idx / next_item_idx (both or neither; training steps only): the NEXT batch of the
- *                    same B and T.  Its token marks ride on this step's backward launch and their
- *                    compaction on the gradient-reduce launch, into buffer token_buffer ^ 1; call
- *                    the next step with that buffer and tokens_ready = 1.
+ *                    same B and T.  Its token state is prepared into buffer token_buffer ^ 1; call
+ *                    the next step with that buffer and tokens_ready = 1.  Which launch carries what:
+ *                    four-launch step (r4r_deepconn_tail() == 1): segment flags AND token marks on the
+ *                    head launch, plan scan and compaction on the backward launch; five-launch step:
+ *                    segment flags on the head launch, plan scan and marks on the backward launch,
+ *                    compaction on the gradient-reduce launch.  The state left behind is the same.
  *   flat_m / flat_v (both or neither; layout of flat_p): when given, the step is also the
  *                    optimiser -- torch.optim.Adam(lr, betas, eps, weight_decay) update number
  *                    adam_step (1-based) of flat_p in place (main.py:94-96,60), done by the launch
@@ -345,6 +348,7 @@ size_t r4r_deepconn_ws_mult_offset(int64_t B, int T, int E, int L, int64_t V);  
 size_t r4r_deepconn_ws_count_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer);   /* token counter of (tower, token buffer): int[0] live count, int[1] the count the last gather consumed, int[2] whether the last gather that was given a segment plan followed it */
 size_t r4r_deepconn_ws_partials_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int which);   /* (tests) the tower's conv partials [B, tiles, 112]: which = 0 pmax, 1 parg */
 size_t r4r_deepconn_ws_plan_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer, int which);   /* (tests) the gather's segment plan (r4r_gather_plan) of (tower, token buffer): which = 0 perm int[B tiles], 1 plan_ready int[1], 2 live */
+size_t r4r_deepconn_ws_state_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer, int which);   /* (tests) token state of (tower, token buffer): which = 0 flags int[V + 4], 1 slot int[V + 4], 2 list int[count]; 3 = the tower's pooling argmax int[B, 100] (buffer ignored) */
 int r4r_deepconn_step(const float *table, int64_t V, const int64_t *user_idx, const int64_t *item_idx,
                       const float *y, float *flat_p, float *flat_g,
                       float *pred, float *se, float *sse_accum,
@@ -355,6 +359,18 @@ int r4r_deepconn_step(const float *table, int64_t V, const int64_t *user_idx, co
                       const int64_t *next_user_idx, const int64_t *next_item_idx,
                       float *flat_m, float *flat_v, float lr, double beta1, double beta2, float eps,
                       float weight_decay, int64_t adam_step, void *stream);
+/* Tail of a DeepCoNN training step (A/B runs and tests; results are bit-identical).  1 (default): wherever the shape
+ * allows, the step is FOUR launches -- GEMM, gather, head, backward -- and the backward launch finishes every gradient
+ * sum and takes every Adam step itself (main.py:59-60): one workgroup per (tower, filter, tap) of the conv gradient
+ * holds all batch splits of its row, so no partial sum leaves the chip and no workgroup waits for another.  0: always
+ * the five-launch step, whose gradient-reduce launch sums the splits' partials and runs Adam (R4R_TAIL=old in the
+ * environment starts a process with 0).  Process-wide, like r4r_gemm_form.  Returns the previous setting.
+ * r4r_deepconn_tail(B, E, L) -> 1 where a training step of that batch size, word_embed_size and latent_size takes the
+ * four-launch form under the current switch, else 0.  A pure function of its arguments and the switch: the batch must
+ * be at most 256 ratings, (batch splits) x E / 4 at most 1,024 (one thread per float4 column and split: E = 300 at
+ * B = 128 is 8 x 76; E = 768 at B = 128 is not taken), latent_size at most 64. */
+int r4r_deepconn_tail_fold(int on);
+int r4r_deepconn_tail(int64_t B, int E, int L);
 /* Token compaction of a batch (distinct tokens -> dense rows) into token-state buffer 0 or 1 of the
  * workspace.  It depends only on the indices, so the caller may run it for batch k+1 on another
  * stream while step k computes, and then pass token_buffer / tokens_ready = 1 to step k+1

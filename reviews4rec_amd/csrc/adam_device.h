@@ -75,6 +75,15 @@ __device__ __forceinline__ void adam_pair_fast(adam_f32x2 &p, adam_f32x2 g, adam
 #endif
 }
 
+// The optimiser as a rider of the launch that finishes a gradient (engine.hip's four-launch step): the element whose
+// gradient sits at g + o is parameter p[o] with moments m[o], v[o].  on = 0: the launch stops at the gradient.
+struct FlatAdam {
+    float *p, *m, *v;            // flat parameter / moment buffers, laid out like the flat gradient
+    const float *g;              // the flat gradient's base
+    AdamScalars s;
+    int on;
+};
+
 // step >= 1: the 1-based count of this update
 static inline AdamScalars adam_make_scalars(float lr, double beta1, double beta2, float eps, float weight_decay,
                                             int64_t step, const int64_t *step_dev) {

@@ -10,6 +10,8 @@
 //   4 head parameter gradients, reduced over the batch in a fixed order (here)
 //   5 argmax-sparse conv wgrad, both towers    (textcnn.hip)
 //   6 wgrad partial reduce -> flat gradient buffer
+// (Since then: project-then-gather for 1+2, 4 fused into 5, and -- where the shape allows, tail_folds() below -- 6 fused
+// into 5 as well: GEMM, gather, head, backward.)
 // All trainable parameters live in ONE flat fp32 buffer (layout below) and so do the
 // gradients: data parallelism is a single RCCL all-reduce over `flat_g`, and Adam is
 // a single r4r_adam_multi sweep over one "tensor".
@@ -76,6 +78,10 @@ struct HeadArgs {
     // (plan.units > 0), and rating 0 withdraws the plan this step's gather has just used (plan_spent, nullable)
     PlanArgs plan;
     int *plan_spent[2];
+    // four-launch step: the token MARKS of the next batch ride here too, in `mark_wgs` workgroups behind the flag role's
+    // (0: they ride on the backward launch); read through kernel_args, inside their own branch
+    TokenArgs marks;
+    int mark_wgs;
 };
 
 
@@ -98,7 +104,15 @@ __global__ __launch_bounds__(256) void deepconn_head_wg_kernel(HeadArgs a) {
     // RESERVE the instantiation's static LDS: 13 KB at latent_size <= 16, several per CU; at 65 .. 128 -- 115 KB -- one
     // per CU, where the role would queue behind the ratings.  Measured at the headline's latent size only.)
     if ((int64_t)blockIdx.x >= a.B) {
-        segment_flags_wave(a.plan, ((int)blockIdx.x - (int)a.B) * 4 + (int)(threadIdx.x >> 6));
+        const int fb = (int)blockIdx.x - (int)a.B, flag_wgs = (2 * a.plan.units + 3) / 4;
+        if (fb < flag_wgs) {
+            segment_flags_wave(a.plan, fb * 4 + (int)(threadIdx.x >> 6));
+        } else {
+            // the marks role (same reservation of LDS, same idle CUs); the compaction that consumes the marks is a role of
+            // the NEXT launch, so they are complete grid-wide when it reads them
+            const HeadArgs &A = kernel_args<HeadArgs>();
+            token_mark_block(A.marks, fb - flag_wgs, A.mark_wgs, 256);
+        }
         return;
     }
     HEAD_STAMP(0)
@@ -313,8 +327,13 @@ struct HeadGradArgs {
 // HG_ROWS row groups of one 256-thread workgroup (fixed order -> deterministic).  `blk`
 // selects the HG_COLS outputs this workgroup owns: few outputs x many row groups keeps each
 // thread's serial chain short (B / 16 terms).
+// STEP (the four-launch step): the thread that finishes an output also takes that parameter's Adam step, with the very
+// sum it has just written (parameter and moments requested up front: their addresses depend on nothing).  No workgroup
+// of the launch reads a parameter another one steps: `cv` below is read before the block's barrier by the column that
+// steps it behind the barrier.
 constexpr int HG_ROWS = 16, HG_COLS = 16;
-__device__ __forceinline__ void head_grad_block(const HeadGradArgs &a, int blk) {
+template <bool STEP = false>
+__device__ __forceinline__ void head_grad_block(const HeadGradArgs &a, int blk, const FlatAdam *opt = nullptr) {
     __shared__ float red[HG_ROWS][HG_COLS];
     const int ox = threadIdx.x & (HG_COLS - 1), rg = threadIdx.x / HG_COLS;
     const int L = a.L, n = 2 * L;
@@ -334,6 +353,18 @@ __device__ __forceinline__ void head_grad_block(const HeadGradArgs &a, int blk) 
     // (with the switch inside the loop hipcc kept the loads behind each other: 8 dependent round trips to data
     // another XCD wrote a moment ago -- the launch's longest chain, 9.4 us of tools/head_trace.py --backward).
     // Same ascending-b order per output as before.
+    float P = 0.f, M = 0.f, V = 0.f;
+    int po = 0;                                              // (the flat layout is far below 2^31 elements)
+    bool stepping = false;
+    if constexpr (STEP) {
+        if (opt->on && rg == 0 && which >= 0 && which < 8) {    // (the SE sum has no parameter)
+            const float *dst = which == 0 ? a.g_fc_w[0] + local : (which == 1 ? a.g_fc_b[0] + local : (which == 2 ? a.g_fc_w[1] + local :
+                  (which == 3 ? a.g_fc_b[1] + local : (which == 4 ? a.g_V + local : (which == 5 ? a.g_lin_w + local :
+                  (which == 6 ? a.g_lin_b : a.g_gb))))));
+            po = (int)(dst - opt->g);
+            stepping = true;
+        }
+    }
     float s = 0.f;
     if (which >= 0) {
         // (plain selects, no switch: hipcc's lowering of a divergent switch over these pointer assignments lost the
@@ -369,6 +400,11 @@ __device__ __forceinline__ void head_grad_block(const HeadGradArgs &a, int blk) 
             }
         }
     }
+    if constexpr (STEP) {
+        // (requested here, under the barrier and the column's sum, not at the top: held across the batch loop they were
+        // three registers the launch's 64 do not have, parked in scratch)
+        if (stepping) { P = opt->p[po]; M = opt->m[po]; V = opt->v[po]; }
+    }
     red[rg][ox] = s;
     __syncthreads();
     if (rg == 0 && which >= 0) {
@@ -385,6 +421,12 @@ __device__ __forceinline__ void head_grad_block(const HeadGradArgs &a, int blk) 
             case 6: a.g_lin_b[0] = t; break;
             case 7: a.g_gb[0] = t; break;
             default: if (a.sse_accum) a.sse_accum[0] += t; break;
+        }
+        if constexpr (STEP) {
+            if (stepping) {
+                adam_elem(P, t, M, V, opt->s);
+                opt->p[po] = P; opt->m[po] = M; opt->v[po] = V;
+            }
         }
     }
 }
@@ -428,6 +470,64 @@ __global__ __launch_bounds__(WG_THREADS, 8) void deepconn_backward_kernel(DcBack
         const int np = plan.units > 0 ? 2 : 0, blk = blockIdx.y * gridDim.x + blockIdx.x;
         if (blk < np) segment_plan_block<WG_THREADS>(plan, blk);
         else token_mark_block(nx, blk - np, gridDim.x * gridDim.y - np, WG_THREADS);
+    }
+#ifdef R4R_TRACE
+    __syncthreads();                                        // the workgroup's end, not thread 0's
+#endif
+    BWD_STAMP(1, wall_clock64())
+}
+
+// The four-launch step's backward: EVERY sum of the step is finished here by the one workgroup that formed all of its
+// terms, and stepped there -- no reduce launch behind it, no hand-over between workgroups.
+//   z = 1, 2  tower z - 1's conv gradient, one workgroup per (filter, tap) holding all splits (wgrad_row_block): the
+//             launch's block size is that role's nsplit * E/4 threads (whole waves, at least 256)
+//   z = 0     head parameter gradients + their Adam step (head_grad_block<true>)
+//   z >= 3    (next batch announced) the plan scan in the first two workgroups, then the next batch's token COMPACTION:
+//             its marks were a role of the head launch, one launch earlier than in the five-launch step
+// The roles of z = 0 and z >= 3 are written for 256 threads: the further waves of their workgroups end at once (the
+// barrier of a workgroup counts its surviving waves only).
+struct DcFoldArgs {
+    WgradArgs w;
+    FlatAdam opt;
+    HeadGradArgs h;
+    int hg_blocks;
+    TokenArgs nx;
+    PlanArgs plan;
+    int comp_blocks;             // compaction workgroups per tower (0: no next batch)
+};
+// BIGV: the compaction's large-vocabulary form (V > COMPACT_BIG_V, eight int4 of flags per thread: it does not fit the
+// launch's 64 registers); the other instantiation carries the one-group form only and has no scratch access at all.
+static_assert(WG_THREADS % 64 == 0, "the 256-thread roles of the fold launch are whole waves: the others end before any barrier");
+template <bool BIGV>
+__global__ __launch_bounds__(WG_ROW_MAX_THREADS, 8) void deepconn_backward_fold_kernel(DcFoldArgs) {
+    const DcFoldArgs &A = kernel_args<DcFoldArgs>();
+    BWD_STAMP(0, wall_clock64())
+    BWD_STAMP(2, (unsigned long long)blockIdx.z + 1)
+    if (blockIdx.z == 1 || blockIdx.z == 2) {
+        wgrad_row_block(A.w, A.opt, blockIdx.x, blockIdx.y, blockIdx.z - 1);
+    } else {
+        // (WHOLE waves leave, before the role's first barrier: s_barrier releases when every wave of the workgroup that has
+        // not ended has arrived -- CDNA3/4 ISA, "S_BARRIER" -- so the 256-thread roles synchronise among their four
+        // waves exactly as in a 256-thread workgroup)
+        if (threadIdx.x >= WG_THREADS) return;
+        const int blk0 = blockIdx.y * gridDim.x + blockIdx.x, nblk = gridDim.x * gridDim.y;
+        if (blockIdx.z == 0) {
+            for (int blk = blk0; blk < A.hg_blocks; blk += nblk) {
+                head_grad_block<true>(A.h, blk, &A.opt);
+                __syncthreads();
+            }
+        } else {
+            const int np = A.plan.units > 0 ? 2 : 0, comp_blocks = A.comp_blocks;
+            const int blk = ((int)blockIdx.z - 3) * nblk + blk0;
+            if (blk < np) {
+                segment_plan_block<WG_THREADS>(A.plan, blk);
+            } else if (blk - np < 2 * comp_blocks) {
+                const int t = (blk - np) >= comp_blocks;
+                const TokenTower &tw = t ? A.nx.t[1] : A.nx.t[0];
+                if constexpr (BIGV) token_compact_block<WG_THREADS / 64, COMPACT_BIG_G>(tw, A.nx.V, blk - np - t * comp_blocks);
+                else token_compact_block<WG_THREADS / 64, 1>(tw, A.nx.V, blk - np - t * comp_blocks);
+            }
+        }
     }
 #ifdef R4R_TRACE
     __syncthreads();                                        // the workgroup's end, not thread 0's
@@ -592,12 +692,47 @@ extern "C" size_t r4r_deepconn_ws_plan_offset(int64_t B, int T, int E, int L, in
     return (which < 0 || which > 2) ? 0 : (size_t)(static_cast<const char *>(at[which]) - base);
 }
 
+// ... and the token state of (tower, token buffer) with the head's argmax: which = 0 flags int[V + 4], 1 slot int[V + 4],
+// 2 list int[count], 3 argmax int[B, 100] (of the tower: `buffer` is ignored).
+extern "C" size_t r4r_deepconn_ws_state_offset(int64_t B, int T, int E, int L, int64_t V, int tower, int buffer, int which) {
+    char base[1];
+    const StepWs w = carve(base, B, T, E, L, V);
+    const int t = tower & 1, bf = buffer & 1;
+    const void *at[4] = {w.flags[bf][t], w.slot[bf][t], w.list[bf][t], w.argmax[t]};
+    return (which < 0 || which > 3) ? 0 : (size_t)(static_cast<const char *>(at[which]) - base);
+}
+
 // Whether a step of this shape may deal its gather by a segment plan: the switch (r4r_gather_plan), whole segment pairs
 // per document, and few enough segments for the one-workgroup scan.
 static bool plan_applies(int64_t B, int T) {
     const int tiles = proj_tiles(T);
     return proj_gather_plan() && (tiles & 1) == 0 && B * tiles <= PLAN_MAX_UNITS;
 }
+
+// Which tail a training step of this shape takes (r4r_deepconn_tail): 1 = the four-launch step (every sum and Adam
+// step inside the backward launch), 0 = backward + reduce.  A pure function of the shape and the switch: the conv
+// gradient's row role must fit one workgroup (nsplit * E/4 <= 1024 threads, one resolve round per split: B <= 256), and
+// the head instantiation for latent_size 65 .. 128 -- 115 KB of LDS, one workgroup per CU -- keeps the old tail: the
+// marks role in its launch would queue behind the ratings instead of filling idle CUs.
+static int g_tail_fold = -1;           // -1: from the environment at first use (R4R_TAIL=old pins the five-launch step; A/B runs)
+static int tail_fold_switch() {
+    if (g_tail_fold < 0) {
+        const char *e = getenv("R4R_TAIL");
+        g_tail_fold = (e && e[0] == 'o') ? 0 : 1;
+    }
+    return g_tail_fold;
+}
+static bool tail_folds(int64_t B, int E, int L) {
+    if (!tail_fold_switch() || B < 1 || E <= 0 || E % 4 != 0 || L > 64) return false;
+    const int ns = textcnn_wgrad_splits(B);
+    return wgrad_row_applies(B, E, ns, (int)cdiv(B, ns));
+}
+extern "C" int r4r_deepconn_tail_fold(int on) {
+    const int before = tail_fold_switch();
+    g_tail_fold = on ? 1 : 0;
+    return before;
+}
+extern "C" int r4r_deepconn_tail(int64_t B, int E, int L) { return tail_folds(B, E, L) ? 1 : 0; }
 
 // Token compaction of a batch into token-state buffer `token_buffer` (project-then-gather only;
 // a no-op for configurations that run the direct conv).  Depends only on the indices: run it for
@@ -731,7 +866,29 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
     }
     h.plan = plan;
     for (int t = 0; t < 2; ++t) h.plan_spent[t] = algo == R4R_CONV_PROJECT ? w.plan_ready[token_buffer][t] : nullptr;
-    const unsigned head_wgs = (unsigned)B + (unsigned)cdiv(2 * (int64_t)plan.units, 4);
+    // the tail of a training step (four launches where the shape allows, tail_folds): then the next batch's marks ride
+    // HERE, about one index per thread and tower, and its compaction on the backward launch
+    const bool fold = flat_g && tail_folds(B, E, L);
+    const bool prefetch = next_user_idx && algo == R4R_CONV_PROJECT;
+    TokenArgs nx{};
+    if (prefetch) {
+        // token state of the next batch (same B, T) into the OTHER token buffer, if asked for and
+        // if that batch will run project-then-gather
+        ProjTower nt[2];
+        const int64_t *nidx[2] = {next_user_idx, next_item_idx};
+        const int ob = token_buffer ^ 1;
+        for (int t = 0; t < 2; ++t) {
+            nt[t] = ProjTower{};
+            nt[t].idx = nidx[t];
+            nt[t].flags = w.flags[ob][t]; nt[t].slot = w.slot[ob][t];
+            nt[t].list = w.list[ob][t]; nt[t].count = w.count[ob][t];
+        }
+        nx = make_token_args(V, nt, 2, B, T);
+    }
+    h.marks = nx;
+    const int64_t mark_want = cdiv(B * (int64_t)T, 256);
+    h.mark_wgs = (fold && prefetch) ? (int)(mark_want < 1024 ? mark_want : 1024) : 0;
+    const unsigned head_wgs = (unsigned)B + (unsigned)cdiv(2 * (int64_t)plan.units, 4) + (unsigned)h.mark_wgs;
     if (L <= 16) deepconn_head_wg_kernel<16><<<head_wgs, 256, 0, st>>>(h);
     else if (L <= 32) deepconn_head_wg_kernel<32><<<head_wgs, 256, 0, st>>>(h);
     else if (L <= 64) deepconn_head_wg_kernel<64><<<head_wgs, 256, 0, st>>>(h);     // (hyper_params.py:63 has no bound)
@@ -767,21 +924,26 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
     wa.table_bytes = (int64_t)V * E * 4;                   // (the wide wgrad reads the rows through a buffer resource)
     wa.nsplit = textcnn_wgrad_splits(B);
     wa.per_split = (int)cdiv(B, wa.nsplit);
-    // token state of the next batch (same B, T) into the OTHER token buffer, if asked for and
-    // if that batch will run project-then-gather
-    const bool prefetch = next_user_idx && algo == R4R_CONV_PROJECT;
-    TokenArgs nx{};
-    if (prefetch) {
-        ProjTower nt[2];
-        const int64_t *nidx[2] = {next_user_idx, next_item_idx};
-        const int ob = token_buffer ^ 1;
-        for (int t = 0; t < 2; ++t) {
-            nt[t] = ProjTower{};
-            nt[t].idx = nidx[t];
-            nt[t].flags = w.flags[ob][t]; nt[t].slot = w.slot[ob][t];
-            nt[t].list = w.list[ob][t]; nt[t].count = w.count[ob][t];
+    const int comp_blocks = prefetch ? (int)cdiv((V + 3) / 4, RED_THREADS * compact_groups(V)) : 0;
+    if (fold) {
+        // 4 launches: every sum and every Adam step inside the backward launch (deepconn_backward_fold_kernel)
+        FlatAdam fo{};
+        if (flat_m) {
+            fo.on = 1;
+            fo.p = flat_p; fo.m = flat_m; fo.v = flat_v; fo.g = flat_g;
+            fo.s = adam_make_scalars(lr, beta1, beta2, eps, weight_decay, adam_step, nullptr);
         }
-        nx = make_token_args(V, nt, 2, B, T);
+        const int side = prefetch ? (planning ? 2 : 0) + 2 * comp_blocks : 0;      // workgroups of the slices z >= 3
+        const unsigned nz = 3 + (unsigned)cdiv(side, F_CONV * 3);
+        {
+            ScopedTiming tm(R4R_TIMING_TEXTCNN_WGRAD, st);
+            const DcFoldArgs fa{wa, fo, hg, hg_blocks, nx, plan, comp_blocks};
+            const dim3 grid(F_CONV, 3, nz);
+            const int nthr = wgrad_row_threads(E, wa.nsplit);
+            if (V > COMPACT_BIG_V) deepconn_backward_fold_kernel<true><<<grid, nthr, 0, st>>>(fa);   // (as token_compact_auto picks)
+            else deepconn_backward_fold_kernel<false><<<grid, nthr, 0, st>>>(fa);
+        }
+        return check_launch("deepconn_step");
     }
     {
         ScopedTiming tm(R4R_TIMING_TEXTCNN_WGRAD, st);
@@ -789,7 +951,6 @@ extern "C" int r4r_deepconn_step(const float *table, int64_t V, const int64_t *u
     }
     // 6: wgrad partial reduce -> flat gradient buffer (+ compaction of the next batch's tokens)
     const int red_blocks = (F_CONV * 3 * E + F_CONV + RED_THREADS - 1) / RED_THREADS;
-    const int comp_blocks = prefetch ? (int)cdiv((V + 3) / 4, RED_THREADS * compact_groups(V)) : 0;
     FusedAdam opt{};
     int opt_blocks = 0;
     if (flat_m) {

@@ -1,6 +1,7 @@
 // Argmax-sparse conv weight gradient: per-workgroup body, shared by the stand-alone kernel
 // (textcnn.hip) and the fused DeepCoNN backward launch (engine.hip).
 #pragma once
+#include "adam_device.h"
 #include "textcnn.h"
 
 namespace r4r {
@@ -257,6 +258,126 @@ __device__ __forceinline__ float wgrad_reduce_elem(const WgradArgs &a, int tower
 __device__ __forceinline__ void wgrad_reduce_block(const WgradArgs &a, int tower, int blk) {
     float *dst;
     (void)wgrad_reduce_elem(a, tower, blk * (int)blockDim.x + (int)threadIdx.x, dst);
+}
+
+// ---- Both stages in ONE workgroup: the workgroup is a (filter, tap) -- one E-wide row of the gradient -- and holds
+// EVERY split of it.  Thread (s, c) = (tid / (E/4), tid % (E/4)) forms float4 column c of split s's partial exactly as
+// wgrad_block_pass does (the same expression over the same documents in the same order: buffer-resource loads,
+// WG_FLIGHT rows in flight, selects instead of branches); the partials meet in LDS instead of part_w, and after one
+// barrier thread i adds element i's partials in split order from 0.f as wgrad_reduce_elem does, writes the gradient and --
+// with `opt.on` -- takes the element's Adam step (parameter and moments were requested at the top: their addresses
+// depend on nothing).  The tap-0 workgroup of a filter forms the bias gradient the same way: per-split sequential sums
+// of the pooled gradients, then their sum in split order.  No partial reaches memory and no second launch reads one;
+// no workgroup waits for another.  The same bits as wgrad_block + wgrad_reduce_elem + adam_elem.
+// Needs: blockDim.x >= max(N, nsplit * E/4), N <= WG_ROW_MAX_DOCS, per_split <= WG_CHUNK (wgrad_row_applies).
+constexpr int WG_ROW_MAX_THREADS = 1024;
+constexpr int WG_ROW_MAX_DOCS = WG_MAX_SPLITS * WG_CHUNK;
+constexpr unsigned WG_ROW_NONE = 0xffffffffu;               // (no row starts there: a row's byte offset is a multiple of 16)
+inline bool wgrad_row_applies(int64_t N, int E, int nsplit, int per_split) {
+    return N >= 1 && N <= WG_ROW_MAX_DOCS && per_split <= WG_CHUNK && nsplit <= WG_MAX_SPLITS && E % 4 == 0 &&
+           (int64_t)nsplit * (E / 4) <= WG_ROW_MAX_THREADS;
+}
+inline int wgrad_row_threads(int E, int nsplit) {           // whole waves, and at least the other roles' 256
+    const int t = (nsplit * (E / 4) + 63) & ~63;
+    return t < WG_THREADS ? WG_THREADS : t;
+}
+__device__ __forceinline__ void wgrad_row_block(const WgradArgs &a, const FlatAdam &opt, int f, int tap, int tower) {
+    __shared__ long r_off[WG_ROW_MAX_DOCS];                 // table row offset in floats of (document, this tap), -1 = no contribution
+    __shared__ unsigned r_bo[WG_ROW_MAX_DOCS];              // the same as a buffer byte offset; WG_ROW_NONE = no contribution
+    __shared__ float r_g[WG_ROW_MAX_DOCS];
+    __shared__ __attribute__((aligned(16))) float r_part[4 * WG_ROW_MAX_THREADS];     // [nsplit][E]
+    __shared__ float r_sb[WG_MAX_SPLITS];
+    const WgradTower &tw = a.t[tower];
+    const float *__restrict__ table = a.table;
+    const int T = a.T, E = a.E, F = a.F, e4 = E / 4, nsplit = a.nsplit;
+    const int N = (int)a.N;
+    const int tid = threadIdx.x;
+    const int s = tid / e4, c = tid - s * e4, ve = 4 * c;
+    const bool worker = s < nsplit;
+    // Finishing: element i of the row's [E weights | the filter's bias (tap 0 only)] belongs to thread i (the few past the
+    // block size, where a shape has them, to the same threads again).  Its parameter and moments are in flight under
+    // everything else.
+    const int tot = E + (tap == 0 ? 1 : 0);
+    float *const row_w = tw.d_w + ((size_t)f * 3 + tap) * E;
+    float *const dst0 = tid < E ? row_w + tid : tw.d_b + f;
+    float P = 0.f, M = 0.f, V = 0.f;
+    if (opt.on && tid < tot) {
+        const int o = (int)(dst0 - opt.g);
+        P = opt.p[o]; M = opt.m[o]; V = opt.v[o];
+    }
+    // phase 1: the chain argmax -> position -> token id -> row offset of EVERY document for this tap, one lane each
+    if (tid < N) {
+        const int p = tw.argmax[(int64_t)tid * F + f];
+        const float gv = tw.g_pooled[(int64_t)tid * F + f];
+        const int t = p - 2 + tap;
+        long off = -1;
+        if (p >= 0 && t >= 0 && t < T) off = (long)tw.idx[(int64_t)tid * T + t] * E;
+        r_off[tid] = off;
+        r_bo[tid] = off >= 0 ? (unsigned)(off * 4) : WG_ROW_NONE;
+        r_g[tid] = (p >= 0) ? gv : 0.f;
+    }
+    __syncthreads();
+    // phase 2: split s's documents, as one round of wgrad_block_pass
+    const int n0 = worker ? s * a.per_split : 0;            // (n0 + 15 < WG_ROW_MAX_DOCS: nsplit <= 16 splits of <= 16)
+    const int nd = worker ? max(0, min(N, n0 + a.per_split) - n0) : 0;
+    wg_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const bool buf_ok = a.table_bytes > 0 && a.table_bytes < (1ll << 32);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(table), 0, buf_ok ? (int)(unsigned)a.table_bytes : 0, 0x00020000);
+    if (worker && nd > 0) {
+        if (buf_ok) {
+#pragma unroll
+            for (int d0 = 0; d0 < WG_CHUNK; d0 += WG_FLIGHT) {
+                wg_f32x4 row[WG_FLIGHT];
+                bool on[WG_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < WG_FLIGHT; ++u) {
+                    const int d = d0 + u;
+                    const unsigned rv = r_bo[n0 + d];       // (unconditional: nd differs between the threads of a wave here)
+                    const unsigned ro = d < nd ? rv : WG_ROW_NONE;
+                    on[u] = ro != WG_ROW_NONE;
+                    const unsigned bo = on[u] ? ro + (unsigned)(ve * 4) : 0xfffffff0u;      // = (unsigned)((off + ve) * 4)
+                    row[u] = __builtin_bit_cast(wg_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)bo, 0, 0));
+                }
+#pragma unroll
+                for (int u = 0; u < WG_FLIGHT; ++u) {  // document order, the same additions as wgrad_block_pass
+                    const wg_f32x4 sum = acc + r_g[n0 + d0 + u] * row[u];
+                    acc = on[u] ? sum : acc;
+                }
+                // (one flight at a time: hipcc started the next flight under this one's additions, sixteen rows of
+                // registers, and spilled two of them at the launch's 64)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+#pragma unroll 4
+            for (int d = 0; d < nd; ++d) {
+                const long off = r_off[n0 + d];
+                if (off >= 0) acc += r_g[n0 + d] * *reinterpret_cast<const wg_f32x4 *>(table + off + ve);
+            }
+        }
+    }
+    r_part[4 * tid] = acc.x; r_part[4 * tid + 1] = acc.y; r_part[4 * tid + 2] = acc.z; r_part[4 * tid + 3] = acc.w;
+    if (tap == 0 && tid < nsplit) {                         // thread k: split k's bias partial, in document order
+        const int b0 = tid * a.per_split, bn = max(0, min(N, b0 + a.per_split) - b0);
+        float sb = 0.f;
+        for (int d = 0; d < bn; ++d) sb += r_g[b0 + d];
+        r_sb[tid] = sb;
+    }
+    __syncthreads();
+    for (int i = tid; i < tot; i += (int)blockDim.x) {
+        float *const dst = i < E ? row_w + i : tw.d_b + f;
+        const int o = opt.on ? (int)(dst - opt.g) : 0;
+        if (opt.on && i != tid) { P = opt.p[o]; M = opt.m[o]; V = opt.v[o]; }
+        const float *src = i < E ? r_part + i : r_sb;       // split k's partial of this element
+        const int stride = i < E ? E : 1;
+        float g = 0.f;
+#pragma unroll 4
+        for (int k = 0; k < nsplit; ++k) g += src[k * stride];     // split order from 0.f, as wgrad_reduce_elem
+        *dst = g;
+        if (opt.on) {
+            adam_elem(P, g, M, V, opt.s);
+            opt.p[o] = P; opt.m[o] = M; opt.v[o] = V;
+        }
+    }
 }
 
 }  // namespace r4r
