@@ -19,6 +19,10 @@
 // on its own (u, i) only, so the result does not depend on the chunking, the tile or the other queries of the call.
 //
 // r4r_rank_dot, at the end of the file: the same stream with counters in place of lists -- the rank of explicit targets.
+//
+// This file has the two streams, the merge and the head of this form (DotHead: the scalar form of the chain); what sits
+// around the streams, the scalar kernels over a head and the host checks and plans are topk_device.h's, shared with
+// topk_relu.hip and topk_hmlp.hip.
 #include <math.h>
 
 #include "common.h"
@@ -36,21 +40,41 @@ constexpr int64_t TOPK_WIDE_TILE_MIN_Q = 512;   // below this 16-query tiles alo
 // A fragments of four no longer fit the registers
 inline int topk_nq(int64_t n_q, int D) { return (n_q >= TOPK_WIDE_TILE_MIN_Q && D <= 128) ? 4 : 1; }
 
-// the chunk the call runs with: the caller's, or one that gives every CU its waves
-inline int64_t topk_resolve_chunk(int64_t n_q, int64_t n_c, int64_t chunk) {
-    if (chunk > 0) return chunk;
-    // Not a function of D (r4r_topk_dot_ws_bytes has none): the tiles are counted as topk_nq counts them for D <= 128.  From
-    // 512 queries on with D > 128 the scan runs 16-query tiles over chunks sized for 64-query ones: four times the
-    // intended waves, the same result.
-    const int64_t tiles = cdiv(n_q, 16 * topk_nq(n_q, 0));
-    int64_t parts = cdiv(TOPK_TARGET_WAVES, tiles > 0 ? tiles : 1);
-    const int64_t most = cdiv(n_c, TOPK_MIN_CHUNK);
-    if (parts > most) parts = most;
-    if (parts < 1) parts = 1;
-    return cdiv(cdiv(n_c, parts), 64) * 64;
-}
+// The tile width the chunk rule (topk_device.h's resolve_chunk) counts with.  Not a function of D (r4r_topk_dot_ws_bytes has
+// none): the tiles are counted as topk_nq counts them for D <= 128.  From 512 queries on with D > 128 the scan runs
+// 16-query tiles over chunks sized for 64-query ones: four times the intended waves, the same result.
+inline int topk_chunk_tile(int64_t n_q) { return 16 * topk_nq(n_q, 0); }
 
-// (the order `ahead`, `list_insert` and the limits shared with topk_relu.hip: topk_device.h)
+// The head of this form: the scalar form of the chain the matrix pipe computes
+struct DotHead {
+    const float *q, *q_bias, *c, *c_bias;
+    int64_t n_c, c_stride;
+    int D;
+
+    __device__ __forceinline__ float q_bias_of(int64_t u) const { return q_bias ? q_bias[u] : 0.f; }
+    __device__ __forceinline__ float score(int64_t u, int64_t i, float qb) const {
+        float dot = 0.f;
+        for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
+        return (dot + (c_bias ? c_bias[i] : 0.f)) + qb;
+    }
+    __device__ __forceinline__ float score(int64_t u, int64_t i) const { return score(u, i, q_bias_of(u)); }
+
+    static constexpr const char *width_name = "D";
+    int width() const { return D; }
+    int ranges(const char *fn) const {
+        R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "%s: D = %d outside 0 .. %d", fn, D, TOPK_MAX_D);
+        return R4R_OK;
+    }
+    int weights(const char *) const { return R4R_OK; }
+};
+
+inline DotHead dot_head(const float *q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                        const float *c_bias, int D) {
+    DotHead h;
+    h.q = q; h.q_bias = q_bias; h.c = c; h.c_bias = c_bias;
+    h.n_c = n_c; h.c_stride = c_stride; h.D = D;
+    return h;
+}
 
 struct ScanArgs {
     const float *q, *q_bias, *c, *c_bias;
@@ -72,10 +96,8 @@ __global__ __launch_bounds__(64) void topk_scan_kernel(ScanArgs a) {
 
     const int lane = threadIdx.x;
     const int row = lane & 15, kq = lane >> 4;
-    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
-    const int64_t u0 = tile * QT;
-    const int64_t c_begin = part * a.chunk;
-    const int64_t c_end = (c_begin + a.chunk < a.n_c) ? c_begin + a.chunk : a.n_c;
+    const ChunkGeom g = chunk_geom(a.tiles, QT, a.chunk, a.n_c);
+    const int64_t u0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
 
     for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
 
@@ -178,15 +200,7 @@ __global__ __launch_bounds__(64) void topk_scan_kernel(ScanArgs a) {
                         const int ql = 16 * s + 4 * (src >> 4) + r;
                         const int64_t ci = base + 16 * l + (src & 15);
                         if (!(v > lane_value(thr[s][r], src))) continue;         // (an earlier survivor raised the bar)
-                        if (a.excl_off != nullptr) {
-                            int64_t lo = a.excl_off[u0 + ql], hi = a.excl_off[u0 + ql + 1];
-                            const int64_t end = hi;
-                            while (lo < hi) {
-                                const int64_t mid = lo + ((hi - lo) >> 1);
-                                if (a.excl_ids[mid] < ci) lo = mid + 1; else hi = mid;
-                            }
-                            if (lo < end && a.excl_ids[lo] == ci) continue;
-                        }
+                        if (is_excluded(a.excl_off, a.excl_ids, u0 + ql, ci)) continue;
                         const float bar = list_insert<int>(sc + ql * K, id + ql * K, K, v, (int)(ci - c_begin), lane);
                         if (kq == (src >> 4)) thr[s][r] = bar;                   // the lanes that hold this query
                     }
@@ -199,7 +213,7 @@ __global__ __launch_bounds__(64) void topk_scan_kernel(ScanArgs a) {
     for (int ql = 0; ql < QT; ++ql) {
         const int64_t u = u0 + ql;
         if (u >= a.n_q) break;
-        const int64_t o = (u * a.parts + part) * K;
+        const int64_t o = (u * a.parts + g.part) * K;
         for (int p = lane; p < K; p += 64) {
             const int ci = id[ql * K + p];
             a.out_scores[o + p] = sc[ql * K + p];                                 // (-inf in an unused slot)
@@ -302,95 +316,54 @@ int topk_launch_merge(const float *ps, const int64_t *pi, int64_t n_q, int64_t p
 using namespace r4r;
 
 extern "C" size_t r4r_topk_dot_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk) {
-    if (n_q <= 0 || n_c <= 0 || K < 1 || K > TOPK_MAX_K || chunk < 0) return 0;
-    const int64_t parts = cdiv(n_c, topk_resolve_chunk(n_q, n_c, chunk));
-    if (parts <= 1) return 0;
-    return (size_t)n_q * (size_t)parts * (size_t)K * (sizeof(float) + sizeof(int64_t));
+    return lists_ws_bytes(n_q, n_c, K, chunk, topk_chunk_tile(n_q));
 }
 
 extern "C" int r4r_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                             const float *c_bias, int D, const int64_t *excl_off, const int64_t *excl_ids, int K,
                             int64_t chunk, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream) {
-    R4R_REQUIRE(K >= 1 && K <= TOPK_MAX_K, "topk_dot: K = %d outside 1 .. %d", K, TOPK_MAX_K);
-    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "topk_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
-    R4R_REQUIRE(n_q >= 0 && n_c >= 0, "topk_dot: negative n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "topk_dot: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "topk_dot: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(n_q == 0 || (out_ids != nullptr && out_scores != nullptr), "topk_dot: null output");
-    R4R_REQUIRE(n_q < ((int64_t)1 << 31), "topk_dot: n_q = %lld too large", (long long)n_q);
-    R4R_REQUIRE(c_stride >= D, "topk_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
-    if (n_q == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(D == 0 || (q != nullptr && c != nullptr), "topk_dot: null q or c with D > 0");
+    const DotHead h = dot_head(q, q_bias, c, n_c, c_stride, c_bias, D);
+    bool work;
+    int rc = topk_check("topk_dot", h, n_q, excl_off, excl_ids, K, chunk, out_ids, out_scores, &work);
+    if (rc != R4R_OK || !work) return rc;
     const int NQ = topk_nq(n_q, D);
+    ListsPlan p;
+    rc = topk_plan("topk_dot", n_q, n_c, K, chunk, topk_chunk_tile(n_q), 16 * NQ, ws, ws_bytes, out_ids, out_scores, &p);
+    if (rc != R4R_OK) return rc;
     ScanArgs a;
     a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias;
     a.excl_off = excl_off; a.excl_ids = excl_ids;
-    a.n_q = n_q; a.n_c = n_c; a.c_stride = c_stride; a.D = D; a.K = K;
-    a.chunk = topk_resolve_chunk(n_q, n_c, chunk);
-    a.parts = cdiv(n_c, a.chunk);
-    a.tiles = cdiv(n_q, 16 * NQ);
-    R4R_REQUIRE(a.parts * a.tiles < ((int64_t)1 << 31), "topk_dot: %lld chunks x %lld query tiles exceed the grid",
-                (long long)a.parts, (long long)a.tiles);
-    const size_t need = r4r_topk_dot_ws_bytes(n_q, n_c, K, chunk);
-    if (need > 0 && (ws == nullptr || ws_bytes < need)) {
-        set_error("topk_dot: workspace %zu < %zu bytes", ws_bytes, need);
-        return R4R_ERR_WORKSPACE;
-    }
+    a.out_scores = p.scan_scores; a.out_ids = p.scan_ids;
+    a.n_q = n_q; a.n_c = n_c; a.c_stride = c_stride; a.chunk = p.chunk; a.parts = p.parts; a.tiles = p.tiles;
+    a.D = D; a.K = K;
     hipStream_t st = as_stream(stream);
-    if (a.parts == 1) {
-        a.out_scores = out_scores;
-        a.out_ids = out_ids;
-    } else {
-        a.out_ids = reinterpret_cast<int64_t *>(ws);
-        a.out_scores = reinterpret_cast<float *>(a.out_ids + (size_t)n_q * a.parts * K);
-    }
-    const int rc = NQ == 4 ? launch_scan_d<4>(a, st) : launch_scan_d<1>(a, st);
-    if (rc != R4R_OK || a.parts == 1) return rc;
-    return topk_launch_merge(a.out_scores, a.out_ids, n_q, a.parts, K, out_ids, out_scores, st);
+    rc = NQ == 4 ? launch_scan_d<4>(a, st) : launch_scan_d<1>(a, st);
+    return topk_finish(p, rc, n_q, K, out_ids, out_scores, st);
 }
-
-// score(u, i) of explicit pairs: the scalar form of the chain the matrix pipe computes
-namespace r4r {
-namespace {
-__global__ void pair_dot_kernel(const float *__restrict__ q, const float *__restrict__ q_bias, const float *__restrict__ c,
-                                int64_t c_stride, const float *__restrict__ c_bias, int D, const int64_t *__restrict__ qi,
-                                const int64_t *__restrict__ ci, int64_t n, float *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ci[p];
-    float dot = 0.f;
-    for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
-    out[p] = (dot + (c_bias ? c_bias[i] : 0.f)) + (q_bias ? q_bias[u] : 0.f);
-}
-}  // namespace
-}  // namespace r4r
 
 extern "C" int r4r_pair_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                             const float *c_bias, int D, const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out,
                             void *stream) {
-    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "pair_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
-    R4R_REQUIRE(n >= 0 && n_q >= 0 && n_c >= 0, "pair_dot: negative size");
-    if (n == 0) return R4R_OK;
-    R4R_REQUIRE(n_q > 0 && n_c > 0, "pair_dot: pairs into an empty table");
-    R4R_REQUIRE(c_stride >= D, "pair_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
-    R4R_REQUIRE(q_idx != nullptr && c_idx != nullptr && out != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
-                "pair_dot: null pointer");
-    hipLaunchKernelGGL(pair_dot_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), q, q_bias, c, c_stride,
-                       c_bias, D, q_idx, c_idx, n, out);
-    return check_launch("pair_dot_kernel");
+    const DotHead h = dot_head(q, q_bias, c, n_c, c_stride, c_bias, D);
+    bool work;
+    const int rc = pair_check("pair_dot", h, n_q, q_idx, c_idx, n, out, &work);
+    if (rc != R4R_OK || !work) return rc;
+    return launch_pairs(h, q_idx, c_idx, n, out, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // r4r_rank_dot: the rank of explicit targets.  Pair p = (query row q_idx[p], target t_idx[p]); its rank is the number of
 // candidates ahead of the target in the order above -- a count, so the scan's lists, survivors and merge fall away.
-//   A  rank_target_kernel   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for a target
-//                           whose own score is -inf or NaN (never touched again)
-//   B  rank_scan_kernel     the scan's stream over a tile of 16 * NQ PAIRS (A fragments gathered through q_idx) and a
-//                           chunk of candidates; the epilogue compares every sum with the pair's target in registers
-//                           and counts; one 64-bit integer atomic per (pair, chunk)
-//   C  rank_excl_kernel     only with exclusions: B counted the excluded ids too; one wave per pair recomputes the
-//                           scalar chain of its query row's excluded ids and subtracts those that were ahead.  Exact,
-//                           because a score's bits depend on its own pair only (MFMA chain == scalar chain).
+//   A  rank_target_kernel<DotHead>   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for
+//                                    a target whose own score is -inf or NaN (never touched again)
+//   B  rank_scan_kernel              the scan's stream over a tile of 16 * NQ PAIRS (A fragments gathered through q_idx)
+//                                    and a chunk of candidates; the epilogue compares every sum with the pair's target
+//                                    in registers and counts; one 64-bit integer atomic per (pair, chunk)
+//   C  rank_excl_kernel<DotHead>     only with exclusions: B counted the excluded ids too; one wave per pair recomputes
+//                                    the scalar chain of its query row's excluded ids and subtracts those that were
+//                                    ahead.  Exact, because a score's bits depend on its own pair only (MFMA chain ==
+//                                    scalar chain).
+// (A and C: topk_device.h.)
 // Integer atomics only: the result depends on no order, no chunking, no tiling and no grouping of the pairs.
 namespace r4r {
 namespace {
@@ -408,20 +381,6 @@ struct RankArgs {
     int D;
 };
 
-__global__ void rank_target_kernel(const float *__restrict__ q, const float *__restrict__ q_bias, const float *__restrict__ c,
-                                   int64_t c_stride, const float *__restrict__ c_bias, int D, const int64_t *__restrict__ qi,
-                                   const int64_t *__restrict__ ti, int64_t n, float *__restrict__ out_score,
-                                   int64_t *__restrict__ out_rank) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ti[p];
-    float dot = 0.f;
-    for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
-    const float s = (dot + (c_bias ? c_bias[i] : 0.f)) + (q_bias ? q_bias[u] : 0.f);
-    out_score[p] = s;
-    out_rank[p] = s > -INFINITY ? 0 : -1;                      // (false for NaN)
-}
-
 // KT, NQ, SL as in topk_scan_kernel; the streaming loop is that kernel's, kept apart from it on purpose
 template <int KT, int NQ, int SL>
 __global__ __launch_bounds__(64) void rank_scan_kernel(RankArgs a) {
@@ -429,6 +388,7 @@ __global__ __launch_bounds__(64) void rank_scan_kernel(RankArgs a) {
     const int D = a.D;
     const int lane = threadIdx.x;
     const int row = lane & 15, kq = lane >> 4;
+    // (chunk_geom, written out: through the helper this kernel's registers are allocated differently from end to end)
     const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
     const int64_t p0 = tile * PT;
     const int64_t c_begin = part * a.chunk;
@@ -556,39 +516,6 @@ __global__ __launch_bounds__(64) void rank_scan_kernel(RankArgs a) {
     }
 }
 
-// One wave per pair over the exclusion list of its query row
-__global__ __launch_bounds__(256) void rank_excl_kernel(const float *__restrict__ q, const float *__restrict__ q_bias,
-                                                        const float *__restrict__ c, int64_t n_c, int64_t c_stride,
-                                                        const float *__restrict__ c_bias, int D,
-                                                        const int64_t *__restrict__ qi, const int64_t *__restrict__ ti,
-                                                        int64_t n_p, const int64_t *__restrict__ excl_off,
-                                                        const int64_t *__restrict__ excl_ids,
-                                                        const float *__restrict__ t_score, int64_t *out_rank) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (p >= n_p) return;
-    const float st = t_score[p];
-    if (!(st > -INFINITY)) return;                            // a pair at -1 keeps its -1
-    const int64_t u = qi[p], t = ti[p];
-    const int64_t lo = excl_off[u], hi = excl_off[u + 1];
-    const float qb = q_bias ? q_bias[u] : 0.f;
-    int n = 0;
-    for (int64_t e0 = lo; e0 < hi; e0 += 64) {
-        const int64_t e = e0 + lane;
-        if (e >= hi) continue;
-        const int64_t i = excl_ids[e];
-        if (i < 0 || i >= n_c || i == t) continue;
-        float dot = 0.f;
-        for (int j = 0; j < D; ++j) dot = __builtin_fmaf(q[u * D + j], c[i * c_stride + j], dot);
-        const float s = (dot + (c_bias ? c_bias[i] : 0.f)) + qb;
-        n += ahead<int64_t>(s, i, st, t) ? 1 : 0;
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
-    if (lane == 0 && n > 0)
-        atomicAdd(reinterpret_cast<unsigned long long *>(out_rank + p), (unsigned long long)(-(int64_t)n));
-}
-
 inline int rank_nq(int64_t n_p, int D) { return (n_p >= RANK_WIDE_TILE_MIN_P && D <= 128) ? 4 : 1; }
 
 template <int KT, int NQ, int SL>
@@ -617,34 +544,21 @@ extern "C" int r4r_rank_dot(const float *q, int64_t n_q, const float *q_bias, co
                             const float *c_bias, int D, const int64_t *q_idx, const int64_t *t_idx, int64_t n_p,
                             const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank,
                             float *out_score, void *stream) {
-    R4R_REQUIRE(D >= 0 && D <= TOPK_MAX_D, "rank_dot: D = %d outside 0 .. %d", D, TOPK_MAX_D);
-    R4R_REQUIRE(n_p >= 0 && n_q >= 0 && n_c >= 0, "rank_dot: negative n_p, n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "rank_dot: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "rank_dot: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(c_stride >= D, "rank_dot: c_stride = %lld below D = %d", (long long)c_stride, D);
-    R4R_REQUIRE(n_p == 0 || (out_rank != nullptr && out_score != nullptr), "rank_dot: null output");
-    if (n_p == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(n_q > 0, "rank_dot: pairs into an empty query table");
-    R4R_REQUIRE(q_idx != nullptr && t_idx != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
-                "rank_dot: null pointer (q_idx, t_idx, or q / c with D > 0)");
+    const DotHead h = dot_head(q, q_bias, c, n_c, c_stride, c_bias, D);
+    bool work;
+    int rc = rank_check("rank_dot", h, n_q, q_idx, t_idx, n_p, excl_off, excl_ids, chunk, out_rank, out_score, &work);
+    if (rc != R4R_OK || !work) return rc;
     const int NQ = rank_nq(n_p, D);
+    ChunkPlan p;
+    rc = rank_plan("rank_dot", n_p, n_c, chunk, topk_chunk_tile(n_p), 16 * NQ, &p);
+    if (rc != R4R_OK) return rc;
     RankArgs a;
     a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias; a.q_idx = q_idx; a.t_idx = t_idx;
     a.t_score = out_score; a.out_rank = out_rank;
-    a.n_p = n_p; a.n_c = n_c; a.c_stride = c_stride; a.D = D;
-    a.chunk = topk_resolve_chunk(n_p, n_c, chunk);
-    a.tiles = cdiv(n_p, 16 * NQ);
-    const int64_t parts = cdiv(n_c, a.chunk);
-    R4R_REQUIRE(parts * a.tiles < ((int64_t)1 << 31) && cdiv(n_p, 4) < ((int64_t)1 << 31),
-                "rank_dot: %lld chunks x %lld pair tiles exceed the grid", (long long)parts, (long long)a.tiles);
+    a.n_p = n_p; a.n_c = n_c; a.c_stride = c_stride; a.chunk = p.chunk; a.tiles = p.tiles; a.D = D;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(rank_target_kernel, dim3((unsigned)cdiv(n_p, 256)), dim3(256), 0, st, q, q_bias, c, c_stride, c_bias, D,
-                       q_idx, t_idx, n_p, out_score, out_rank);
-    int rc = check_launch("rank_target_kernel");
+    rc = launch_rank_targets(h, q_idx, t_idx, n_p, out_score, out_rank, st);
     if (rc != R4R_OK) return rc;
-    rc = NQ == 4 ? launch_rank_d<4>(a, parts, st) : launch_rank_d<1>(a, parts, st);
-    if (rc != R4R_OK || excl_off == nullptr) return rc;
-    hipLaunchKernelGGL(rank_excl_kernel, dim3((unsigned)cdiv(n_p, 4)), dim3(256), 0, st, q, q_bias, c, n_c, c_stride, c_bias, D,
-                       q_idx, t_idx, n_p, excl_off, excl_ids, (const float *)out_score, out_rank);
-    return check_launch("rank_excl_kernel");
+    rc = NQ == 4 ? launch_rank_d<4>(a, p.parts, st) : launch_rank_d<1>(a, p.parts, st);
+    return rank_finish(h, rc, q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
 }

@@ -19,9 +19,11 @@
 // Scores are never written: each is compared with its query's K-th best, survivors go through topk_device.h's
 // list_insert, the partial lists have r4r_topk_dot's workspace layout and topk.hip's merge kernel finishes (skipped for a
 // single chunk).  r4r_rank_hmlp: the same stream over a tile of PAIRS with counters in place of lists.
-// The scalar kernels (pairs, rank targets, the exclusion correction) compute hmlp_pair_score: the chain above written
-// out.  v_mfma_f32_16x16x4_f32 is bitwise that chain over m (topk.hip), zero rows of W give z = 0 and w = 0 adds
-// nothing, so a score's bits depend on its own pair only.
+// topk_device.h's scalar kernels (pairs, rank targets, the exclusion correction) over this file's HmlpHead compute
+// hmlp_pair_score: the chain above written out.  v_mfma_f32_16x16x4_f32 is bitwise that chain over m (topk.hip), zero
+// rows of W give z = 0 and w = 0 adds nothing, so a score's bits depend on its own pair only.
+// This file has the two streams and the head; the scalar kernels, the chunk rule, the argument checks and the plan of a
+// call are topk_device.h's, shared with topk.hip and topk_relu.hip.
 #include <math.h>
 
 #include "common.h"
@@ -35,18 +37,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int HMLP_MAX_D = 64;
 constexpr int HMLP_MAX_H = 64;
 constexpr int HMLP_QT = 4;         // queries (pairs, for the rank) per wave
-
-// the chunk the call runs with: the caller's, or one that gives every CU its waves (topk_resolve_chunk's rule over
-// this file's query tile)
-inline int64_t hmlp_resolve_chunk(int64_t n_q, int64_t n_c, int64_t chunk) {
-    if (chunk > 0) return chunk;
-    const int64_t tiles = cdiv(n_q, HMLP_QT);
-    int64_t parts = cdiv(TOPK_TARGET_WAVES, tiles > 0 ? tiles : 1);
-    const int64_t most = cdiv(n_c, TOPK_MIN_CHUNK);
-    if (parts > most) parts = most;
-    if (parts < 1) parts = 1;
-    return cdiv(cdiv(n_c, parts), 64) * 64;
-}
 
 // the scalar chain of one pair: q, c point at the pair's rows.  (g is a compile-time index: h stays in registers.)
 __device__ __forceinline__ float hmlp_pair_score(const float *q, const float *c, const float *W, const float *b, const float *w,
@@ -72,10 +62,29 @@ __device__ __forceinline__ float hmlp_pair_score(const float *q, const float *c,
     return (((h[0] + h[1]) + (h[2] + h[3])) + cb) + qb;
 }
 
+// The head of this form (topk_device.h); the two streams read its fields
 struct HmlpHead {
     const float *q, *q_bias, *c, *c_bias, *W, *b, *w;
     int64_t n_c, c_stride;
     int D, H;
+
+    __device__ __forceinline__ float q_bias_of(int64_t u) const { return q_bias ? q_bias[u] : 0.f; }
+    __device__ __forceinline__ float score(int64_t u, int64_t i, float qb) const {
+        return hmlp_pair_score(q + u * D, c + i * c_stride, W, b, w, D, H, c_bias ? c_bias[i] : 0.f, qb);
+    }
+    __device__ __forceinline__ float score(int64_t u, int64_t i) const { return score(u, i, q_bias_of(u)); }
+
+    static constexpr const char *width_name = "D";
+    int width() const { return D; }
+    int ranges(const char *fn) const {
+        R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "%s: D = %d outside 0 .. %d", fn, D, HMLP_MAX_D);
+        R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "%s: H = %d outside 0 .. %d", fn, H, HMLP_MAX_H);
+        return R4R_OK;
+    }
+    int weights(const char *fn) const {
+        R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "%s: null w or W with H > 0", fn);
+        return R4R_OK;
+    }
 };
 
 // What a wave keeps for its whole chunk: the head (A fragments; b and w in the accumulator layout) and the column of
@@ -212,10 +221,8 @@ __global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
     int *id = reinterpret_cast<int *>(sc + QT * K);            // [QT][K]  candidate - chunk begin
 
     const int lane = threadIdx.x;
-    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
-    const int64_t u0 = tile * QT;
-    const int64_t c_begin = part * a.chunk;
-    const int64_t c_end = (c_begin + a.chunk < a.h.n_c) ? c_begin + a.chunk : a.h.n_c;
+    const ChunkGeom g = chunk_geom(a.tiles, QT, a.chunk, a.h.n_c);
+    const int64_t u0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
 
     for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
 
@@ -261,15 +268,7 @@ __global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
                     const float v = lane_value(sv[s], src);
                     const int64_t ci = base + src;             // (src < 16: a lane of kq == 0)
                     if (!(v > thr[s])) continue;               // (an earlier survivor raised the bar)
-                    if (a.excl_off != nullptr) {
-                        int64_t lo = a.excl_off[u0 + s], hi = a.excl_off[u0 + s + 1];
-                        const int64_t end = hi;
-                        while (lo < hi) {
-                            const int64_t mid = lo + ((hi - lo) >> 1);
-                            if (a.excl_ids[mid] < ci) lo = mid + 1; else hi = mid;
-                        }
-                        if (lo < end && a.excl_ids[lo] == ci) continue;
-                    }
+                    if (is_excluded(a.excl_off, a.excl_ids, u0 + s, ci)) continue;
                     thr[s] = list_insert<int>(sc + s * K, id + s * K, K, v, (int)(ci - c_begin), lane);
                 }
             }
@@ -281,7 +280,7 @@ __global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
     for (int ql = 0; ql < QT; ++ql) {
         const int64_t u = u0 + ql;
         if (u >= a.n_q) break;
-        const int64_t o = (u * a.parts + part) * K;
+        const int64_t o = (u * a.parts + g.part) * K;
         for (int p = lane; p < K; p += 64) {
             const int ci = id[ql * K + p];
             a.out_scores[o + p] = sc[ql * K + p];              // (-inf in an unused slot)
@@ -290,24 +289,16 @@ __global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
     }
 }
 
-__global__ void pair_hmlp_kernel(HmlpHead a, const int64_t *__restrict__ qi, const int64_t *__restrict__ ci, int64_t n,
-                                 float *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ci[p];
-    out[p] = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H, a.c_bias ? a.c_bias[i] : 0.f,
-                             a.q_bias ? a.q_bias[u] : 0.f);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // r4r_rank_hmlp: r4r_rank_dot's three launches over this file's chain.
-//   A  rank_hmlp_target_kernel   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for a
-//                                target whose own score is -inf or NaN (never touched again)
-//   B  rank_hmlp_scan_kernel     the scan's stream over a tile of HMLP_QT PAIRS (query rows gathered through q_idx) and a
-//                                chunk of candidates; every score is compared with the pair's target in registers and
-//                                counted; one 64-bit integer atomic per (pair, chunk)
-//   C  rank_hmlp_excl_kernel     only with exclusions: B counted the excluded ids too; one wave per pair recomputes the
-//                                scalar chain of its query row's excluded ids and subtracts those that were ahead
+//   A  rank_target_kernel<HmlpHead>   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for
+//                                     a target whose own score is -inf or NaN (never touched again)
+//   B  rank_hmlp_scan_kernel          the scan's stream over a tile of HMLP_QT PAIRS (query rows gathered through q_idx)
+//                                     and a chunk of candidates; every score is compared with the pair's target in
+//                                     registers and counted; one 64-bit integer atomic per (pair, chunk)
+//   C  rank_excl_kernel<HmlpHead>     only with exclusions: B counted the excluded ids too; one wave per pair recomputes
+//                                     the scalar chain of its query row's excluded ids and subtracts those that were ahead
+// (A and C: topk_device.h.)
 struct HmlpRankArgs {
     HmlpHead h;
     const int64_t *q_idx, *t_idx;
@@ -316,27 +307,14 @@ struct HmlpRankArgs {
     int64_t n_p, chunk, tiles;
 };
 
-__global__ void rank_hmlp_target_kernel(HmlpHead a, const int64_t *__restrict__ qi, const int64_t *__restrict__ ti, int64_t n,
-                                        float *__restrict__ out_score, int64_t *__restrict__ out_rank) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ti[p];
-    const float s = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H,
-                                    a.c_bias ? a.c_bias[i] : 0.f, a.q_bias ? a.q_bias[u] : 0.f);
-    out_score[p] = s;
-    out_rank[p] = s > -INFINITY ? 0 : -1;                      // (false for NaN)
-}
-
 template <int KT, int HT>
 __global__ __launch_bounds__(64) void rank_hmlp_scan_kernel(HmlpRankArgs a) {
     constexpr int PT = HMLP_QT;
     const int D = a.h.D;
     const int lane = threadIdx.x;
-    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
-    const int64_t p0 = tile * PT;
-    const int64_t c_begin = part * a.chunk;
-    const int64_t c_end = (c_begin + a.chunk < a.h.n_c) ? c_begin + a.chunk : a.h.n_c;
-    const int c_len = (int)(c_end - c_begin);                  // (chunk <= 2^30)
+    const ChunkGeom g = chunk_geom(a.tiles, PT, a.chunk, a.h.n_c);
+    const int64_t p0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
+    const int c_len = g.c_len();
 
     HmlpWave<KT, HT> wv;
     wv.init(a.h, lane);
@@ -391,36 +369,6 @@ __global__ __launch_bounds__(64) void rank_hmlp_scan_kernel(HmlpRankArgs a) {
     // (mine > 0 only for a pair below n_p whose target is ranked: the others wait for +inf)
     if (lane < PT && mine > 0)
         atomicAdd(reinterpret_cast<unsigned long long *>(a.out_rank + p0 + lane), (unsigned long long)mine);
-}
-
-// One wave per pair over the exclusion list of its query row
-__global__ __launch_bounds__(256) void rank_hmlp_excl_kernel(HmlpHead a, const int64_t *__restrict__ qi,
-                                                             const int64_t *__restrict__ ti, int64_t n_p,
-                                                             const int64_t *__restrict__ excl_off,
-                                                             const int64_t *__restrict__ excl_ids,
-                                                             const float *__restrict__ t_score, int64_t *out_rank) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (p >= n_p) return;
-    const float st = t_score[p];
-    if (!(st > -INFINITY)) return;                            // a pair at -1 keeps its -1
-    const int64_t u = qi[p], t = ti[p];
-    const int64_t lo = excl_off[u], hi = excl_off[u + 1];
-    const float qb = a.q_bias ? a.q_bias[u] : 0.f;
-    int n = 0;
-    for (int64_t e0 = lo; e0 < hi; e0 += 64) {
-        const int64_t e = e0 + lane;
-        if (e >= hi) continue;
-        const int64_t i = excl_ids[e];
-        if (i < 0 || i >= a.n_c || i == t) continue;
-        const float s = hmlp_pair_score(a.q + u * a.D, a.c + i * a.c_stride, a.W, a.b, a.w, a.D, a.H,
-                                        a.c_bias ? a.c_bias[i] : 0.f, qb);
-        n += ahead<int64_t>(s, i, st, t) ? 1 : 0;
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
-    if (lane == 0 && n > 0)
-        atomicAdd(reinterpret_cast<unsigned long long *>(out_rank + p), (unsigned long long)(-(int64_t)n));
 }
 
 template <int KT, int HT>
@@ -480,107 +428,55 @@ inline HmlpHead hmlp_head(const float *q, const float *q_bias, const float *c, i
 using namespace r4r;
 
 extern "C" size_t r4r_topk_hmlp_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk) {
-    if (n_q <= 0 || n_c <= 0 || K < 1 || K > TOPK_MAX_K || chunk < 0) return 0;
-    const int64_t parts = cdiv(n_c, hmlp_resolve_chunk(n_q, n_c, chunk));
-    if (parts <= 1) return 0;
-    return (size_t)n_q * (size_t)parts * (size_t)K * (sizeof(float) + sizeof(int64_t));
+    return lists_ws_bytes(n_q, n_c, K, chunk, HMLP_QT);
 }
 
 extern "C" int r4r_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes,
                              int64_t *out_ids, float *out_scores, void *stream) {
-    R4R_REQUIRE(K >= 1 && K <= TOPK_MAX_K, "topk_hmlp: K = %d outside 1 .. %d", K, TOPK_MAX_K);
-    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "topk_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
-    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "topk_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
-    R4R_REQUIRE(n_q >= 0 && n_c >= 0, "topk_hmlp: negative n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "topk_hmlp: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "topk_hmlp: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(n_q == 0 || (out_ids != nullptr && out_scores != nullptr), "topk_hmlp: null output");
-    R4R_REQUIRE(n_q < ((int64_t)1 << 31), "topk_hmlp: n_q = %lld too large", (long long)n_q);
-    R4R_REQUIRE(c_stride >= D, "topk_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
-    if (n_q == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "topk_hmlp: null w or W with H > 0");
-    R4R_REQUIRE(D == 0 || (q != nullptr && c != nullptr), "topk_hmlp: null q or c with D > 0");
     HmlpScanArgs a;
     a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    bool work;
+    int rc = topk_check("topk_hmlp", a.h, n_q, excl_off, excl_ids, K, chunk, out_ids, out_scores, &work);
+    if (rc != R4R_OK || !work) return rc;
+    ListsPlan p;
+    rc = topk_plan("topk_hmlp", n_q, n_c, K, chunk, HMLP_QT, HMLP_QT, ws, ws_bytes, out_ids, out_scores, &p);
+    if (rc != R4R_OK) return rc;
     a.excl_off = excl_off; a.excl_ids = excl_ids;
-    a.n_q = n_q; a.K = K;
-    a.chunk = hmlp_resolve_chunk(n_q, n_c, chunk);
-    a.parts = cdiv(n_c, a.chunk);
-    a.tiles = cdiv(n_q, HMLP_QT);
-    R4R_REQUIRE(a.parts * a.tiles < ((int64_t)1 << 31), "topk_hmlp: %lld chunks x %lld query tiles exceed the grid",
-                (long long)a.parts, (long long)a.tiles);
-    const size_t need = r4r_topk_hmlp_ws_bytes(n_q, n_c, K, chunk);
-    if (need > 0 && (ws == nullptr || ws_bytes < need)) {
-        set_error("topk_hmlp: workspace %zu < %zu bytes", ws_bytes, need);
-        return R4R_ERR_WORKSPACE;
-    }
+    a.out_scores = p.scan_scores; a.out_ids = p.scan_ids;
+    a.n_q = n_q; a.chunk = p.chunk; a.parts = p.parts; a.tiles = p.tiles; a.K = K;
     hipStream_t st = as_stream(stream);
-    if (a.parts == 1) {
-        a.out_scores = out_scores;
-        a.out_ids = out_ids;
-    } else {
-        a.out_ids = reinterpret_cast<int64_t *>(ws);
-        a.out_scores = reinterpret_cast<float *>(a.out_ids + (size_t)n_q * a.parts * K);
-    }
-    const int rc = dispatch_hmlp_scan(a, st);
-    if (rc != R4R_OK || a.parts == 1) return rc;
-    return topk_launch_merge(a.out_scores, a.out_ids, n_q, a.parts, K, out_ids, out_scores, st);
+    return topk_finish(p, dispatch_hmlp_scan(a, st), n_q, K, out_ids, out_scores, st);
 }
 
 extern "C" int r4r_pair_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream) {
-    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "pair_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
-    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "pair_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
-    R4R_REQUIRE(n >= 0 && n_q >= 0 && n_c >= 0, "pair_hmlp: negative size");
-    if (n == 0) return R4R_OK;
-    R4R_REQUIRE(n_q > 0 && n_c > 0, "pair_hmlp: pairs into an empty table");
-    R4R_REQUIRE(c_stride >= D, "pair_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
-    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "pair_hmlp: null w or W with H > 0");
-    R4R_REQUIRE(q_idx != nullptr && c_idx != nullptr && out != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
-                "pair_hmlp: null pointer");
-    R4R_REQUIRE(cdiv(n, 256) < ((int64_t)1 << 31), "pair_hmlp: n = %lld exceeds the grid", (long long)n);
     const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
-    hipLaunchKernelGGL(pair_hmlp_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), h, q_idx, c_idx, n, out);
-    return check_launch("pair_hmlp_kernel");
+    bool work;
+    const int rc = pair_check("pair_hmlp", h, n_q, q_idx, c_idx, n, out, &work);
+    if (rc != R4R_OK || !work) return rc;
+    return launch_pairs(h, q_idx, c_idx, n, out, as_stream(stream));
 }
 
 extern "C" int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
                              const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream) {
-    R4R_REQUIRE(D >= 0 && D <= HMLP_MAX_D, "rank_hmlp: D = %d outside 0 .. %d", D, HMLP_MAX_D);
-    R4R_REQUIRE(H >= 0 && H <= HMLP_MAX_H, "rank_hmlp: H = %d outside 0 .. %d", H, HMLP_MAX_H);
-    R4R_REQUIRE(n_p >= 0 && n_q >= 0 && n_c >= 0, "rank_hmlp: negative n_p, n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "rank_hmlp: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "rank_hmlp: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(c_stride >= D, "rank_hmlp: c_stride = %lld below D = %d", (long long)c_stride, D);
-    R4R_REQUIRE(n_p == 0 || (out_rank != nullptr && out_score != nullptr), "rank_hmlp: null output");
-    if (n_p == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(n_q > 0, "rank_hmlp: pairs into an empty query table");
-    R4R_REQUIRE(H == 0 || (w != nullptr && W != nullptr), "rank_hmlp: null w or W with H > 0");
-    R4R_REQUIRE(q_idx != nullptr && t_idx != nullptr && (D == 0 || (q != nullptr && c != nullptr)),
-                "rank_hmlp: null pointer (q_idx, t_idx, or q / c with D > 0)");
     HmlpRankArgs a;
     a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    bool work;
+    int rc = rank_check("rank_hmlp", a.h, n_q, q_idx, t_idx, n_p, excl_off, excl_ids, chunk, out_rank, out_score, &work);
+    if (rc != R4R_OK || !work) return rc;
+    ChunkPlan p;
+    rc = rank_plan("rank_hmlp", n_p, n_c, chunk, HMLP_QT, HMLP_QT, &p);
+    if (rc != R4R_OK) return rc;
     a.q_idx = q_idx; a.t_idx = t_idx;
     a.t_score = out_score; a.out_rank = out_rank;
-    a.n_p = n_p;
-    a.chunk = hmlp_resolve_chunk(n_p, n_c, chunk);
-    a.tiles = cdiv(n_p, HMLP_QT);
-    const int64_t parts = cdiv(n_c, a.chunk);
-    R4R_REQUIRE(parts * a.tiles < ((int64_t)1 << 31) && cdiv(n_p, 4) < ((int64_t)1 << 31),
-                "rank_hmlp: %lld chunks x %lld pair tiles exceed the grid", (long long)parts, (long long)a.tiles);
+    a.n_p = n_p; a.chunk = p.chunk; a.tiles = p.tiles;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(rank_hmlp_target_kernel, dim3((unsigned)cdiv(n_p, 256)), dim3(256), 0, st, a.h, q_idx, t_idx, n_p,
-                       out_score, out_rank);
-    int rc = check_launch("rank_hmlp_target_kernel");
+    rc = launch_rank_targets(a.h, q_idx, t_idx, n_p, out_score, out_rank, st);
     if (rc != R4R_OK) return rc;
-    rc = dispatch_hmlp_rank(a, parts, st);
-    if (rc != R4R_OK || excl_off == nullptr) return rc;
-    hipLaunchKernelGGL(rank_hmlp_excl_kernel, dim3((unsigned)cdiv(n_p, 4)), dim3(256), 0, st, a.h, q_idx, t_idx, n_p, excl_off,
-                       excl_ids, (const float *)out_score, out_rank);
-    return check_launch("rank_hmlp_excl_kernel");
+    return rank_finish(a.h, dispatch_hmlp_rank(a, p.parts, st), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
 }

@@ -12,9 +12,11 @@
 // One accumulator per query and chain stays in registers while the columns stream by in blocks.  Scores are never
 // written: each is compared with its query's K-th best, survivors go through topk_device.h's list_insert, the partial
 // lists have r4r_topk_dot's workspace layout and topk.hip's merge kernel finishes (skipped for a single chunk).
-// r4r_rank_relu: the same stream with counters in place of lists.  Every kernel of this file computes a score with
-// the SAME instruction sequence on the same operands (relu_term / the fmaf of the dot, ascending j, three additions),
-// so a score's bits depend on its own pair only.
+// r4r_rank_relu: the same stream with counters in place of lists.  The two streams and topk_device.h's scalar kernels
+// over this file's ReluHead compute a score with the SAME instruction sequence on the same operands (relu_term / the
+// fmaf of the dot, ascending j, three additions), so a score's bits depend on its own pair only.
+// This file has the two streams and the head; the scalar kernels, the chunk rule, the argument checks and the plan of a
+// call are topk_device.h's, shared with topk.hip and topk_hmlp.hip.
 #include <math.h>
 
 #include "common.h"
@@ -30,18 +32,6 @@ constexpr int RELU_MAX_P = 128;
 constexpr int RELU_QT = 16;        // queries (pairs, for the rank) per wave
 constexpr int RELU_CB = 8;         // columns of a candidate row a lane holds at a time
 
-// the chunk the call runs with: the caller's, or one that gives every CU its waves (topk_resolve_chunk's rule over
-// this file's query tile)
-inline int64_t relu_resolve_chunk(int64_t n_q, int64_t n_c, int64_t chunk) {
-    if (chunk > 0) return chunk;
-    const int64_t tiles = cdiv(n_q, RELU_QT);
-    int64_t parts = cdiv(TOPK_TARGET_WAVES, tiles > 0 ? tiles : 1);
-    const int64_t most = cdiv(n_c, TOPK_MIN_CHUNK);
-    if (parts > most) parts = most;
-    if (parts < 1) parts = 1;
-    return cdiv(cdiv(n_c, parts), 64) * 64;
-}
-
 // one hidden term of the chain: add, max, fma -- explicitly these three
 __device__ __forceinline__ float relu_term(float w, float q, float c, float h) {
     return __builtin_fmaf(w, __builtin_fmaxf(q + c, 0.f), h);
@@ -54,6 +44,39 @@ __device__ __forceinline__ float relu_pair_score(const float *q, const float *c,
     for (int j = 0; j < H; ++j) h = relu_term(w[j], q[j], c[j], h);
     for (int j = 0; j < P; ++j) d = __builtin_fmaf(q[H + j], c[H + j], d);
     return ((h + d) + cb) + qb;
+}
+
+// The head of this form (topk_device.h): the scalar chain over the rows of pair (u, i)
+struct ReluHead {
+    const float *q, *q_bias, *c, *c_bias, *w;
+    int64_t n_c, c_stride;
+    int H, P;
+
+    __device__ __forceinline__ float q_bias_of(int64_t u) const { return q_bias ? q_bias[u] : 0.f; }
+    __device__ __forceinline__ float score(int64_t u, int64_t i, float qb) const {
+        return relu_pair_score(q + u * (H + P), c + i * c_stride, w, H, P, c_bias ? c_bias[i] : 0.f, qb);
+    }
+    __device__ __forceinline__ float score(int64_t u, int64_t i) const { return score(u, i, q_bias_of(u)); }
+
+    static constexpr const char *width_name = "H + P";
+    int width() const { return H + P; }
+    int ranges(const char *fn) const {
+        R4R_REQUIRE(H >= 0 && H <= RELU_MAX_H, "%s: H = %d outside 0 .. %d", fn, H, RELU_MAX_H);
+        R4R_REQUIRE(P >= 0 && P <= RELU_MAX_P, "%s: P = %d outside 0 .. %d", fn, P, RELU_MAX_P);
+        return R4R_OK;
+    }
+    int weights(const char *fn) const {
+        R4R_REQUIRE(H == 0 || w != nullptr, "%s: null w with H > 0", fn);
+        return R4R_OK;
+    }
+};
+
+inline ReluHead relu_head(const float *q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                          const float *c_bias, const float *w, int H, int P) {
+    ReluHead h;
+    h.q = q; h.q_bias = q_bias; h.c = c; h.c_bias = c_bias; h.w = w;
+    h.n_c = n_c; h.c_stride = c_stride; h.H = H; h.P = P;
+    return h;
 }
 
 // NB columns from j0 of the lane's candidate row against the tile's queries.  qs: LDS [H + P][RELU_QT] (column-major),
@@ -140,10 +163,8 @@ __global__ __launch_bounds__(64) void relu_scan_kernel(ReluScanArgs a) {
     int *id = reinterpret_cast<int *>(sc + QT * K);            // [QT][K]  candidate - chunk begin
 
     const int lane = threadIdx.x;
-    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
-    const int64_t u0 = tile * QT;
-    const int64_t c_begin = part * a.chunk;
-    const int64_t c_end = (c_begin + a.chunk < a.n_c) ? c_begin + a.chunk : a.n_c;
+    const ChunkGeom g = chunk_geom(a.tiles, QT, a.chunk, a.n_c);
+    const int64_t u0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
 
     for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
     for (int e = lane; e < HP * QT; e += 64) {
@@ -180,15 +201,7 @@ __global__ __launch_bounds__(64) void relu_scan_kernel(ReluScanArgs a) {
                 const float v = lane_value(sv[i], src);
                 const int64_t ci = base + src;
                 if (!(v > thr[i])) continue;                   // (an earlier survivor raised the bar)
-                if (a.excl_off != nullptr) {
-                    int64_t lo = a.excl_off[u0 + i], hi = a.excl_off[u0 + i + 1];
-                    const int64_t end = hi;
-                    while (lo < hi) {
-                        const int64_t mid = lo + ((hi - lo) >> 1);
-                        if (a.excl_ids[mid] < ci) lo = mid + 1; else hi = mid;
-                    }
-                    if (lo < end && a.excl_ids[lo] == ci) continue;
-                }
+                if (is_excluded(a.excl_off, a.excl_ids, u0 + i, ci)) continue;
                 thr[i] = list_insert<int>(sc + i * K, id + i * K, K, v, (int)(ci - c_begin), lane);
             }
         }
@@ -198,7 +211,7 @@ __global__ __launch_bounds__(64) void relu_scan_kernel(ReluScanArgs a) {
     for (int ql = 0; ql < QT; ++ql) {
         const int64_t u = u0 + ql;
         if (u >= a.n_q) break;
-        const int64_t o = (u * a.parts + part) * K;
+        const int64_t o = (u * a.parts + g.part) * K;
         for (int p = lane; p < K; p += 64) {
             const int ci = id[ql * K + p];
             a.out_scores[o + p] = sc[ql * K + p];              // (-inf in an unused slot)
@@ -207,25 +220,16 @@ __global__ __launch_bounds__(64) void relu_scan_kernel(ReluScanArgs a) {
     }
 }
 
-__global__ void pair_relu_kernel(const float *__restrict__ q, const float *__restrict__ q_bias, const float *__restrict__ c,
-                                 int64_t c_stride, const float *__restrict__ c_bias, const float *__restrict__ w, int H, int P,
-                                 const int64_t *__restrict__ qi, const int64_t *__restrict__ ci, int64_t n,
-                                 float *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ci[p];
-    out[p] = relu_pair_score(q + u * (H + P), c + i * c_stride, w, H, P, c_bias ? c_bias[i] : 0.f, q_bias ? q_bias[u] : 0.f);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // r4r_rank_relu: r4r_rank_dot's three launches over this file's chain.
-//   A  rank_relu_target_kernel   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for a
-//                                target whose own score is -inf or NaN (never touched again)
-//   B  rank_relu_scan_kernel     the scan's stream over a tile of RELU_QT PAIRS (query rows gathered through q_idx into
-//                                LDS) and a chunk of candidates; every score is compared with the pair's target in
-//                                registers and counted; one 64-bit integer atomic per (pair, chunk)
-//   C  rank_relu_excl_kernel     only with exclusions: B counted the excluded ids too; one wave per pair recomputes the
-//                                scalar chain of its query row's excluded ids and subtracts those that were ahead
+//   A  rank_target_kernel<ReluHead>   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for
+//                                     a target whose own score is -inf or NaN (never touched again)
+//   B  rank_relu_scan_kernel          the scan's stream over a tile of RELU_QT PAIRS (query rows gathered through q_idx
+//                                     into LDS) and a chunk of candidates; every score is compared with the pair's
+//                                     target in registers and counted; one 64-bit integer atomic per (pair, chunk)
+//   C  rank_excl_kernel<ReluHead>     only with exclusions: B counted the excluded ids too; one wave per pair recomputes
+//                                     the scalar chain of its query row's excluded ids and subtracts those that were ahead
+// (A and C: topk_device.h.)
 struct ReluRankArgs {
     const float *q, *q_bias, *c, *c_bias, *w;
     const int64_t *q_idx, *t_idx;
@@ -234,20 +238,6 @@ struct ReluRankArgs {
     int64_t n_p, n_c, c_stride, chunk, tiles;
     int H, P;
 };
-
-__global__ void rank_relu_target_kernel(const float *__restrict__ q, const float *__restrict__ q_bias,
-                                        const float *__restrict__ c, int64_t c_stride, const float *__restrict__ c_bias,
-                                        const float *__restrict__ w, int H, int P, const int64_t *__restrict__ qi,
-                                        const int64_t *__restrict__ ti, int64_t n, float *__restrict__ out_score,
-                                        int64_t *__restrict__ out_rank) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t u = qi[p], i = ti[p];
-    const float s = relu_pair_score(q + u * (H + P), c + i * c_stride, w, H, P, c_bias ? c_bias[i] : 0.f,
-                                    q_bias ? q_bias[u] : 0.f);
-    out_score[p] = s;
-    out_rank[p] = s > -INFINITY ? 0 : -1;                      // (false for NaN)
-}
 
 __global__ __launch_bounds__(64) void rank_relu_scan_kernel(ReluRankArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char relu_lds[];
@@ -258,11 +248,9 @@ __global__ __launch_bounds__(64) void rank_relu_scan_kernel(ReluRankArgs a) {
     float *ws = qbs + PT;                                      // [H]
 
     const int lane = threadIdx.x;
-    const int64_t tile = blockIdx.x % a.tiles, part = blockIdx.x / a.tiles;
-    const int64_t p0 = tile * PT;
-    const int64_t c_begin = part * a.chunk;
-    const int64_t c_end = (c_begin + a.chunk < a.n_c) ? c_begin + a.chunk : a.n_c;
-    const int c_len = (int)(c_end - c_begin);                  // (chunk <= 2^30)
+    const ChunkGeom g = chunk_geom(a.tiles, PT, a.chunk, a.n_c);
+    const int64_t p0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
+    const int c_len = g.c_len();
 
     for (int e = lane; e < HP * PT; e += 64) {
         const int j = e / PT;
@@ -315,149 +303,68 @@ __global__ __launch_bounds__(64) void rank_relu_scan_kernel(ReluRankArgs a) {
         atomicAdd(reinterpret_cast<unsigned long long *>(a.out_rank + p0 + lane), (unsigned long long)mine);
 }
 
-// One wave per pair over the exclusion list of its query row
-__global__ __launch_bounds__(256) void rank_relu_excl_kernel(const float *__restrict__ q, const float *__restrict__ q_bias,
-                                                             const float *__restrict__ c, int64_t n_c, int64_t c_stride,
-                                                             const float *__restrict__ c_bias, const float *__restrict__ w,
-                                                             int H, int P, const int64_t *__restrict__ qi,
-                                                             const int64_t *__restrict__ ti, int64_t n_p,
-                                                             const int64_t *__restrict__ excl_off,
-                                                             const int64_t *__restrict__ excl_ids,
-                                                             const float *__restrict__ t_score, int64_t *out_rank) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    if (p >= n_p) return;
-    const float st = t_score[p];
-    if (!(st > -INFINITY)) return;                            // a pair at -1 keeps its -1
-    const int64_t u = qi[p], t = ti[p];
-    const int64_t lo = excl_off[u], hi = excl_off[u + 1];
-    const float qb = q_bias ? q_bias[u] : 0.f;
-    int n = 0;
-    for (int64_t e0 = lo; e0 < hi; e0 += 64) {
-        const int64_t e = e0 + lane;
-        if (e >= hi) continue;
-        const int64_t i = excl_ids[e];
-        if (i < 0 || i >= n_c || i == t) continue;
-        const float s = relu_pair_score(q + u * (H + P), c + i * c_stride, w, H, P, c_bias ? c_bias[i] : 0.f, qb);
-        n += ahead<int64_t>(s, i, st, t) ? 1 : 0;
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) n += __shfl_xor(n, m);
-    if (lane == 0 && n > 0)
-        atomicAdd(reinterpret_cast<unsigned long long *>(out_rank + p), (unsigned long long)(-(int64_t)n));
-}
-
 }  // namespace
 }  // namespace r4r
 
 using namespace r4r;
 
 extern "C" size_t r4r_topk_relu_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk) {
-    if (n_q <= 0 || n_c <= 0 || K < 1 || K > TOPK_MAX_K || chunk < 0) return 0;
-    const int64_t parts = cdiv(n_c, relu_resolve_chunk(n_q, n_c, chunk));
-    if (parts <= 1) return 0;
-    return (size_t)n_q * (size_t)parts * (size_t)K * (sizeof(float) + sizeof(int64_t));
+    return lists_ws_bytes(n_q, n_c, K, chunk, RELU_QT);
 }
 
 extern "C" int r4r_topk_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *w, int H, int P, const int64_t *excl_off,
                              const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes, int64_t *out_ids,
                              float *out_scores, void *stream) {
-    R4R_REQUIRE(K >= 1 && K <= TOPK_MAX_K, "topk_relu: K = %d outside 1 .. %d", K, TOPK_MAX_K);
-    R4R_REQUIRE(H >= 0 && H <= RELU_MAX_H, "topk_relu: H = %d outside 0 .. %d", H, RELU_MAX_H);
-    R4R_REQUIRE(P >= 0 && P <= RELU_MAX_P, "topk_relu: P = %d outside 0 .. %d", P, RELU_MAX_P);
-    R4R_REQUIRE(n_q >= 0 && n_c >= 0, "topk_relu: negative n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "topk_relu: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "topk_relu: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(n_q == 0 || (out_ids != nullptr && out_scores != nullptr), "topk_relu: null output");
-    R4R_REQUIRE(n_q < ((int64_t)1 << 31), "topk_relu: n_q = %lld too large", (long long)n_q);
-    R4R_REQUIRE(c_stride >= H + P, "topk_relu: c_stride = %lld below H + P = %d", (long long)c_stride, H + P);
-    if (n_q == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(H == 0 || w != nullptr, "topk_relu: null w with H > 0");
-    R4R_REQUIRE(H + P == 0 || (q != nullptr && c != nullptr), "topk_relu: null q or c with H + P > 0");
+    const ReluHead h = relu_head(q, q_bias, c, n_c, c_stride, c_bias, w, H, P);
+    bool work;
+    int rc = topk_check("topk_relu", h, n_q, excl_off, excl_ids, K, chunk, out_ids, out_scores, &work);
+    if (rc != R4R_OK || !work) return rc;
+    ListsPlan p;
+    rc = topk_plan("topk_relu", n_q, n_c, K, chunk, RELU_QT, RELU_QT, ws, ws_bytes, out_ids, out_scores, &p);
+    if (rc != R4R_OK) return rc;
     ReluScanArgs a;
     a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias; a.w = w;
     a.excl_off = excl_off; a.excl_ids = excl_ids;
-    a.n_q = n_q; a.n_c = n_c; a.c_stride = c_stride; a.H = H; a.P = P; a.K = K;
-    a.chunk = relu_resolve_chunk(n_q, n_c, chunk);
-    a.parts = cdiv(n_c, a.chunk);
-    a.tiles = cdiv(n_q, RELU_QT);
-    R4R_REQUIRE(a.parts * a.tiles < ((int64_t)1 << 31), "topk_relu: %lld chunks x %lld query tiles exceed the grid",
-                (long long)a.parts, (long long)a.tiles);
-    const size_t need = r4r_topk_relu_ws_bytes(n_q, n_c, K, chunk);
-    if (need > 0 && (ws == nullptr || ws_bytes < need)) {
-        set_error("topk_relu: workspace %zu < %zu bytes", ws_bytes, need);
-        return R4R_ERR_WORKSPACE;
-    }
+    a.out_scores = p.scan_scores; a.out_ids = p.scan_ids;
+    a.n_q = n_q; a.n_c = n_c; a.c_stride = c_stride; a.chunk = p.chunk; a.parts = p.parts; a.tiles = p.tiles;
+    a.H = H; a.P = P; a.K = K;
     hipStream_t st = as_stream(stream);
-    if (a.parts == 1) {
-        a.out_scores = out_scores;
-        a.out_ids = out_ids;
-    } else {
-        a.out_ids = reinterpret_cast<int64_t *>(ws);
-        a.out_scores = reinterpret_cast<float *>(a.out_ids + (size_t)n_q * a.parts * K);
-    }
     const size_t lds = relu_stage_floats(H, P) * 4 + (size_t)RELU_QT * (size_t)K * 8;
     static_assert((size_t)((RELU_MAX_H + RELU_MAX_P) * RELU_QT + RELU_QT + RELU_MAX_H) * 4 + (size_t)RELU_QT * TOPK_MAX_K * 8 <= 65536,
                   "the staged queries and the lists fit the LDS a launch gets without asking for more");
-    hipLaunchKernelGGL(relu_scan_kernel, dim3((unsigned)(a.parts * a.tiles)), dim3(64), lds, st, a);
-    const int rc = check_launch("relu_scan_kernel");
-    if (rc != R4R_OK || a.parts == 1) return rc;
-    return topk_launch_merge(a.out_scores, a.out_ids, n_q, a.parts, K, out_ids, out_scores, st);
+    hipLaunchKernelGGL(relu_scan_kernel, dim3((unsigned)(p.parts * p.tiles)), dim3(64), lds, st, a);
+    return topk_finish(p, check_launch("relu_scan_kernel"), n_q, K, out_ids, out_scores, st);
 }
 
 extern "C" int r4r_pair_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *c_idx,
                              int64_t n, float *out, void *stream) {
-    R4R_REQUIRE(H >= 0 && H <= RELU_MAX_H, "pair_relu: H = %d outside 0 .. %d", H, RELU_MAX_H);
-    R4R_REQUIRE(P >= 0 && P <= RELU_MAX_P, "pair_relu: P = %d outside 0 .. %d", P, RELU_MAX_P);
-    R4R_REQUIRE(n >= 0 && n_q >= 0 && n_c >= 0, "pair_relu: negative size");
-    if (n == 0) return R4R_OK;
-    R4R_REQUIRE(n_q > 0 && n_c > 0, "pair_relu: pairs into an empty table");
-    R4R_REQUIRE(c_stride >= H + P, "pair_relu: c_stride = %lld below H + P = %d", (long long)c_stride, H + P);
-    R4R_REQUIRE(H == 0 || w != nullptr, "pair_relu: null w with H > 0");
-    R4R_REQUIRE(q_idx != nullptr && c_idx != nullptr && out != nullptr && (H + P == 0 || (q != nullptr && c != nullptr)),
-                "pair_relu: null pointer");
-    R4R_REQUIRE(cdiv(n, 256) < ((int64_t)1 << 31), "pair_relu: n = %lld exceeds the grid", (long long)n);
-    hipLaunchKernelGGL(pair_relu_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), q, q_bias, c, c_stride,
-                       c_bias, w, H, P, q_idx, c_idx, n, out);
-    return check_launch("pair_relu_kernel");
+    const ReluHead h = relu_head(q, q_bias, c, n_c, c_stride, c_bias, w, H, P);
+    bool work;
+    const int rc = pair_check("pair_relu", h, n_q, q_idx, c_idx, n, out, &work);
+    if (rc != R4R_OK || !work) return rc;
+    return launch_pairs(h, q_idx, c_idx, n, out, as_stream(stream));
 }
 
 extern "C" int r4r_rank_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *t_idx,
                              int64_t n_p, const int64_t *excl_off, const int64_t *excl_ids, int64_t chunk, int64_t *out_rank,
                              float *out_score, void *stream) {
-    R4R_REQUIRE(H >= 0 && H <= RELU_MAX_H, "rank_relu: H = %d outside 0 .. %d", H, RELU_MAX_H);
-    R4R_REQUIRE(P >= 0 && P <= RELU_MAX_P, "rank_relu: P = %d outside 0 .. %d", P, RELU_MAX_P);
-    R4R_REQUIRE(n_p >= 0 && n_q >= 0 && n_c >= 0, "rank_relu: negative n_p, n_q or n_c");
-    R4R_REQUIRE(chunk >= 0 && chunk <= TOPK_MAX_CHUNK, "rank_relu: chunk = %lld outside 0 .. 2^30", (long long)chunk);
-    R4R_REQUIRE((excl_off == nullptr) == (excl_ids == nullptr), "rank_relu: excl_off and excl_ids go together (both or neither)");
-    R4R_REQUIRE(c_stride >= H + P, "rank_relu: c_stride = %lld below H + P = %d", (long long)c_stride, H + P);
-    R4R_REQUIRE(n_p == 0 || (out_rank != nullptr && out_score != nullptr), "rank_relu: null output");
-    if (n_p == 0 || n_c == 0) return R4R_OK;                    // nothing to rank: nothing enqueued, outputs untouched
-    R4R_REQUIRE(n_q > 0, "rank_relu: pairs into an empty query table");
-    R4R_REQUIRE(H == 0 || w != nullptr, "rank_relu: null w with H > 0");
-    R4R_REQUIRE(q_idx != nullptr && t_idx != nullptr && (H + P == 0 || (q != nullptr && c != nullptr)),
-                "rank_relu: null pointer (q_idx, t_idx, or q / c with H + P > 0)");
+    const ReluHead h = relu_head(q, q_bias, c, n_c, c_stride, c_bias, w, H, P);
+    bool work;
+    int rc = rank_check("rank_relu", h, n_q, q_idx, t_idx, n_p, excl_off, excl_ids, chunk, out_rank, out_score, &work);
+    if (rc != R4R_OK || !work) return rc;
+    ChunkPlan p;
+    rc = rank_plan("rank_relu", n_p, n_c, chunk, RELU_QT, RELU_QT, &p);
+    if (rc != R4R_OK) return rc;
     ReluRankArgs a;
     a.q = q; a.q_bias = q_bias; a.c = c; a.c_bias = c_bias; a.w = w; a.q_idx = q_idx; a.t_idx = t_idx;
     a.t_score = out_score; a.out_rank = out_rank;
-    a.n_p = n_p; a.n_c = n_c; a.c_stride = c_stride; a.H = H; a.P = P;
-    a.chunk = relu_resolve_chunk(n_p, n_c, chunk);
-    a.tiles = cdiv(n_p, RELU_QT);
-    const int64_t parts = cdiv(n_c, a.chunk);
-    R4R_REQUIRE(parts * a.tiles < ((int64_t)1 << 31) && cdiv(n_p, 4) < ((int64_t)1 << 31),
-                "rank_relu: %lld chunks x %lld pair tiles exceed the grid", (long long)parts, (long long)a.tiles);
+    a.n_p = n_p; a.n_c = n_c; a.c_stride = c_stride; a.chunk = p.chunk; a.tiles = p.tiles; a.H = H; a.P = P;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(rank_relu_target_kernel, dim3((unsigned)cdiv(n_p, 256)), dim3(256), 0, st, q, q_bias, c, c_stride, c_bias,
-                       w, H, P, q_idx, t_idx, n_p, out_score, out_rank);
-    int rc = check_launch("rank_relu_target_kernel");
+    rc = launch_rank_targets(h, q_idx, t_idx, n_p, out_score, out_rank, st);
     if (rc != R4R_OK) return rc;
-    hipLaunchKernelGGL(rank_relu_scan_kernel, dim3((unsigned)(parts * a.tiles)), dim3(64), relu_stage_floats(H, P) * 4, st, a);
-    rc = check_launch("rank_relu_scan_kernel");
-    if (rc != R4R_OK || excl_off == nullptr) return rc;
-    hipLaunchKernelGGL(rank_relu_excl_kernel, dim3((unsigned)cdiv(n_p, 4)), dim3(256), 0, st, q, q_bias, c, n_c, c_stride, c_bias,
-                       w, H, P, q_idx, t_idx, n_p, excl_off, excl_ids, (const float *)out_score, out_rank);
-    return check_launch("rank_relu_excl_kernel");
+    hipLaunchKernelGGL(rank_relu_scan_kernel, dim3((unsigned)(p.parts * p.tiles)), dim3(64), relu_stage_floats(H, P) * 4, st, a);
+    return rank_finish(h, check_launch("rank_relu_scan_kernel"), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
 }

@@ -247,10 +247,27 @@ class Catalogue:
         return torch.from_numpy(sub_off).to(self.dev), torch.from_numpy(np.ascontiguousarray(sub_ids)).to(self.dev)
 
     # ------------------------------------------------------------------ the calls
+    _form = 'dot'          # the entry points the calls go through: r4r_topk_<form>, r4r_pair_<form>, r4r_rank_<form>
+
+    def _head(self, q, n, qb):
+        """The leading arguments of the form's entry points: ``n`` query rows (q, q_bias), the cached item side and
+        what describes the score."""
+        return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), self.D)
+
+    def _pairs(self, users, items):
+        """(users, items) as host int64 tensors, equally long, every id in range."""
+        u = self._users(users)
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
+            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        return u, i
+
     def recommend(self, users, k=10, exclude_seen=True):
         """``users``: ids as a list, a numpy array or a tensor on any device.
         -> (items int64 [n, k], scores float32 [n, k]) on the device: per user the k best eligible items, score
-        descending, ties by ascending id; unused slots hold (-1, -inf)."""
+        descending, ties by ascending id; unused slots hold (-1, -inf).  One r4r_topk_<form> call."""
         k = int(k)
         if not 1 <= k <= MAX_K:
             raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
@@ -262,29 +279,25 @@ class Catalogue:
             return items, scores
         q, qb = self._queries(u)
         eo, ei = self._exclusions(u) if exclude_seen else (None, None)
-        lib = _lib.lib()
-        ws = ops._workspace(lib.r4r_topk_dot_ws_bytes(n, self.n_c, k, 0), self.dev)
-        _lib.call('r4r_topk_dot', ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), self.D,
-                  ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items), ptr(scores))
+        ws_bytes = getattr(_lib.lib(), 'r4r_topk_%s_ws_bytes' % self._form)
+        ws = ops._workspace(ws_bytes(n, self.n_c, k, 0), self.dev)
+        _lib.call('r4r_topk_' + self._form, *self._head(q, n, qb), ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items),
+                  ptr(scores))
         return items, scores
 
     def score_pairs(self, users, items):
         """The fp32 score ``recommend`` ranks by, for explicit (user, item) pairs (lists, arrays or tensors on any
-        device, equally long) -> float32 [n] on the device (-inf where the item is not eligible)."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        device, equally long) -> float32 [n] on the device (-inf where the item is not eligible).  One r4r_pair_<form>
+        call."""
+        u, i = self._pairs(users, items)
         out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
         if u.numel() == 0:
             return out
         uniq, inv = torch.unique(u, return_inverse=True)
         q, qb = self._queries(uniq)
         qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_pair_dot', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
-                  self.D, ptr(qi), ptr(ci), int(u.numel()), ptr(out))
+        _lib.call('r4r_pair_' + self._form, *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ci), int(u.numel()),
+                  ptr(out))
         return out
 
     def rank(self, users, items, exclude_seen=True):
@@ -292,14 +305,9 @@ class Catalogue:
         catalogue (lists, arrays or tensors on any device, equally long)
         -> (ranks int64 [n], scores float32 [n]) on the device: the number of eligible items ahead of the item (score
         descending, ties by ascending id; with ``exclude_seen`` the user's training items are not counted, the item
-        itself never is), -1 where the item is not eligible; the scores are ``score_pairs``' bits.  One r4r_rank_dot
+        itself never is), -1 where the item is not eligible; the scores are ``score_pairs``' bits.  One r4r_rank_<form>
         call: no list, no sort."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
+        u, i = self._pairs(users, items)
         n = int(u.numel())
         ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
         scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
@@ -309,8 +317,8 @@ class Catalogue:
         q, qb = self._queries(uniq)
         eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
         qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_rank_dot', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
-                  self.D, ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0, ptr(ranks), ptr(scores))
+        _lib.call('r4r_rank_' + self._form, *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ti), n, ptr(eo), ptr(ei),
+                  0, ptr(ranks), ptr(scores))
         return ranks, scores
 
 
@@ -411,8 +419,9 @@ def fold_relu_head(params, hyper_params, side, x=None, gx=None, bias=None, dtype
 
 class ReluCatalogue(Catalogue):
     """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
-    (-1, -inf) fill and argument checks) for the ReLU-sum families: deepconn++ and the three NeuMF stages
-    (``fold_relu_head``), ranked by r4r_topk_relu / r4r_pair_relu / r4r_rank_relu.
+    (-1, -inf) fill and argument checks: the three calls are ``Catalogue``'s own, over this class's ``_head``) for the
+    ReLU-sum families: deepconn++ and the three NeuMF stages (``fold_relu_head``), ranked by r4r_topk_relu /
+    r4r_pair_relu / r4r_rank_relu.
 
     ``refresh()`` flushes the engine's pending table updates and caches the item side (``c``, ``c_bias`` with -inf in
     ineligible rows, ``w``): deepconn++ runs the item documents through the tower ``tower_batch`` at a time, NeuMF
@@ -420,7 +429,7 @@ class ReluCatalogue(Catalogue):
     weights.  A pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks reach this
     class for deepconn++ only; NeuMF is served here and through ``eval_catalogue(catalogue=ReluCatalogue(...))``."""
 
-    _entry = dict(ws='r4r_topk_relu_ws_bytes', topk='r4r_topk_relu', pair='r4r_pair_relu', rank='r4r_rank_relu')
+    _form = 'relu'
 
     def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
         why = relu_catalogue_limits(hyper_params)
@@ -503,63 +512,8 @@ class ReluCatalogue(Catalogue):
                     P, self.hp, 'user', x=z, bias=ub[s:s + self.tower_batch])
             return q, qb
 
-    def recommend(self, users, k=10, exclude_seen=True):
-        """``Catalogue.recommend``'s contract over the ReLU-sum (one r4r_topk_relu call)."""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
-        u = self._users(users)
-        n = int(u.numel())
-        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
-        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
-        if n == 0 or self.n_c == 0:
-            return items, scores
-        q, qb = self._queries(u)
-        eo, ei = self._exclusions(u) if exclude_seen else (None, None)
-        lib = _lib.lib()
-        ws = ops._workspace(lib.r4r_topk_relu_ws_bytes(n, self.n_c, k, 0), self.dev)
-        _lib.call('r4r_topk_relu', ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.w),
-                  self.H, self.P, ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items), ptr(scores))
-        return items, scores
-
-    def score_pairs(self, users, items):
-        """``Catalogue.score_pairs``' contract over the ReLU-sum (one r4r_pair_relu call)."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
-        out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-        if u.numel() == 0:
-            return out
-        uniq, inv = torch.unique(u, return_inverse=True)
-        q, qb = self._queries(uniq)
-        qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_pair_relu', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
-                  ptr(self.w), self.H, self.P, ptr(qi), ptr(ci), int(u.numel()), ptr(out))
-        return out
-
-    def rank(self, users, items, exclude_seen=True):
-        """``Catalogue.rank``'s contract over the ReLU-sum (one r4r_rank_relu call: no list, no sort)."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
-        n = int(u.numel())
-        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
-        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
-        if n == 0 or self.n_c == 0:
-            return ranks, scores
-        uniq, inv = torch.unique(u, return_inverse=True)
-        q, qb = self._queries(uniq)
-        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
-        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_rank_relu', ptr(q), int(uniq.numel()), ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias),
-                  ptr(self.w), self.H, self.P, ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0, ptr(ranks), ptr(scores))
-        return ranks, scores
+    def _head(self, q, n, qb):
+        return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.w), self.H, self.P)
 
 
 HMLP_MAX_L = 64                     # r4r_topk_hmlp: D <= 64, H <= 64
@@ -587,7 +541,8 @@ def narre_catalogue_limits(hyper_params):
 
 class NarreCatalogue(Catalogue):
     """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
-    (-1, -inf) fill and argument checks) for NARRE, ranked by r4r_topk_hmlp / r4r_pair_hmlp / r4r_rank_hmlp.
+    (-1, -inf) fill and argument checks: the three calls are ``Catalogue``'s own, over this class's ``_head``) for NARRE,
+    ranked by r4r_topk_hmlp / r4r_pair_hmlp / r4r_rank_hmlp.
 
     NARRE's attention weighs the reviews of one side by the id embeddings of THAT side's neighbours -- the items a
     user's own reviews are about, the users who reviewed an item (NARRE.py:110-113) -- and a rating outside the training
@@ -602,6 +557,8 @@ class NarreCatalogue(Catalogue):
     forward per review and the eval-mode attention.  The query side is computed per call from the current weights.  A
     pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks do not reach this
     class; NARRE is served here and through ``eval_catalogue(catalogue=NarreCatalogue(...))``."""
+
+    _form = 'hmlp'
 
     def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
         why = narre_catalogue_limits(hyper_params)
@@ -680,63 +637,6 @@ class NarreCatalogue(Catalogue):
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.w),
                 self.D, self.H)
-
-    def recommend(self, users, k=10, exclude_seen=True):
-        """``Catalogue.recommend``'s contract over the product-MLP head (one r4r_topk_hmlp call)."""
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
-        u = self._users(users)
-        n = int(u.numel())
-        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
-        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
-        if n == 0 or self.n_c == 0:
-            return items, scores
-        q, qb = self._queries(u)
-        eo, ei = self._exclusions(u) if exclude_seen else (None, None)
-        lib = _lib.lib()
-        ws = ops._workspace(lib.r4r_topk_hmlp_ws_bytes(n, self.n_c, k, 0), self.dev)
-        _lib.call('r4r_topk_hmlp', *self._head(q, n, qb), ptr(eo), ptr(ei), k, 0, ptr(ws), ws.numel(), ptr(items),
-                  ptr(scores))
-        return items, scores
-
-    def score_pairs(self, users, items):
-        """``Catalogue.score_pairs``' contract over the product-MLP head (one r4r_pair_hmlp call)."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
-        out = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-        if u.numel() == 0:
-            return out
-        uniq, inv = torch.unique(u, return_inverse=True)
-        q, qb = self._queries(uniq)
-        qi, ci = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_pair_hmlp', *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ci), int(u.numel()), ptr(out))
-        return out
-
-    def rank(self, users, items, exclude_seen=True):
-        """``Catalogue.rank``'s contract over the product-MLP head (one r4r_rank_hmlp call: no list, no sort)."""
-        u = self._users(users)
-        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1)
-        if i.numel() != u.numel():
-            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
-        if i.numel() and (int(i.min()) < 0 or int(i.max()) >= self.n_c):
-            raise ValueError('catalogue: item ids must lie in [0, %d)' % self.n_c)
-        n = int(u.numel())
-        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
-        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
-        if n == 0 or self.n_c == 0:
-            return ranks, scores
-        uniq, inv = torch.unique(u, return_inverse=True)
-        q, qb = self._queries(uniq)
-        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
-        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
-        _lib.call('r4r_rank_hmlp', *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ti), n, ptr(eo), ptr(ei), 0,
-                  ptr(ranks), ptr(scores))
-        return ranks, scores
 
 
 def hook_limits(hyper_params):

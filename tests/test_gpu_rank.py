@@ -89,7 +89,9 @@ def random_lists(rng, n_q, n_c, longest=40):
 
 # ---------------------------------------------------------------- 1. exact arithmetic
 RANK_EXACT = sorted({(n, n_c, D) for n, n_c, D, _ in EXACT} |
-                    {(511, 257, 5), (512, 4099, 64), (577, 1000, 128), (513, 300, 256), (600, 255, 0)})
+                    {(511, 257, 5), (512, 4099, 64), (577, 1000, 128), (513, 300, 256), (600, 255, 0),
+                     # the target kernel's last 256-thread workgroup exactly full / holding one pair, 65 candidates
+                     (256, 65, 5), (257, 65, 8)})
 
 
 @functools.lru_cache(maxsize=None)
@@ -111,7 +113,7 @@ def exact_case(n_p, n_c, D):
 
 def test_the_exact_cases_hold_ties_on_both_sides_and_unranked_targets():
     """On the reference alone: the generator must produce what the exact test is there to catch."""
-    assert len(RANK_EXACT) == 48
+    assert len(RANK_EXACT) == 50
     lower = higher = unranked = 0
     for n_p, n_c, D in RANK_EXACT:
         k = exact_case(n_p, n_c, D)
@@ -231,6 +233,11 @@ def test_exclusions():
         assert np.array_equal(ranks, want), (chunk, np.argwhere(ranks != want)[:5].ravel())
         assert np.array_equal(sc, s[qi, ti].astype(np.float32), equal_nan=True), chunk
         assert np.array_equal(call(qi, ti, chunk, excl=False)[0], free), chunk
+        # five pairs: waves of the exclusion kernel's last workgroup have no pair.  Rows 2 (1000 excluded ids, the targets
+        # among them) and 3 (300): the kernel's lane loop takes 16 and 5 trips
+        five = slice(28, 33)
+        ranks, sc = call(qi[five], ti[five], chunk)
+        assert np.array_equal(ranks, want[five]) and np.array_equal(sc, s[qi[five], ti[five]].astype(np.float32), equal_nan=True), chunk
 
 
 # ---------------------------------------------------------------- 4. real-valued inputs

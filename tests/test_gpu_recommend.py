@@ -238,16 +238,23 @@ def test_pair_scores_have_the_bits_of_the_ranking(D):
     from reviews4rec_amd import _lib
     from reviews4rec_amd._lib import ptr
     K = 10
-    q, qb, c, cb = real_inputs(D, seed=1)
-    ids, sc = topk(q, qb, c, cb, K, 0, pad=0)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    qi = dev(np.repeat(np.arange(33, dtype=np.int64), K))
-    ci = dev(ids.reshape(-1))
-    out = torch.empty(33 * K, dtype=torch.float32, device=DEV)
-    qd, cd = dev(q if D else np.zeros((33, 1), np.float32)), dev(c if D else np.zeros((4099, 1), np.float32))
-    qbd, cbd = dev(qb), dev(cb)
-    _lib.call('r4r_pair_dot', ptr(qd), 33, ptr(qbd), ptr(cd), 4099, D, ptr(cbd), D, ptr(qi), ptr(ci), 33 * K, ptr(out))
-    assert np.array_equal(out.cpu().numpy().view(np.uint32), sc.reshape(-1).view(np.uint32))
+    # (against 65 candidates: 256 pairs fill the last 256-thread workgroup of the pair kernel exactly, 257 leave one pair
+    # in it)
+    for n_c, counts in ((4099, (33 * K,)), (65, (256, 257))):
+        q, qb, c, cb = real_inputs(D, n_c=n_c, seed=1)
+        ids, sc = topk(q, qb, c, cb, K, 0, pad=0)
+        assert (ids >= 0).all()
+        qd, cd = dev(q if D else np.zeros((33, 1), np.float32)), dev(c if D else np.zeros((n_c, 1), np.float32))
+        qbd, cbd = dev(qb), dev(cb)
+        for n in counts:
+            qi = dev(np.repeat(np.arange(33, dtype=np.int64), K)[:n])
+            ci = dev(ids.reshape(-1)[:n])
+            out = torch.full((33 * K,), 7.0, dtype=torch.float32, device=DEV)
+            _lib.call('r4r_pair_dot', ptr(qd), 33, ptr(qbd), ptr(cd), n_c, D, ptr(cbd), D, ptr(qi), ptr(ci), n, ptr(out))
+            out = out.cpu().numpy()
+            assert np.array_equal(out[:n].view(np.uint32), sc.reshape(-1)[:n].view(np.uint32)), (n_c, n)
+            assert (out[n:] == 7.0).all(), (n_c, n)                  # nothing is written past the last pair
 
 
 # ---------------------------------------------------------------- 5. batching invariance

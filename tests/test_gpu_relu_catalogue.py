@@ -252,12 +252,16 @@ def test_real_valued_inputs_within_the_a_priori_bound(H, P):
 @pytest.mark.parametrize('H, P', [(0, 0), (3, 0), (10, 10), (64, 64), (128, 128)])
 def test_pair_scores_have_the_bits_of_the_ranking(H, P):
     K = 10
-    q, qb, c, cb, w = real_inputs(H, P, rng=np.random.default_rng(300 + 17 * H + P))
-    t = Tables(q, qb, c, cb, w, H)
-    ids, sc = topk(t, K, 0)
-    assert (ids >= 0).all()
-    out = pairs(t, np.repeat(np.arange(33), K), ids.reshape(-1))
-    assert np.array_equal(out.view(np.uint32), sc.reshape(-1).view(np.uint32))
+    # (against 65 candidates: 256 pairs fill the last 256-thread workgroup of the pair kernel exactly, 257 leave one pair
+    # in it)
+    for n_c, counts in ((4099, (33 * K,)), (65, (256, 257))):
+        q, qb, c, cb, w = real_inputs(H, P, n_c=n_c, rng=np.random.default_rng(300 + 17 * H + P))
+        t = Tables(q, qb, c, cb, w, H)
+        ids, sc = topk(t, K, 0)
+        assert (ids >= 0).all()
+        for n in counts:
+            out = pairs(t, np.repeat(np.arange(33), K)[:n], ids.reshape(-1)[:n])
+            assert np.array_equal(out.view(np.uint32), sc.reshape(-1)[:n].view(np.uint32)), (n_c, n)
 
 
 # ---------------------------------------------------------------- 6. batching invariance
@@ -310,7 +314,11 @@ def host_ranks(S, qi, ti, excl):
 
 
 @pytest.mark.parametrize('n_p, n_c, H, P', [(1, 65, 3, 0), (17, 4099, 10, 10), (65, 65, 0, 5), (130, 4099, 64, 64),
-                                            (130, 65, 9, 7), (17, 4099, 128, 128)])
+                                            (130, 65, 9, 7), (17, 4099, 128, 128),
+                                            # the target kernel's last 256-thread workgroup exactly full / holding one pair
+                                            (256, 65, 3, 5), (257, 65, 10, 0),
+                                            # waves of the exclusion kernel's last workgroup without a pair (below)
+                                            (5, 257, 10, 10)])
 def test_ranks_are_the_count_of_candidates_ahead(n_p, n_c, H, P):
     rng = np.random.default_rng(700 + n_p + n_c + H)
     n_q = 9
@@ -328,6 +336,12 @@ def test_ranks_are_the_count_of_candidates_ahead(n_p, n_c, H, P):
         # (pairs sharing row 2, the pair (2, 3) twice, the tie partners 3 / 5, the -inf target 7, a target on its row's
         # exclusion list)
         lists[1] = np.union1d(lists[1], [ti[5]]).astype(np.int64)
+    if (n_p, n_c) == (5, 257):
+        # two lists of 100 ids (the lane loop of the exclusion kernel takes a second trip), one holding its pair's target
+        qi[:2] = [1, 2]
+        lists[1] = np.union1d(np.setdiff1d(rng.permutation(n_c), [ti[0]])[:99], [ti[0]]).astype(np.int64)
+        lists[2] = np.sort(np.setdiff1d(rng.permutation(n_c), [ti[1]])[:100]).astype(np.int64)
+        assert len(lists[1]) == len(lists[2]) == 100 and ti[0] in lists[1] and ti[1] not in lists[2]
     off = np.zeros(n_q + 1, np.int64)
     np.cumsum([len(l) for l in lists], out=off[1:])
     excl = (off, np.concatenate(lists))
