@@ -1245,6 +1245,68 @@ int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float 
                   const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
                   const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Catalogue recommendation: ReLU-FM heads.  The same lists, pair scores and ranks for a model whose head is
+ * Linear -> ReLU -> Linear -> FM over [user | item]:
+ *   TransNet(++)  TransNet.py:14-35      the source network: two towers over one side's document each, project =
+ *                                        Linear(2 L, L), ReLU, Linear(L, L) over [user tower | item tower]
+ *                 TransNet.py:105-119    the test-time score: source_fm over the source network's output (transnet++:
+ *                                        over [user_embedding | item_embedding | output]), column 0; it reads no
+ *                                        review of the pair
+ *                 common_pytorch_models.py:41-57   the FM: lin(x) + 1/2 sum_f ((x V)_f^2 - (x^2 V^2)_f)
+ *                 data.py:240-246        for a rating outside the training split nothing is removed from either document
+ *                 eval.py:31-32          the score is output[0] (eval.py:72 for the ranking metric)
+ * The first Linear separates, W0 [zu ; zi] + b0 = (W0[:, :L] zu + b0) + W0[:, L:] zi, and an FM of a linear image of
+ * h = relu(.) is a short sum of signed squares and one linear term of y = W h + b: rows (W2^T Vr)^T with s = +1/2, rows
+ * diag(sqrt(sum_f Vr^2)) W2 with s = -1/2, and one row lr^T W2 with l = 1 (reviews4rec_amd.recommend.fold_transnet_head
+ * has the table; transnet++'s embedding terms enter as P = 8 plain input columns and two scalars).
+ *
+ * score(u, i) is ONE fixed fp32 expression, D = H + P:
+ *   x_m = fmaxf(q[u][m] + c[i][m], 0.f)   m < H               C's fmaxf: a NaN sum counts as 0
+ *   x_m = q[u][m] + c[i][m]               H <= m < D          plain: a NaN here reaches the score
+ *   y_j = fmaf(W[j][m], x_m, y_j)                             m ascending from +0.0f, then y_j = y_j + b[j], j = 0 .. M-1
+ *   e_j = fmaf(s[j], y_j, l[j])
+ *   t_g = fmaf(e_j, y_j, t_g)                                 over the j with ((j >> 2) & 3) == g, ascending from +0.0f, g = 0 .. 3
+ *   score = ((((t_0 + t_1) + (t_2 + t_3)) + c_bias[i]) + q_bias[u])
+ * The four-way split of the last sum is the accumulator layout of v_mfma_f32_16x16x4_f32 with rows = rows of y: lane
+ * group l >> 4 holds rows 4 g + r of every 16, so the epilogue is four chains and two cross-lane adds.  A NULL b, q_bias
+ * or c_bias counts as 0.  Zero-padding D to a multiple of 4 and M to a multiple of 16 changes no bit: a pad column
+ * multiplies by W = 0, and a pad row (W, b, s, l all zero) gives y = 0, e = 0 and adds e y = 0 to its chain.
+ *   q [n_q, D] dense, q_bias [n_q] or NULL;  c rows c_stride >= D floats apart (the pad is never read), c_bias [n_c] or
+ *   NULL;  W [M, D] dense, row-major;  b [M] or NULL;  s [M], l [M]
+ * Everything else is r4r_topk_dot's contract: score descending, ties by ascending candidate id; a candidate whose score
+ * is -inf or NaN is never returned (-inf in c_bias marks a row ineligible), nor one on the query's ascending CSR
+ * exclusion list (excl_off [n_q + 1], excl_ids; both NULL = none); unused slots hold id -1 and score -inf.  The order
+ * is total and a score's bits depend on its own pair only: the result does not depend on `chunk`, the grid, or how
+ * queries and pairs are grouped into calls.
+ * Limits: 0 <= H <= 64 (the native limit of the TransNet engine), 0 <= P <= 16, 0 <= M <= 80, 1 <= K <= 128,
+ * 0 <= chunk <= 2^30 (0 = the library's choice), c_stride >= D, W, s and l non-NULL when M > 0, q and c non-NULL when
+ * D > 0, excl_off and excl_ids both or neither.  n_q == 0, n_c == 0 or n_p == 0 returns R4R_OK, enqueues nothing and
+ * leaves the outputs untouched.  Every refusal precedes the first launch and the first dereference; a short workspace
+ * is R4R_ERR_WORKSPACE.  Nothing allocates, nothing synchronises.
+ *
+ * r4r_topk_rfm: out_ids / out_scores [n_q, K].  Two launches (an MFMA scan whose A operand is W and whose B operand is
+ *   relu(q + c) formed in registers; r4r_topk_dot's merge), or one when the catalogue is a single chunk.  The workspace
+ *   holds the chunks' partial lists in r4r_topk_dot's layout.
+ * r4r_pair_rfm: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ * r4r_rank_rfm: r4r_rank_dot's semantics exactly.  out_score[p] has r4r_pair_rfm's bits; out_rank[p] counts the
+ *   candidates ahead of target t_idx[p] for query row q_idx[p] that are neither -inf / NaN nor on that ROW's exclusion
+ *   list; the target never counts against itself; a target whose own score is -inf or NaN gets -1.  Integer atomics
+ *   only: equal for every chunk, tiling and grouping.  No workspace.
+ * ---------------------------------------------------------------------- */
+size_t r4r_topk_rfm_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
+int r4r_topk_rfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *l, int H, int P, int M,
+                 const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes,
+                 int64_t *out_ids, float *out_scores, void *stream);
+int r4r_pair_rfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *l, int H, int P, int M,
+                 const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream);
+int r4r_rank_rfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *l, int H, int P, int M,
+                 const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
+                 const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ Layout
   recommend.py     catalogue top-K lists and full-catalogue ranks (Catalogue, catalogue_limits, fold_fm,
                    ranking_metrics) over csrc/topk.hip; the same for the ReLU-sum heads of deepconn++ and NeuMF
                    (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip, and for NARRE's
-                   product-MLP head (NarreCatalogue, narre_catalogue_limits) over csrc/topk_hmlp.hip
+                   product-MLP head (NarreCatalogue, narre_catalogue_limits) over csrc/topk_hmlp.hip, and for the TransNets'
+                   ReLU-FM head (TransNetCatalogue, transnet_catalogue_limits, fold_transnet_head) over csrc/topk_rfm.hip
 """
 __version__ = '0.1.0'
 
@@ -37,4 +38,5 @@ def get_model_class(model_type):
 from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
 from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
 from .recommend import NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
+from .recommend import TransNetCatalogue, fold_transnet_head, transnet_catalogue_limits  # noqa: E402,F401
 from .eval import eval_catalogue  # noqa: E402,F401

@@ -38,8 +38,19 @@ data.py:240-246), so per-user and per-item vectors exist and
 
 is ranked by r4r_topk_hmlp / r4r_rank_hmlp (csrc/topk_hmlp.hip: an MFMA scan whose A operand is W) through
 ``NarreCatalogue`` (``narre_catalogue_limits`` has the limits) and ``eval.eval_catalogue(catalogue=NarreCatalogue(...))``;
-``main``'s hooks still refuse it.  MF and the TransNets need an FM over a per-pair transform of the two sides and stay
-refused.
+``main``'s hooks still refuse it.
+
+The TransNets score a pair at test time with source_fm over Linear -> ReLU -> Linear of [user tower | item tower]
+(TransNet.py:105-119; eval.py:31-32 takes output[0]); both towers read one side's document only.  The first Linear
+separates as deepconn++'s does, and an FM of a linear image of h = relu(.) is a short sum of signed squares and one linear
+term of y = W h + b (``fold_transnet_head``), so
+
+    score(u, i) = sum_j y_j (s_j y_j + l_j) + user scalar + item scalar,    y = W [relu(qa[u] + ca[i]) ; qp[u] + cp[i]] + b
+
+is ranked by r4r_topk_rfm / r4r_rank_rfm (csrc/topk_rfm.hip: the same scan with relu(q + c) as the B operand and squares
+in the epilogue) through ``TransNetCatalogue`` (``transnet_catalogue_limits`` has the limits) and
+``eval.eval_catalogue(catalogue=TransNetCatalogue(...))``; ``main``'s hooks still refuse them.  MF (MF.py:45-49, an FM
+over [mlp | user * item]) stays refused: it needs product columns and about 2 L rows of y.
 
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
@@ -637,6 +648,194 @@ class NarreCatalogue(Catalogue):
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.w),
                 self.D, self.H)
+
+RFM_MAX_L = 64                      # r4r_topk_rfm: H <= 64, P <= 16, M <= 80
+_TRANSNET_EMB = 5                   # the width of transnet++'s id embeddings (TransNet.py:75-76)
+
+
+def transnet_catalogue_limits(hyper_params):
+    """None when ``TransNetCatalogue`` can rank this configuration, else the reason it cannot."""
+    mt = hyper_params['model_type']
+    if mt in SUPPORTED:
+        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
+    if mt in ('deepconn++', 'NeuMF'):
+        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
+    if mt == 'NARRE':
+        return 'model_type %r has a product-MLP head: NarreCatalogue serves it' % (mt,)
+    if mt not in ('transnet', 'transnet++'):
+        why = _REFUSED.get(mt)
+        return 'model_type %r has no ReLU-FM form: no class serves it%s' % (mt, ' (' + why + ')' if why else '')
+    if _latent_size(hyper_params) > RFM_MAX_L:
+        return 'latent_size %d > %d' % (_latent_size(hyper_params), RFM_MAX_L)
+    return None
+
+
+def fold_transnet_head(params, hyper_params, side, z, emb=None, dtype=torch.float32, head=True):
+    """One side of a TransNet's test-time score, source_fm([ue | ie |] project(cat(zu, zi)))[:, 0] (TransNet.py:105-119,
+    common_pytorch_models.py:41-57), as the rows of the ReLU-FM form (include/r4r.h):
+
+        score(u, i) = sum_{j<M} y_j (s_j y_j + l_j) + q_bias[u] + c_bias[i]
+        y = W x + b,   x_m = relu(qa[u][m] + ca[i][m])  m < H = L,   x_{H+f} = qp[u][f] + cp[i][f]  f < P
+
+    With W0, b0 = source.project.0, W2, b2 = source.project.2, V, lw, lb = source_fm.V, lin.weight[0], lin.bias, R = 8,
+    o = 10 (transnet++: the leading rows of V / lw that belong to [user_embedding | item_embedding]) or 0, Vr = V[o:],
+    lr = lw[o:], sig_k = sum_f Vr[k][f]^2 and M = R + L + 1:
+
+        qa = W0[:, :L] zu + b0      ca = W0[:, L:] zi
+        rows       W over the H ReLU'd inputs    b            s     l
+        f < R      (W2^T Vr)^T                   b2^T Vr     +1/2   0       the FM's (x V)_f, squared
+        R + k      diag(sqrt(sig)) W2            sqrt(sig) b2 -1/2  0       the FM's x_k^2 (V^2)_k, k < L
+        R + L      lr^T W2                       lr . b2      0     1       the FM's linear term
+        q_bias = lb                 c_bias = 0
+
+    transnet++ (P = 8): qp = V[0:5]^T ue, cp = V[5:10]^T ie enter row f through W[f][H + f] = 1, and the scalars
+    lw[0:5] . ue - 1/2 sum_k ue_k^2 sum_f V[k][f]^2 (the same over ie, V[5:10], lw[5:10]) go to q_bias / c_bias.
+    Dropout is the identity in eval mode.  ``params``: the model's parameters by state_dict key; ``z`` [n, L]: the side's
+    eval-mode source tower latents; ``emb`` [n, 5]: its id embedding rows (transnet++ only).
+    -> side 'user': (rows [n, H + P], q_bias [n], (W [M, H + P], b [M], s [M], l [M])), the last None with ``head=False``
+    (the head does not depend on the rows: a caller that holds it need not have it built again);
+    side 'item': (rows, c_bias [n]).
+    Plain torch on whatever device the inputs live on, computed in float64 and rounded once to ``dtype``."""
+    if side not in ('user', 'item'):
+        raise ValueError("fold_transnet_head: side must be 'user' or 'item', got %r" % (side,))
+    mt = hyper_params['model_type']
+    if mt not in ('transnet', 'transnet++'):
+        raise ValueError('fold_transnet_head: no ReLU-FM form for %r' % (mt,))
+    pp = mt == 'transnet++'
+    if (emb is None) == pp:
+        raise ValueError('fold_transnet_head: %s takes %s' % (mt, 'z and emb' if pp else 'z alone'))
+    f64 = lambda t: t.detach().to(torch.float64)
+    W0, b0, W2, b2, V, lw, lb = (f64(params[k]) for k in (
+        'source.project.0.weight', 'source.project.0.bias', 'source.project.2.weight', 'source.project.2.bias',
+        'source_fm.V', 'source_fm.lin.weight', 'source_fm.lin.bias'))
+    if z.dim() != 2 or (pp and (emb.dim() != 2 or emb.shape[0] != z.shape[0] or emb.shape[1] != _TRANSNET_EMB)):
+        raise ValueError('fold_transnet_head: z [n, L] and emb [n, %d] do not match' % _TRANSNET_EMB)
+    n, L = z.shape
+    o = 2 * _TRANSNET_EMB if pp else 0
+    R = V.shape[1]
+    lw = lw.reshape(-1)
+    if tuple(W0.shape) != (L, 2 * L) or tuple(W2.shape) != (L, L) or V.shape[0] != o + L or lw.numel() != o + L:
+        raise ValueError('fold_transnet_head: project %s %s / source_fm.V %s do not match latent width %d'
+                         % (tuple(W0.shape), tuple(W2.shape), tuple(V.shape), L))
+    user = side == 'user'
+    x = f64(z)
+    rows = x @ (W0[:, :L] if user else W0[:, L:]).T
+    bias = torch.zeros(n, dtype=torch.float64, device=z.device)
+    if user:
+        rows, bias = rows + b0, bias + lb.reshape(())
+    if pp:
+        e = f64(emb)
+        sl = slice(0, _TRANSNET_EMB) if user else slice(_TRANSNET_EMB, o)
+        rows = torch.cat([rows, e @ V[sl]], 1)
+        bias = bias + e @ lw[sl] - 0.5 * ((e * e) @ (V[sl] * V[sl]).sum(1))
+    if not user:
+        return rows.to(dtype), bias.to(dtype)
+    if not head:
+        return rows.to(dtype), bias.to(dtype), None
+    Vr, lr = V[o:], lw[o:]
+    root = (Vr * Vr).sum(1).sqrt()
+    P, M = (R if pp else 0), R + L + 1
+    W = torch.zeros((M, L + P), dtype=torch.float64, device=z.device)
+    W[:R, :L], W[R:R + L, :L], W[R + L, :L] = (W2.T @ Vr).T, root[:, None] * W2, lr @ W2
+    if pp:
+        W[torch.arange(R), L + torch.arange(R)] = 1.0
+    b = torch.cat([b2 @ Vr, root * b2, (lr @ b2).reshape(1)])
+    s = torch.cat([torch.full((R,), 0.5), torch.full((L,), -0.5), torch.zeros(1)]).to(torch.float64).to(z.device)
+    l = torch.cat([torch.zeros(R + L), torch.ones(1)]).to(torch.float64).to(z.device)
+    return rows.to(dtype), bias.to(dtype), tuple(t.to(dtype).contiguous() for t in (W, b, s, l))
+
+
+class TransNetCatalogue(Catalogue):
+    """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
+    (-1, -inf) fill and argument checks: the three calls are ``Catalogue``'s own, over this class's ``_head``) for
+    transnet and transnet++, ranked by r4r_topk_rfm / r4r_pair_rfm / r4r_rank_rfm.
+
+    At test time a TransNet predicts without the pair's review: source_fm over the source network (TransNet.py:105-119),
+    whose towers read the user's and the item's document -- every review of the owner; a rating outside the training
+    split removes nothing (data.py:240-246).  ``fold_transnet_head`` has the table.
+
+    ``refresh()`` flushes the engine's pending row updates and caches the item side (``c``, ``c_bias`` with -inf in
+    ineligible rows, the head ``W``, ``b``, ``s``, ``l``): the item documents through source.item_conv over
+    target.word2vec.weight, ``tower_batch`` at a time.  The query side is computed per call from the current weights.
+    A pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks do not reach this
+    class; the TransNets are served here and through ``eval_catalogue(catalogue=TransNetCatalogue(...))``."""
+
+    _form = 'rfm'
+
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
+        why = transnet_catalogue_limits(hyper_params)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
+        self.mt = hyper_params['model_type']
+        self.pp = self.mt == 'transnet++'
+        self.tower_batch = int(tower_batch)
+        self.dev = next(model.parameters()).device
+        if self.dev.type != 'cuda':
+            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
+                               'CPU fallback')
+        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
+        self.eligible = eligible_items(hyper_params, train_reader, candidates)
+        L = _latent_size(hyper_params)
+        self.H, self.P, self.M = L, (FM_RANK if self.pp else 0), FM_RANK + L + 1
+        self.D = self.H + self.P
+        self.n_c = self.n_items                                # candidate rows the kernel walks: one per item id
+        self._seen = None
+        self.refresh()
+
+    def _params(self):
+        return {k: v.detach() for k, v in self.model.named_parameters()}
+
+    def _tower(self, tower, idx):
+        """Eval-mode forward of a source tower over the target network's frozen word table."""
+        with torch.no_grad():
+            conv = tower.convs[0]
+            pooled, _ = ops.textcnn_fwd_raw(idx, self.model.target.word2vec.weight, conv.weight.detach(),
+                                            conv.bias.detach())
+            return ops.linear(pooled, tower.fc.weight.detach(), tower.fc.bias.detach())
+
+    def _side(self, P, side, ids, sel):
+        """``fold_transnet_head`` of the owners ``ids`` (a host int64 array; ``sel``: the same ids on the device)."""
+        src = self.model.source
+        pool, tower, table = ((self.reader.store.users, src.user_conv, 'user_embedding') if side == 'user' else
+                              (self.reader.store.items, src.item_conv, 'item_embedding'))
+        z = self._tower(tower, self._documents(pool, ids))
+        emb = getattr(self.model, table).weight.detach()[sel] if self.pp else None
+        return fold_transnet_head(P, self.hp, side, z, emb=emb, head=False)      # (the head is refresh()'s)
+
+    def refresh(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+        P = self._params()
+        elig = torch.from_numpy(self.eligible).to(self.dev)
+        c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
+        cb = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
+                sel = elig[s:s + self.tower_batch]                                                # dropped chunk by chunk
+                c[sel], cb[sel] = self._side(P, 'item', self.eligible[s:s + self.tower_batch], sel)
+            self.c, self.c_bias = c, cb
+            # the head is the user side's; the fold of zero user rows yields it without a tower forward
+            none = torch.zeros((0, self.H), dtype=torch.float32, device=self.dev)
+            no_emb = torch.zeros((0, _TRANSNET_EMB), dtype=torch.float32, device=self.dev) if self.pp else None
+            self.W, self.b, self.s, self.l = fold_transnet_head(P, self.hp, 'user', none, emb=no_emb)[2]
+
+    def _queries(self, u_host):
+        """(q [n, H + P], q_bias [n]) of the requested users from the current weights."""
+        P = self._params()
+        u = u_host.to(self.dev)
+        ids = u_host.numpy()
+        q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
+        qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            for s in range(0, len(ids), self.tower_batch):
+                q[s:s + self.tower_batch], qb[s:s + self.tower_batch], _ = self._side(
+                    P, 'user', ids[s:s + self.tower_batch], u[s:s + self.tower_batch])
+        return q, qb
+
+    def _head(self, q, n, qb):
+        return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.s),
+                ptr(self.l), self.H, self.P, self.M)
 
 
 def hook_limits(hyper_params):
