@@ -1307,6 +1307,70 @@ int r4r_rank_rfm(const float *q, int64_t n_q, const float *q_bias, const float *
                  const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
                  const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Catalogue recommendation: product-FM heads.  The same lists, pair scores and ranks for a model whose head is an FM
+ * over [Linear -> ReLU -> Linear of [user | item]  |  user * item]:
+ *   MF            MF.py:45-49 / 60-66    projection = Linear(2 L, L), ReLU, Linear(L, L) over [user embedding | item
+ *                                        embedding]; final = FM(2 L, L) over [projection | user embedding * item embedding]
+ *                 common_pytorch_models.py:41-57   the FM: lin(x) + 1/2 sum_f ((x V)_f^2 - (x^2 V^2)_f)
+ * The first Linear separates, W1 [ue ; ie] + b1 = (W1[:, :L] ue + b1) + W1[:, L:] ie; with h = relu(.) and m = ue * ie the
+ * FM's input is [W3 h + b3 ; m], so its squares are signed squares of y = W [h ; m] + b (rows (W3^T Va | Vb^T) with
+ * s = +1/2, rows diag(sqrt(sum_f Va^2)) W3 with s = -1/2), and everything else is PER COLUMN of x = [h ; m]: the linear
+ * term e = [la^T W3 | lm], and -1/2 sigma_b m^2 as g x^2 -- the square of a product column is that column's own x^2
+ * (reviews4rec_amd.recommend.fold_mf_head has the table).
+ *
+ * score(u, i) is ONE fixed fp32 expression, D = H + G:
+ *   x_m = fmaxf(q[u][m] + c[i][m], 0.f)   m < H               C's fmaxf: a NaN sum counts as 0
+ *   x_m = q[u][m] * c[i][m]               H <= m < D          a product: a NaN here reaches the score
+ *   y_j = fmaf(W[j][m], x_m, y_j)                             m ascending from +0.0f, then y_j = y_j + b[j], j = 0 .. M-1
+ *   t_k = fmaf(s[j] * y_j, y_j, t_k)                          over the j with ((j >> 2) & 3) == k, ascending from +0.0f
+ *   v_k = fmaf(fmaf(g[m], x_m, e[m]), x_m, v_k)               over the m with (m & 3) == k, ascending from +0.0f, k = 0 .. 3
+ *   score = (((((t_0 + v_0) + (t_1 + v_1)) + ((t_2 + v_2) + (t_3 + v_3))) + c_bias[i]) + q_bias[u])
+ * (s[j] * y_j is one rounded product.)  The four-way split of both sums is the layout of v_mfma_f32_16x16x4_f32 with
+ * rows = rows of y: lane group l >> 4 holds rows 4 k + r of every 16 of the result and columns 4 t + k of the input it
+ * forms, so the epilogue is four row chains, the four column chains the same lanes carried along, one add of the two
+ * and two cross-lane adds; the scalar pair kernel writes the same chain out and gives the scan's bits.  A NULL b, g, e,
+ * q_bias or c_bias counts as 0.  Zero-padding D to a multiple of 4 and M to a multiple of 16 changes no bit: a pad
+ * column (q = c = 0, so x = 0; W, g, e zero) adds fmaf(fmaf(0, 0, 0), 0, v_k) = v_k and multiplies by W = 0, and a pad
+ * row (W, b, s zero) gives y = 0 and adds fmaf(0, 0, t_k) = t_k.
+ *   q [n_q, D] dense, q_bias [n_q] or NULL;  c rows c_stride >= D floats apart (the pad is never read), c_bias [n_c] or
+ *   NULL;  W [M, D] dense, row-major;  b [M] or NULL;  s [M];  g [D] or NULL;  e [D] or NULL
+ * Everything else is r4r_topk_dot's contract: score descending, ties by ascending candidate id; a candidate whose score
+ * is -inf or NaN is never returned (-inf in c_bias marks a row ineligible), nor one on the query's ascending CSR
+ * exclusion list (excl_off [n_q + 1], excl_ids; both NULL = none); unused slots hold id -1 and score -inf.  The order
+ * is total and a score's bits depend on its own pair only: the result does not depend on `chunk`, the grid, or how
+ * queries and pairs are grouped into calls.
+ * Limits: 0 <= H <= 64, 0 <= G <= 64, 0 <= M <= 128, 1 <= K <= 128, 0 <= chunk <= 2^30 (0 = the library's choice),
+ * c_stride >= D, W and s non-NULL when M > 0, q and c non-NULL when D > 0, excl_off and excl_ids both or neither.
+ * n_q == 0, n_c == 0 or n_p == 0 returns R4R_OK, enqueues nothing and leaves the outputs untouched.  Every refusal
+ * precedes the first launch and the first dereference; a short workspace is R4R_ERR_WORKSPACE.  Nothing allocates,
+ * nothing synchronises.  The head lives in LDS (W in MFMA fragment order, shared by the four waves of a workgroup); above
+ * 64 x 64 a scan needs more than 64 KiB of it, and each of the three calls raises that kernel's limit (once per
+ * device) before its FIRST launch -- where the runtime refuses that, the call returns R4R_ERR_LAUNCH, has launched
+ * nothing and has written no output.
+ *
+ * r4r_topk_pfm: out_ids / out_scores [n_q, K].  Two launches (an MFMA scan whose A operand is W, read from LDS, and whose
+ *   B operand is formed in registers; r4r_topk_dot's merge), or one when the catalogue is a single chunk.  The workspace
+ *   holds the chunks' partial lists in r4r_topk_dot's layout.
+ * r4r_pair_pfm: the same expression for n explicit pairs (q_idx[p], c_idx[p]) -> out[p].
+ * r4r_rank_pfm: r4r_rank_dot's semantics exactly.  out_score[p] has r4r_pair_pfm's bits; out_rank[p] counts the
+ *   candidates ahead of target t_idx[p] for query row q_idx[p] that are neither -inf / NaN nor on that ROW's exclusion
+ *   list; the target never counts against itself; a target whose own score is -inf or NaN gets -1.  Integer atomics
+ *   only: equal for every chunk, tiling and grouping.  No workspace.
+ * ---------------------------------------------------------------------- */
+size_t r4r_topk_pfm_ws_bytes(int64_t n_q, int64_t n_c, int K, int64_t chunk);
+int r4r_topk_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *g, const float *e,
+                 int H, int G, int M, const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws,
+                 size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_pair_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *g, const float *e,
+                 int H, int G, int M, const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream);
+int r4r_rank_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                 const float *c_bias, const float *W, const float *b, const float *s, const float *g, const float *e,
+                 int H, int G, int M, const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
+                 const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ Layout
                    ranking_metrics) over csrc/topk.hip; the same for the ReLU-sum heads of deepconn++ and NeuMF
                    (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip, and for NARRE's
                    product-MLP head (NarreCatalogue, narre_catalogue_limits) over csrc/topk_hmlp.hip, and for the TransNets'
-                   ReLU-FM head (TransNetCatalogue, transnet_catalogue_limits, fold_transnet_head) over csrc/topk_rfm.hip
+                   ReLU-FM head (TransNetCatalogue, transnet_catalogue_limits, fold_transnet_head) over csrc/topk_rfm.hip,
+                   and for MF's product-FM head (MFCatalogue, mf_catalogue_limits, fold_mf_head) over csrc/topk_pfm.hip
 """
 __version__ = '0.1.0'
 
@@ -39,4 +40,5 @@ from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # 
 from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
 from .recommend import NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
 from .recommend import TransNetCatalogue, fold_transnet_head, transnet_catalogue_limits  # noqa: E402,F401
+from .recommend import MFCatalogue, fold_mf_head, mf_catalogue_limits  # noqa: E402,F401
 from .eval import eval_catalogue  # noqa: E402,F401

@@ -49,8 +49,21 @@ term of y = W h + b (``fold_transnet_head``), so
 
 is ranked by r4r_topk_rfm / r4r_rank_rfm (csrc/topk_rfm.hip: the same scan with relu(q + c) as the B operand and squares
 in the epilogue) through ``TransNetCatalogue`` (``transnet_catalogue_limits`` has the limits) and
-``eval.eval_catalogue(catalogue=TransNetCatalogue(...))``; ``main``'s hooks still refuse them.  MF (MF.py:45-49, an FM
-over [mlp | user * item]) stays refused: it needs product columns and about 2 L rows of y.
+``eval.eval_catalogue(catalogue=TransNetCatalogue(...))``; ``main``'s hooks still refuse them.
+
+MF (MF.py:45-49) scores a pair with an FM over [Linear -> ReLU -> Linear of [user | item] | user * item].  The first
+Linear separates again, the FM's squares are signed squares of y = W [h ; m] + b with h = relu(.) and m = user * item, and
+what is left is per column of x = [h ; m] -- the square of a product column is that column's own x^2
+(``fold_mf_head``) -- so
+
+    score(u, i) = sum_j s_j y_j^2 + sum_m x_m (g_m x_m + e_m) + user scalar + item scalar,
+    y = W x + b,   x = [relu(qa[u] + ca[i]) ; ue[u] * ie[i]]
+
+is ranked by r4r_topk_pfm / r4r_rank_pfm (csrc/topk_pfm.hip: the scan with product columns, a column sum carried by the
+lanes that form x, and the 2 L x 2 L head resident in LDS) through ``MFCatalogue`` (``mf_catalogue_limits`` has the limits)
+and ``eval.eval_catalogue(catalogue=MFCatalogue(...))``.  ``main``'s hooks still refuse MF, ``catalogue_limits`` and
+``_REFUSED`` still give the reason ``Catalogue`` cannot rank it, and ``transnet_catalogue_limits`` still says that no class
+serves it: those texts are pinned by tests and predate ``MFCatalogue``.
 
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
@@ -836,6 +849,156 @@ class TransNetCatalogue(Catalogue):
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.s),
                 ptr(self.l), self.H, self.P, self.M)
+
+
+PFM_MAX_L = 64                      # r4r_topk_pfm: H <= 64, G <= 64, M <= 128
+
+
+def mf_catalogue_limits(hyper_params):
+    """None when ``MFCatalogue`` can rank this configuration, else the reason it cannot.  (The sibling functions'
+    texts for MF -- ``transnet_catalogue_limits``' "no class serves it" among them -- predate this class and are kept as
+    they are.)"""
+    mt = hyper_params['model_type']
+    if mt in SUPPORTED:
+        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
+    if mt in ('deepconn++', 'NeuMF'):
+        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
+    if mt == 'NARRE':
+        return 'model_type %r has a product-MLP head: NarreCatalogue serves it' % (mt,)
+    if mt in ('transnet', 'transnet++'):
+        return 'model_type %r has a ReLU-FM head: TransNetCatalogue serves it' % (mt,)
+    if mt != 'MF':
+        return 'model_type %r has no product-FM form' % (mt,)
+    if _latent_size(hyper_params) > PFM_MAX_L:
+        return 'latent_size %d > %d' % (_latent_size(hyper_params), PFM_MAX_L)
+    return None
+
+
+def fold_mf_head(params, hyper_params, side, emb, bias=None, dtype=torch.float32, head=True):
+    """One side of MF's eval-mode score, final([projection(cat(ue, ie)) | ue * ie]) + the three biases (MF.py:45-50,
+    common_pytorch_models.py:41-57), as the rows of the product-FM form (include/r4r.h):
+
+        score(u, i) = sum_{j<M} s_j y_j^2 + sum_{m<D} x_m (g_m x_m + e_m) + q_bias[u] + c_bias[i]
+        y = W x + b,   x_m = relu(qa[u][m] + ca[i][m])  m < H = L,   x_{H+f} = ue[u][f] ie[i][f]  f < G = L
+
+    With W1, b1 = projection.1, W3, b3 = projection.3, V, lw, lb = final.V [2 L, L], final.lin.weight[0], final.lin.bias,
+    Va = V[:L], Vb = V[L:], la = lw[:L], lm = lw[L:], sig_a = sum_f Va[.][f]^2, sig_b likewise over Vb, D = M = 2 L:
+
+        qa = W1[:, :L] ue + b1      ca = W1[:, L:] ie
+        rows       W over h              W over m    b              s
+        f < L      (W3^T Va)^T           Vb^T        b3^T Va       +1/2      the FM's (x V)_f, squared
+        L + k      diag(sqrt(sig_a)) W3  0           sqrt(sig_a) b3 -1/2     the FM's ir_k^2 (V^2)_k, ir = W3 h + b3
+        columns    e = [la^T W3 | lm]    g = [0 | -1/2 sig_b]                the linear term, and m_k^2 (V^2)_{L+k}
+        q_bias = user_bias + global_bias + lb + la . b3        c_bias = item_bias
+
+    Dropout is the identity in eval mode.  ``params``: the model's parameters by state_dict key; ``emb`` [n, L]: the
+    side's embedding rows; ``bias`` [n]: its rows of user_bias / item_bias (None: zeros).
+    -> side 'user': (rows [n, 2 L] = [qa | ue], q_bias [n], (W [2 L, 2 L], b [2 L], s [2 L], g [2 L], e [2 L])), the last
+    None with ``head=False`` (the head does not depend on the rows);  side 'item': (rows [n, 2 L] = [ca | ie], c_bias [n]).
+    Plain torch on whatever device the inputs live on, computed in float64 and rounded once to ``dtype``."""
+    if side not in ('user', 'item'):
+        raise ValueError("fold_mf_head: side must be 'user' or 'item', got %r" % (side,))
+    if hyper_params['model_type'] != 'MF':
+        raise ValueError('fold_mf_head: no product-FM form for %r' % (hyper_params['model_type'],))
+    f64 = lambda t: t.detach().to(torch.float64)
+    W1, b1, W3, b3, V, lw, lb, gb = (f64(params[k]) for k in (
+        'projection.1.weight', 'projection.1.bias', 'projection.3.weight', 'projection.3.bias', 'final.V',
+        'final.lin.weight', 'final.lin.bias', 'global_bias'))
+    if emb.dim() != 2 or (bias is not None and (bias.dim() != 1 or bias.shape[0] != emb.shape[0])):
+        raise ValueError('fold_mf_head: emb [n, L] and bias [n] do not match')
+    n, L = emb.shape
+    lw = lw.reshape(-1)
+    if tuple(W1.shape) != (L, 2 * L) or tuple(W3.shape) != (L, L) or tuple(V.shape) != (2 * L, L) or lw.numel() != 2 * L:
+        raise ValueError('fold_mf_head: projection %s %s / final.V %s do not match latent width %d'
+                         % (tuple(W1.shape), tuple(W3.shape), tuple(V.shape), L))
+    user = side == 'user'
+    x = f64(emb)
+    sc = torch.zeros(n, dtype=torch.float64, device=emb.device) if bias is None else f64(bias)
+    la, lm = lw[:L], lw[L:]
+    if not user:
+        return torch.cat([x @ W1[:, L:].T, x], 1).to(dtype), sc.to(dtype)
+    rows = torch.cat([x @ W1[:, :L].T + b1, x], 1)
+    sc = sc + gb.reshape(()) + lb.reshape(()) + la @ b3
+    if not head:
+        return rows.to(dtype), sc.to(dtype), None
+    Va, Vb = V[:L], V[L:]
+    root = (Va * Va).sum(1).sqrt()
+    zero = torch.zeros((L, L), dtype=torch.float64, device=emb.device)
+    W = torch.cat([torch.cat([(W3.T @ Va).T, Vb.T], 1), torch.cat([root[:, None] * W3, zero], 1)], 0)
+    b = torch.cat([b3 @ Va, root * b3])
+    s = torch.cat([torch.full((L,), 0.5), torch.full((L,), -0.5)]).to(torch.float64).to(emb.device)
+    g = torch.cat([zero[0], -0.5 * (Vb * Vb).sum(1)])
+    e = torch.cat([la @ W3, lm])
+    return rows.to(dtype), sc.to(dtype), tuple(t.to(dtype).contiguous() for t in (W, b, s, g, e))
+
+
+class MFCatalogue(Catalogue):
+    """``Catalogue``'s surface (``refresh``, ``recommend``, ``score_pairs``, ``rank``; the same return types, devices,
+    (-1, -inf) fill and argument checks: the three calls are ``Catalogue``'s own, over this class's ``_head``) for MF,
+    ranked by r4r_topk_pfm / r4r_pair_pfm / r4r_rank_pfm.  ``fold_mf_head`` has the table.
+
+    ``refresh()`` flushes the engine's pending row updates (the blocked sweeps of the native step leave table rows
+    behind the schedule until ``flush()``) and caches the item side (``c`` = [ca | ie], ``c_bias`` = item_bias with -inf
+    in ineligible rows, the head ``W``, ``b``, ``s``, ``g``, ``e``): the item table through one small matmul, no tower
+    and no document.  The query side is computed per call from the current weights, after the same flush.  A pass leaves
+    the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks do not reach this class (they still
+    refuse MF, and ``transnet_catalogue_limits`` still says that no class serves it: both texts are older than this
+    class); MF is served here and through ``eval_catalogue(catalogue=MFCatalogue(...))``."""
+
+    _form = 'pfm'
+
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None):
+        why = mf_catalogue_limits(hyper_params)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
+        self.mt = hyper_params['model_type']
+        self.dev = next(model.parameters()).device
+        if self.dev.type != 'cuda':
+            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
+                               'CPU fallback')
+        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
+        self.eligible = eligible_items(hyper_params, train_reader, candidates)
+        L = _latent_size(hyper_params)
+        self.H, self.G, self.M = L, L, 2 * L
+        self.D = self.H + self.G
+        self.n_c = int(model.item_bias.numel())                # candidate rows the kernel walks: the item table as it is
+        self._seen = None
+        self.refresh()
+
+    def _params(self):
+        return {k: v.detach() for k, v in self.model.named_parameters()}
+
+    def _flush(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+
+    def refresh(self):
+        self._flush()
+        m, P = self.model, self._params()
+        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
+        mask[torch.from_numpy(self.eligible).to(self.dev)] = True
+        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        with torch.no_grad():
+            c, cb = fold_mf_head(P, self.hp, 'item', m.item_embedding.weight.detach(), bias=m.item_bias.detach())
+            self.c, self.c_bias = c.contiguous(), torch.where(mask, cb, ninf)
+            # the head is the user side's; the fold of zero user rows yields it
+            none = torch.zeros((0, self.H), dtype=torch.float32, device=self.dev)
+            self.W, self.b, self.s, self.g, self.e = fold_mf_head(P, self.hp, 'user', none)[2]
+
+    def _queries(self, u_host):
+        """(q [n, 2 L], q_bias [n]) of the requested users from the current weights."""
+        self._flush()
+        m = self.model
+        u = u_host.to(self.dev)
+        with torch.no_grad():
+            q, qb, _ = fold_mf_head(self._params(), self.hp, 'user', m.user_embedding.weight.detach()[u],
+                                    bias=m.user_bias.detach()[u], head=False)
+        return q.contiguous(), qb.contiguous()
+
+    def _head(self, q, n, qb):
+        return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.s),
+                ptr(self.g), ptr(self.e), self.H, self.G, self.M)
 
 
 def hook_limits(hyper_params):
