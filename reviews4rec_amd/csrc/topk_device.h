@@ -4,9 +4,10 @@
 //           search; the three scalar kernels (pairs, rank targets, the exclusion correction) over a score HEAD
 //   host    the chunk rule, the workspace size, the argument checks of the three call kinds, the plan of a call, the
 //           merge of the chunks' partial lists, the launches of the scalar kernels
-// The six streaming kernels are each file's own.  They call chunk_geom and is_excluded, which leave
-// their instructions as they were (profiles/topk_shared_isa.txt); clearing and writing back the lists, what a ranked
-// pair waits for and the wave sum of its counters did not, and stay written out in each kernel.
+// The streaming kernels are each file's own, but for topk_hmlp.hip's and topk_rfm.hip's, which are one text in
+// topk_mfma_device.h.  They call chunk_geom and is_excluded, which leave their instructions as they
+// were (profiles/topk_shared_isa.txt); clearing and writing back the lists, what a ranked pair waits for and the wave
+// sum of its counters did not, and stay written out in each kernel.
 //
 // A score head is a trivially copyable struct, passed to kernels by value:
 //   q, c, n_c, c_stride             the two tables (rows of width() columns)

@@ -8,7 +8,8 @@
 // The ReLU sits behind an H x D matrix product per pair: matrix-core work, but not topk.hip's shape.  Here the A operand
 // of v_mfma_f32_16x16x4_f32 is the head's matrix W, shared by every pair, and the B operand is formed in registers:
 // rows = hidden units, columns = 16 candidates, k = the input width.
-// Launch 1, hmlp_scan_kernel: one WAVE per workgroup = (tile of HMLP_QT queries) x (chunk of candidates), no barrier.
+// Launch 1, mfma_scan_kernel<HmlpWave> (topk_mfma_device.h has the stream): one WAVE per workgroup = (tile of HMLP_QT
+// queries) x (chunk of candidates), no barrier.
 //   A  lane l supplies W[16 ht + (l & 15)][4 t + (l >> 4)] for MFMA (ht, t): loaded once, kept for the whole chunk.
 //   B  lane l loads c[slab + (l & 15)][4 t + (l >> 4)] (one dword per lane and t, as topk.hip does and for its reason) and
 //      multiplies it by its query's q[u][4 t + (l >> 4)]: x, one v_mul_f32 per B fragment.  The tile's queries reuse the
@@ -22,12 +23,14 @@
 // topk_device.h's scalar kernels (pairs, rank targets, the exclusion correction) over this file's HmlpHead compute
 // hmlp_pair_score: the chain above written out.  v_mfma_f32_16x16x4_f32 is bitwise that chain over m (topk.hip), zero
 // rows of W give z = 0 and w = 0 adds nothing, so a score's bits depend on its own pair only.
-// This file has the two streams and the head; the scalar kernels, the chunk rule, the argument checks and the plan of a
-// call are topk_device.h's, shared with topk.hip and topk_relu.hip.
+// This file has the chain, the head and the wave; the two streams and the host sequence of a call are
+// topk_mfma_device.h's, shared with topk_rfm.hip; the scalar kernels, the chunk rule, the argument checks and the plan
+// of a call are topk_device.h's, shared with every form.
 #include <math.h>
 
 #include "common.h"
 #include "topk_device.h"
+#include "topk_mfma_device.h"
 
 namespace r4r {
 namespace {
@@ -62,7 +65,7 @@ __device__ __forceinline__ float hmlp_pair_score(const float *q, const float *c,
     return (((h[0] + h[1]) + (h[2] + h[3])) + cb) + qb;
 }
 
-// The head of this form (topk_device.h); the two streams read its fields
+// The head of this form (topk_device.h); topk_mfma_device.h's two streams read its fields
 struct HmlpHead {
     const float *q, *q_bias, *c, *c_bias, *W, *b, *w;
     int64_t n_c, c_stride;
@@ -89,8 +92,10 @@ struct HmlpHead {
 
 // What a wave keeps for its whole chunk: the head (A fragments; b and w in the accumulator layout) and the column of
 // each B fragment.  KT: MFMAs over the input width (D <= 4 KT), HT: 16-row tiles of hidden units (H <= 16 HT).
-template <int KT, int HT>
+template <int KT_, int HT>
 struct HmlpWave {
+    typedef HmlpHead Head;
+    static constexpr int KT = KT_, QT = HMLP_QT;
     float wf[HT][KT];          // W[16 ht + row][4 t + kq]; zero beyond H and beyond D
     float bj[HT][4], wj[HT][4];// b / w of hidden unit 16 ht + 4 kq + r; zero beyond H (and for a NULL b)
     int jo[KT];                // the column lane (., kq) reads for MFMA t, clamped into the row
@@ -175,243 +180,36 @@ struct HmlpWave {
     }
 };
 
-// the B fragments of one slab in flight: c[slab + row][4 t + kq] and the row's bias
-template <int KT>
-struct HmlpSlab {
-    float bn[KT], cbn;
-
-    __device__ __forceinline__ void clear() {
-        cbn = 0.f;
-#pragma unroll
-        for (int t = 0; t < KT; ++t) bn[t] = 0.f;
-    }
-    // Unconditional loads from clamped addresses: a column past D reads column D - 1 and is zeroed in `take`, a row of
-    // the NEXT chunk is read and ignored, a row past the table reads the table's last row.
-    __device__ __forceinline__ void load(const HmlpHead &a, const int (&jo)[KT], int64_t i) {
-        const int64_t ic = i < a.n_c ? i : a.n_c - 1;
-        const float *src = a.c + ic * a.c_stride;
-        if (a.D > 0) {
-#pragma unroll
-            for (int t = 0; t < KT; ++t) bn[t] = src[jo[t]];
-        }
-        if (a.c_bias != nullptr) cbn = a.c_bias[ic];
-    }
-    __device__ __forceinline__ void take(int D, int kq, float (&bf)[KT], float &cb) const {
-        cb = cbn;
-#pragma unroll
-        for (int t = 0; t < KT; ++t) bf[t] = (4 * t + kq < D) ? bn[t] : 0.f;
-    }
-};
-
-struct HmlpScanArgs {
-    HmlpHead h;
-    const int64_t *excl_off, *excl_ids;
-    float *out_scores;        // [n_q, parts, K]
-    int64_t *out_ids;
-    int64_t n_q, chunk, parts, tiles;
-    int K;
-};
-
-template <int KT, int HT>
-__global__ __launch_bounds__(64) void hmlp_scan_kernel(HmlpScanArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char hmlp_lds[];
-    constexpr int QT = HMLP_QT;
-    const int K = a.K, D = a.h.D;
-    float *sc = reinterpret_cast<float *>(hmlp_lds);           // [QT][K]
-    int *id = reinterpret_cast<int *>(sc + QT * K);            // [QT][K]  candidate - chunk begin
-
-    const int lane = threadIdx.x;
-    const ChunkGeom g = chunk_geom(a.tiles, QT, a.chunk, a.h.n_c);
-    const int64_t u0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
-
-    for (int i = lane; i < QT * K; i += 64) { sc[i] = -INFINITY; id[i] = fill_id<int>::value; }
-
-    HmlpWave<KT, HT> wv;
-    wv.init(a.h, lane);
-    const int row = wv.row, kq = wv.kq;
-    float qf[QT][KT], qb[QT], thr[QT];                         // qb, thr: wave-uniform
-#pragma unroll
-    for (int s = 0; s < QT; ++s) {
-        const int64_t u = u0 + s;
-        const bool exists = u < a.n_q;
-        const int64_t uc = exists ? u : a.n_q - 1;
-        wv.query(a.h, a.h.q + uc * D, exists, qf[s]);
-        qb[s] = a.h.q_bias != nullptr ? a.h.q_bias[uc] : 0.f;
-        thr[s] = exists ? -INFINITY : INFINITY;                // rows past n_q never survive
-    }
-    wave_lds_fence();
-
-    HmlpSlab<KT> nx;
-    float bf[KT], cb;
-    nx.clear();
-    if (c_begin < c_end) nx.load(a.h, wv.jo, c_begin + row);
-    nx.take(D, kq, bf, cb);
-    for (int64_t base = c_begin; base < c_end; base += 16) {
-        if (base + 16 < c_end) nx.load(a.h, wv.jo, base + 16 + row);
-        float sv[QT];
-        wv.scores(bf, qf, cb, sv);
-        const bool live = kq == 0 && base + row < c_end;       // one lane per candidate offers it
-        bool any = false;
-#pragma unroll
-        for (int s = 0; s < QT; ++s) {
-            sv[s] = sv[s] + qb[s];
-            any |= live && sv[s] > thr[s];
-        }
-        if (__ballot(any) != 0) {
-            // survivors, one at a time (wave-uniform control flow from here on)
-#pragma unroll
-            for (int s = 0; s < QT; ++s) {
-                unsigned long long m = __ballot(live && sv[s] > thr[s]);
-                while (m) {
-                    const int src = __builtin_ctzll(m);
-                    m &= m - 1;
-                    const float v = lane_value(sv[s], src);
-                    const int64_t ci = base + src;             // (src < 16: a lane of kq == 0)
-                    if (!(v > thr[s])) continue;               // (an earlier survivor raised the bar)
-                    if (is_excluded(a.excl_off, a.excl_ids, u0 + s, ci)) continue;
-                    thr[s] = list_insert<int>(sc + s * K, id + s * K, K, v, (int)(ci - c_begin), lane);
-                }
-            }
-        }
-        nx.take(D, kq, bf, cb);
-    }
-
-    // the partial lists, filled up with (-inf, -1)
-    for (int ql = 0; ql < QT; ++ql) {
-        const int64_t u = u0 + ql;
-        if (u >= a.n_q) break;
-        const int64_t o = (u * a.parts + g.part) * K;
-        for (int p = lane; p < K; p += 64) {
-            const int ci = id[ql * K + p];
-            a.out_scores[o + p] = sc[ql * K + p];              // (-inf in an unused slot)
-            a.out_ids[o + p] = ci != fill_id<int>::value ? c_begin + ci : (int64_t)-1;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// r4r_rank_hmlp: r4r_rank_dot's three launches over this file's chain.
-//   A  rank_target_kernel<HmlpHead>   one thread per pair: the scalar chain -> out_score[p]; out_rank[p] = 0, or -1 for
-//                                     a target whose own score is -inf or NaN (never touched again)
-//   B  rank_hmlp_scan_kernel          the scan's stream over a tile of HMLP_QT PAIRS (query rows gathered through q_idx)
-//                                     and a chunk of candidates; every score is compared with the pair's target in
-//                                     registers and counted; one 64-bit integer atomic per (pair, chunk)
-//   C  rank_excl_kernel<HmlpHead>     only with exclusions: B counted the excluded ids too; one wave per pair recomputes
-//                                     the scalar chain of its query row's excluded ids and subtracts those that were ahead
-// (A and C: topk_device.h.)
-struct HmlpRankArgs {
-    HmlpHead h;
-    const int64_t *q_idx, *t_idx;
-    const float *t_score;     // out_score, written by launch A
-    int64_t *out_rank;
-    int64_t n_p, chunk, tiles;
-};
-
-template <int KT, int HT>
-__global__ __launch_bounds__(64) void rank_hmlp_scan_kernel(HmlpRankArgs a) {
-    constexpr int PT = HMLP_QT;
-    const int D = a.h.D;
-    const int lane = threadIdx.x;
-    const ChunkGeom g = chunk_geom(a.tiles, PT, a.chunk, a.h.n_c);
-    const int64_t p0 = g.first, c_begin = g.c_begin, c_end = g.c_end;
-    const int c_len = g.c_len();
-
-    HmlpWave<KT, HT> wv;
-    wv.init(a.h, lane);
-    const int row = wv.row, kq = wv.kq;
-    // Of each pair: its query row, its query bias, its target's score and its target's id relative to the chunk (-1:
-    // before it, so no tie is ahead; INT_MAX: behind it, so every tie is).  A pair past n_p or at -1 waits for a score
-    // above +inf: it counts nothing.  (All wave-uniform.)
-    float qf[PT][KT], qb[PT], ts[PT];
-    int trel[PT], cnt[PT];
-#pragma unroll
-    for (int s = 0; s < PT; ++s) {
-        const int64_t p = p0 + s;
-        const bool exists = p < a.n_p;
-        const int64_t pc = exists ? p : a.n_p - 1;
-        const int64_t u = a.q_idx[pc];
-        wv.query(a.h, a.h.q + u * D, exists, qf[s]);
-        qb[s] = a.h.q_bias != nullptr ? a.h.q_bias[u] : 0.f;
-        const float st = a.t_score[pc];
-        const int64_t d = a.t_idx[pc] - c_begin;
-        const bool ranked = exists && st > -INFINITY;          // (false for NaN)
-        ts[s] = ranked ? st : INFINITY;
-        trel[s] = !ranked || d < 0 ? -1 : (d > 0x7fffffff ? 0x7fffffff : (int)d);
-        cnt[s] = 0;
-    }
-
-    HmlpSlab<KT> nx;
-    float bf[KT], cb;
-    nx.clear();
-    if (c_begin < c_end) nx.load(a.h, wv.jo, c_begin + row);
-    nx.take(D, kq, bf, cb);
-    for (int64_t base = c_begin; base < c_end; base += 16) {
-        if (base + 16 < c_end) nx.load(a.h, wv.jo, base + 16 + row);
-        float sv[PT];
-        wv.scores(bf, qf, cb, sv);
-        const int rel = (int)(base - c_begin) + row;
-        const bool live = kq == 0 && rel < c_len;              // one lane per candidate counts it
-#pragma unroll
-        for (int s = 0; s < PT; ++s)
-            cnt[s] += (live && ahead<int>(sv[s] + qb[s], rel, ts[s], trel[s])) ? 1 : 0;     // (false for a NaN score)
-        nx.take(D, kq, bf, cb);
-    }
-
-    // lane s adds pair s's count over the wave to its rank -- one atomic instruction per wave
-    int mine = 0;
-#pragma unroll
-    for (int s = 0; s < PT; ++s) {
-        int v = cnt[s];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-        if (lane == s) mine = v;
-    }
-    // (mine > 0 only for a pair below n_p whose target is ranked: the others wait for +inf)
-    if (lane < PT && mine > 0)
-        atomicAdd(reinterpret_cast<unsigned long long *>(a.out_rank + p0 + lane), (unsigned long long)mine);
-}
-
-template <int KT, int HT>
-int launch_hmlp_scan(const HmlpScanArgs &a, hipStream_t st) {
-    const size_t lds = (size_t)HMLP_QT * (size_t)a.K * 8;
-    hipLaunchKernelGGL((hmlp_scan_kernel<KT, HT>), dim3((unsigned)(a.parts * a.tiles)), dim3(64), lds, st, a);
-    return check_launch("hmlp_scan_kernel");
-}
-
-template <int KT, int HT>
-int launch_hmlp_rank(const HmlpRankArgs &a, int64_t parts, hipStream_t st) {
-    hipLaunchKernelGGL((rank_hmlp_scan_kernel<KT, HT>), dim3((unsigned)(parts * a.tiles)), dim3(64), 0, st, a);
-    return check_launch("rank_hmlp_scan_kernel");
-}
-
 // KT by D (2, 4, 8, 16 MFMAs over the input width), HT by H (1 .. 4 tiles of 16 hidden units)
 #define HMLP_DISPATCH(FN, D, H, ...)                                                   \
     do {                                                                               \
         const int kt_ = (D) <= 8 ? 2 : (D) <= 16 ? 4 : (D) <= 32 ? 8 : 16;             \
         const int ht_ = (H) <= 16 ? 1 : (H) <= 32 ? 2 : (H) <= 48 ? 3 : 4;             \
         switch (kt_ * 8 + ht_) {                                                       \
-        case 2 * 8 + 1: return FN<2, 1>(__VA_ARGS__);                                  \
-        case 2 * 8 + 2: return FN<2, 2>(__VA_ARGS__);                                  \
-        case 2 * 8 + 3: return FN<2, 3>(__VA_ARGS__);                                  \
-        case 2 * 8 + 4: return FN<2, 4>(__VA_ARGS__);                                  \
-        case 4 * 8 + 1: return FN<4, 1>(__VA_ARGS__);                                  \
-        case 4 * 8 + 2: return FN<4, 2>(__VA_ARGS__);                                  \
-        case 4 * 8 + 3: return FN<4, 3>(__VA_ARGS__);                                  \
-        case 4 * 8 + 4: return FN<4, 4>(__VA_ARGS__);                                  \
-        case 8 * 8 + 1: return FN<8, 1>(__VA_ARGS__);                                  \
-        case 8 * 8 + 2: return FN<8, 2>(__VA_ARGS__);                                  \
-        case 8 * 8 + 3: return FN<8, 3>(__VA_ARGS__);                                  \
-        case 8 * 8 + 4: return FN<8, 4>(__VA_ARGS__);                                  \
-        case 16 * 8 + 1: return FN<16, 1>(__VA_ARGS__);                                \
-        case 16 * 8 + 2: return FN<16, 2>(__VA_ARGS__);                                \
-        case 16 * 8 + 3: return FN<16, 3>(__VA_ARGS__);                                \
-        default: return FN<16, 4>(__VA_ARGS__);                                        \
+        case 2 * 8 + 1: return FN<HmlpWave<2, 1>>(__VA_ARGS__);                        \
+        case 2 * 8 + 2: return FN<HmlpWave<2, 2>>(__VA_ARGS__);                        \
+        case 2 * 8 + 3: return FN<HmlpWave<2, 3>>(__VA_ARGS__);                        \
+        case 2 * 8 + 4: return FN<HmlpWave<2, 4>>(__VA_ARGS__);                        \
+        case 4 * 8 + 1: return FN<HmlpWave<4, 1>>(__VA_ARGS__);                        \
+        case 4 * 8 + 2: return FN<HmlpWave<4, 2>>(__VA_ARGS__);                        \
+        case 4 * 8 + 3: return FN<HmlpWave<4, 3>>(__VA_ARGS__);                        \
+        case 4 * 8 + 4: return FN<HmlpWave<4, 4>>(__VA_ARGS__);                        \
+        case 8 * 8 + 1: return FN<HmlpWave<8, 1>>(__VA_ARGS__);                        \
+        case 8 * 8 + 2: return FN<HmlpWave<8, 2>>(__VA_ARGS__);                        \
+        case 8 * 8 + 3: return FN<HmlpWave<8, 3>>(__VA_ARGS__);                        \
+        case 8 * 8 + 4: return FN<HmlpWave<8, 4>>(__VA_ARGS__);                        \
+        case 16 * 8 + 1: return FN<HmlpWave<16, 1>>(__VA_ARGS__);                      \
+        case 16 * 8 + 2: return FN<HmlpWave<16, 2>>(__VA_ARGS__);                      \
+        case 16 * 8 + 3: return FN<HmlpWave<16, 3>>(__VA_ARGS__);                      \
+        default: return FN<HmlpWave<16, 4>>(__VA_ARGS__);                              \
         }                                                                              \
     } while (0)
 
-int dispatch_hmlp_scan(const HmlpScanArgs &a, hipStream_t st) { HMLP_DISPATCH(launch_hmlp_scan, a.h.D, a.h.H, a, st); }
-int dispatch_hmlp_rank(const HmlpRankArgs &a, int64_t parts, hipStream_t st) {
-    HMLP_DISPATCH(launch_hmlp_rank, a.h.D, a.h.H, a, parts, st);
+int dispatch_hmlp_scan(const MfmaScanArgs<HmlpHead> &a, hipStream_t st) {
+    HMLP_DISPATCH(launch_mfma_scan, a.h.D, a.h.H, "hmlp_scan_kernel", a, st);
+}
+int dispatch_hmlp_rank(const MfmaRankArgs<HmlpHead> &a, int64_t parts, hipStream_t st) {
+    HMLP_DISPATCH(launch_mfma_rank, a.h.D, a.h.H, "rank_hmlp_scan_kernel", a, parts, st);
 }
 
 inline HmlpHead hmlp_head(const float *q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
@@ -435,48 +233,23 @@ extern "C" int r4r_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, c
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *excl_off, const int64_t *excl_ids, int K, int64_t chunk, void *ws, size_t ws_bytes,
                              int64_t *out_ids, float *out_scores, void *stream) {
-    HmlpScanArgs a;
-    a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
-    bool work;
-    int rc = topk_check("topk_hmlp", a.h, n_q, excl_off, excl_ids, K, chunk, out_ids, out_scores, &work);
-    if (rc != R4R_OK || !work) return rc;
-    ListsPlan p;
-    rc = topk_plan("topk_hmlp", n_q, n_c, K, chunk, HMLP_QT, HMLP_QT, ws, ws_bytes, out_ids, out_scores, &p);
-    if (rc != R4R_OK) return rc;
-    a.excl_off = excl_off; a.excl_ids = excl_ids;
-    a.out_scores = p.scan_scores; a.out_ids = p.scan_ids;
-    a.n_q = n_q; a.chunk = p.chunk; a.parts = p.parts; a.tiles = p.tiles; a.K = K;
-    hipStream_t st = as_stream(stream);
-    return topk_finish(p, dispatch_hmlp_scan(a, st), n_q, K, out_ids, out_scores, st);
+    const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    return mfma_topk_call("topk_hmlp", h, HMLP_QT, HMLP_QT, dispatch_hmlp_scan, n_q, excl_off, excl_ids, K, chunk, ws,
+                          ws_bytes, out_ids, out_scores, stream);
 }
 
 extern "C" int r4r_pair_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *q_idx, const int64_t *c_idx, int64_t n, float *out, void *stream) {
     const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
-    bool work;
-    const int rc = pair_check("pair_hmlp", h, n_q, q_idx, c_idx, n, out, &work);
-    if (rc != R4R_OK || !work) return rc;
-    return launch_pairs(h, q_idx, c_idx, n, out, as_stream(stream));
+    return mfma_pair_call("pair_hmlp", h, n_q, q_idx, c_idx, n, out, stream);
 }
 
 extern "C" int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
                              const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
                              const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
                              const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream) {
-    HmlpRankArgs a;
-    a.h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
-    bool work;
-    int rc = rank_check("rank_hmlp", a.h, n_q, q_idx, t_idx, n_p, excl_off, excl_ids, chunk, out_rank, out_score, &work);
-    if (rc != R4R_OK || !work) return rc;
-    ChunkPlan p;
-    rc = rank_plan("rank_hmlp", n_p, n_c, chunk, HMLP_QT, HMLP_QT, &p);
-    if (rc != R4R_OK) return rc;
-    a.q_idx = q_idx; a.t_idx = t_idx;
-    a.t_score = out_score; a.out_rank = out_rank;
-    a.n_p = n_p; a.chunk = p.chunk; a.tiles = p.tiles;
-    hipStream_t st = as_stream(stream);
-    rc = launch_rank_targets(a.h, q_idx, t_idx, n_p, out_score, out_rank, st);
-    if (rc != R4R_OK) return rc;
-    return rank_finish(a.h, dispatch_hmlp_rank(a, p.parts, st), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
+    const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    return mfma_rank_call("rank_hmlp", h, HMLP_QT, HMLP_QT, dispatch_hmlp_rank, n_q, q_idx, t_idx, n_p, excl_off, excl_ids,
+                          chunk, out_rank, out_score, stream);
 }

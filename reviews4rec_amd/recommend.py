@@ -91,6 +91,24 @@ def _latent_size(hyper_params):
     return int(hyper_params.get('latent_size', 10))        # (the default of main.native_step_limits)
 
 
+# Who serves which model types, in the order the classes came: each later ``*_catalogue_limits`` refuses the types of
+# the classes before its own with these words.
+_SERVED = (
+    (SUPPORTED, 'is a dot product plus two scalars: Catalogue serves it'),
+    (('deepconn++', 'NeuMF'), 'has a ReLU-sum head: ReluCatalogue serves it'),
+    (('NARRE',), 'has a product-MLP head: NarreCatalogue serves it'),
+    (('transnet', 'transnet++'), 'has a ReLU-FM head: TransNetCatalogue serves it'),
+)
+
+
+def _served_before(mt, n):
+    """The refusal of a model type that one of the first ``n`` classes serves, else None."""
+    for types, what in _SERVED[:n]:
+        if mt in types:
+            return 'model_type %r %s' % (mt, what)
+    return None
+
+
 def catalogue_limits(hyper_params):
     """None when ``Catalogue`` can rank this configuration, else the reason it cannot."""
     mt = hyper_params['model_type']
@@ -165,8 +183,10 @@ class Catalogue:
     the engines' buffers, so nothing else is read back.  A pass leaves the training state where it found it: no
     dropout draw, no step count, no conv-rule step, no token buffer of the engine is touched."""
 
+    _limits = staticmethod(catalogue_limits)       # a subclass names its own
+
     def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
-        why = catalogue_limits(hyper_params)
+        why = self._limits(hyper_params)
         if why is not None:
             raise RuntimeError('reviews4rec_amd.recommend: ' + why)
         self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
@@ -178,18 +198,48 @@ class Catalogue:
                                'CPU fallback')
         self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
         self.eligible = eligible_items(hyper_params, train_reader, candidates)
-        self.D = {'bias_only': 0, 'MF_dot': _latent_size(hyper_params), 'deepconn': FM_RANK}[self.mt]
-        # candidate rows the kernel walks: the item tables as they are (MF: total_items + 1 rows), or one per item id
-        self.n_c = int(model.item_bias.numel()) if self.mt != 'deepconn' else self.n_items
+        self._shape()
         self._seen = None
         self.refresh()
 
+    def _shape(self):
+        """What describes the score's form (``D``; a subclass: ``H``, ``P``, ... as its ``_head`` passes them) and
+        ``n_c``, the candidate rows the kernel walks."""
+        self.D = {'bias_only': 0, 'MF_dot': _latent_size(self.hp), 'deepconn': FM_RANK}[self.mt]
+        # the item tables as they are (MF: total_items + 1 rows), or one per item id
+        self.n_c = int(self.model.item_bias.numel()) if self.mt != 'deepconn' else self.n_items
+
     # ------------------------------------------------------------------ the cache
+    def _flush(self):
+        if self.engine is not None and hasattr(self.engine, 'flush'):
+            self.engine.flush()
+
+    def _params(self):
+        return {k: v.detach() for k, v in self.model.named_parameters()}
+
+    def _eligible_rows(self):
+        """(elig, mask, ninf): the eligible ids on the device, the bool mask of their rows among the n_c candidates, and
+        a fresh float32 [n_c] of -inf (the c_bias of a row that is not eligible)."""
+        elig = torch.from_numpy(self.eligible).to(self.dev)
+        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
+        mask[elig] = True
+        return elig, mask, torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+
+    def _batches(self, ids):
+        """(sl, ids[sl]) over ``ids``, ``tower_batch`` at a time: token documents are dropped chunk by chunk."""
+        for s in range(0, len(ids), self.tower_batch):
+            sl = slice(s, s + self.tower_batch)
+            yield sl, ids[sl]
+
+    def _words(self):
+        """The word table the towers read."""
+        return self.model.word2vec.weight
+
     def _tower(self, tower, idx):
         """Eval-mode forward of a TextCNN tower (no dropout draw, no autograd): idx [n, T] -> latent [n, L]."""
         with torch.no_grad():
             conv = tower.convs[0]
-            pooled, _ = ops.textcnn_fwd_raw(idx, self.model.word2vec.weight, conv.weight.detach(), conv.bias.detach())
+            pooled, _ = ops.textcnn_fwd_raw(idx, self._words(), conv.weight.detach(), conv.bias.detach())
             return ops.linear(pooled, tower.fc.weight.detach(), tower.fc.bias.detach())
 
     def _documents(self, pool, ids):
@@ -208,24 +258,19 @@ class Catalogue:
         return fold_fm(fm.V, fm.lin.weight, fm.lin.bias, m.global_bias, latent, side)
 
     def refresh(self):
-        if self.engine is not None and hasattr(self.engine, 'flush'):
-            self.engine.flush()
+        self._flush()
         m = self.model
-        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
-        elig = torch.from_numpy(self.eligible).to(self.dev)
-        mask[elig] = True
-        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        elig, mask, ninf = self._eligible_rows()
         with torch.no_grad():
             if self.mt != 'deepconn':
                 self.c = m.item_embedding.weight.detach() if self.mt == 'MF_dot' else None      # in place, not copied
                 self.c_bias = torch.where(mask, m.item_bias.detach(), ninf)
                 return
             c = torch.zeros((self.n_c, FM_RANK), dtype=torch.float32, device=self.dev)
-            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
-                ids = self.eligible[s:s + self.tower_batch]                                       # dropped chunk by chunk
+            for sl, ids in self._batches(self.eligible):
                 vec, bias = self._fold(self._tower(m.item_conv, self._documents(self.reader.store.items, ids)), 'item')
-                c[elig[s:s + self.tower_batch]] = vec
-                ninf[elig[s:s + self.tower_batch]] = bias
+                c[elig[sl]] = vec
+                ninf[elig[sl]] = bias
             self.c, self.c_bias = c, ninf
 
     # ------------------------------------------------------------------ the query side
@@ -247,10 +292,8 @@ class Catalogue:
                 return q, (m.user_bias.detach()[u] + m.global_bias.detach()).contiguous()
             q = torch.empty((u.numel(), FM_RANK), dtype=torch.float32, device=self.dev)
             qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-            ids = u_host.numpy()
-            for s in range(0, len(ids), self.tower_batch):
-                docs = self._documents(self.reader.store.users, ids[s:s + self.tower_batch])
-                q[s:s + self.tower_batch], qb[s:s + self.tower_batch] = self._fold(self._tower(m.user_conv, docs), 'user')
+            for sl, ids in self._batches(u_host.numpy()):
+                q[sl], qb[sl] = self._fold(self._tower(m.user_conv, self._documents(self.reader.store.users, ids)), 'user')
             return q, qb
 
     @property
@@ -353,8 +396,9 @@ _NEUMF_STAGES = ('GMF', 'MLP', 'NeuMF')
 def relu_catalogue_limits(hyper_params):
     """None when ``ReluCatalogue`` can rank this configuration, else the reason it cannot."""
     mt = hyper_params['model_type']
-    if mt in SUPPORTED:
-        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
+    served = _served_before(mt, 1)
+    if served:
+        return served
     if mt not in ('deepconn++', 'NeuMF'):
         why = _REFUSED.get(mt)
         return 'model_type %r has no ReLU-sum form%s' % (mt, ': ' + why if why else '')
@@ -454,31 +498,15 @@ class ReluCatalogue(Catalogue):
     class for deepconn++ only; NeuMF is served here and through ``eval_catalogue(catalogue=ReluCatalogue(...))``."""
 
     _form = 'relu'
+    _limits = staticmethod(relu_catalogue_limits)
 
-    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
-        why = relu_catalogue_limits(hyper_params)
-        if why is not None:
-            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
-        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
-        self.mt = hyper_params['model_type']
-        self.kind = _relu_kind(hyper_params)
-        self.tower_batch = int(tower_batch)
-        self.dev = next(model.parameters()).device
-        if self.dev.type != 'cuda':
-            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
-                               'CPU fallback')
-        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
-        self.eligible = eligible_items(hyper_params, train_reader, candidates)
-        L = _latent_size(hyper_params)
+    def _shape(self):
+        self.kind = _relu_kind(self.hp)
+        L = _latent_size(self.hp)
         self.H, self.P = {'deepconn++': (L, 0), 'MLP': (L, 0), 'NeuMF': (L, L), 'GMF': (0, L)}[self.kind]
         self.D = self.H + self.P
-        # candidate rows the kernel walks: one per item id (deepconn++), or the item tables as they are (total_items + 1)
-        self.n_c = self.n_items if self.kind == 'deepconn++' else int(model.item_bias.numel())
-        self._seen = None
-        self.refresh()
-
-    def _params(self):
-        return {k: v.detach() for k, v in self.model.named_parameters()}
+        # one row per item id (deepconn++), or the item tables as they are (total_items + 1)
+        self.n_c = self.n_items if self.kind == 'deepconn++' else int(self.model.item_bias.numel())
 
     def _tables(self, side):
         m = self.model
@@ -488,13 +516,9 @@ class ReluCatalogue(Catalogue):
         return (None, t) if self.kind == 'GMF' else (t, None)
 
     def refresh(self):
-        if self.engine is not None and hasattr(self.engine, 'flush'):
-            self.engine.flush()
+        self._flush()
         m, P = self.model, self._params()
-        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
-        elig = torch.from_numpy(self.eligible).to(self.dev)
-        mask[elig] = True
-        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        elig, mask, ninf = self._eligible_rows()
         with torch.no_grad():
             if self.kind != 'deepconn++':
                 x, gx = self._tables('item')
@@ -502,9 +526,8 @@ class ReluCatalogue(Catalogue):
                 self.c, self.c_bias = c.contiguous(), torch.where(mask, cb, ninf)
             else:
                 c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
-                for s in range(0, len(self.eligible), self.tower_batch):                          # token documents are
-                    ids = self.eligible[s:s + self.tower_batch]                                   # dropped chunk by chunk
-                    sel = elig[s:s + self.tower_batch]
+                for sl, ids in self._batches(self.eligible):
+                    sel = elig[sl]
                     z = self._tower(m.item_conv, self._documents(self.reader.store.items, ids))
                     c[sel], ninf[sel] = fold_relu_head(P, self.hp, 'item', x=z, bias=m.item_bias.detach()[sel])
                 self.c, self.c_bias = c, ninf
@@ -529,11 +552,9 @@ class ReluCatalogue(Catalogue):
                 return q.contiguous(), qb.contiguous()
             q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
             qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-            ids = u_host.numpy()
-            for s in range(0, len(ids), self.tower_batch):
-                z = self._tower(m.user_conv, self._documents(self.reader.store.users, ids[s:s + self.tower_batch]))
-                q[s:s + self.tower_batch], qb[s:s + self.tower_batch], _ = fold_relu_head(
-                    P, self.hp, 'user', x=z, bias=ub[s:s + self.tower_batch])
+            for sl, ids in self._batches(u_host.numpy()):
+                z = self._tower(m.user_conv, self._documents(self.reader.store.users, ids))
+                q[sl], qb[sl], _ = fold_relu_head(P, self.hp, 'user', x=z, bias=ub[sl])
             return q, qb
 
     def _head(self, q, n, qb):
@@ -547,10 +568,9 @@ def narre_catalogue_limits(hyper_params):
     """None when ``NarreCatalogue`` can rank this configuration, else the reason it cannot."""
     from .data import NEIGHBOURS
     mt = hyper_params['model_type']
-    if mt in SUPPORTED:
-        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
-    if mt in ('deepconn++', 'NeuMF'):
-        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
+    served = _served_before(mt, 2)
+    if served:
+        return served
     if mt != 'NARRE':
         why = _REFUSED.get(mt)
         return 'model_type %r has no product-MLP form%s' % (mt, ': ' + why if why else '')
@@ -583,24 +603,11 @@ class NarreCatalogue(Catalogue):
     class; NARRE is served here and through ``eval_catalogue(catalogue=NarreCatalogue(...))``."""
 
     _form = 'hmlp'
+    _limits = staticmethod(narre_catalogue_limits)
 
-    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
-        why = narre_catalogue_limits(hyper_params)
-        if why is not None:
-            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
-        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
-        self.mt = hyper_params['model_type']
-        self.tower_batch = int(tower_batch)
-        self.dev = next(model.parameters()).device
-        if self.dev.type != 'cuda':
-            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
-                               'CPU fallback')
-        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
-        self.eligible = eligible_items(hyper_params, train_reader, candidates)
-        self.D = self.H = _latent_size(hyper_params)
-        self.n_c = self.n_items                                # candidate rows the kernel walks: one per item id
-        self._seen = None
-        self.refresh()
+    def _shape(self):
+        self.D = self.H = _latent_size(self.hp)
+        self.n_c = self.n_items                                # one row per item id
 
     def _attended(self, side, ids):
         """au (side 'user') or ai ('item') [n, L] of the owners ``ids`` (a host int64 array) from the current weights:
@@ -630,16 +637,13 @@ class NarreCatalogue(Catalogue):
             return att + own.weight.detach()[torch.from_numpy(ids).to(self.dev)]
 
     def refresh(self):
-        if self.engine is not None and hasattr(self.engine, 'flush'):
-            self.engine.flush()
+        self._flush()
         m = self.model
-        elig = torch.from_numpy(self.eligible).to(self.dev)
+        elig, _, cb = self._eligible_rows()
         c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
-        cb = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
-                sel = elig[s:s + self.tower_batch]                                                # dropped chunk by chunk
-                c[sel] = self._attended('item', self.eligible[s:s + self.tower_batch])
+            for sl, ids in self._batches(self.eligible):
+                c[elig[sl]] = self._attended('item', ids)
             cb[elig] = m.item_bias.detach()[elig]
             self.c, self.c_bias = c, cb
             self.W = m.final[1].weight.detach().to(torch.float32).contiguous().clone()
@@ -650,17 +654,17 @@ class NarreCatalogue(Catalogue):
         """(q [n, L], q_bias [n]) of the requested users from the current weights."""
         m = self.model
         u = u_host.to(self.dev)
-        ids = u_host.numpy()
         q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for s in range(0, len(ids), self.tower_batch):
-                q[s:s + self.tower_batch] = self._attended('user', ids[s:s + self.tower_batch])
+            for sl, ids in self._batches(u_host.numpy()):
+                q[sl] = self._attended('user', ids)
             qb = (m.user_bias.detach()[u] + m.global_bias.detach()) + m.final[3].bias.detach().reshape(())
         return q, qb.contiguous()
 
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.w),
                 self.D, self.H)
+
 
 RFM_MAX_L = 64                      # r4r_topk_rfm: H <= 64, P <= 16, M <= 80
 _TRANSNET_EMB = 5                   # the width of transnet++'s id embeddings (TransNet.py:75-76)
@@ -669,12 +673,9 @@ _TRANSNET_EMB = 5                   # the width of transnet++'s id embeddings (T
 def transnet_catalogue_limits(hyper_params):
     """None when ``TransNetCatalogue`` can rank this configuration, else the reason it cannot."""
     mt = hyper_params['model_type']
-    if mt in SUPPORTED:
-        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
-    if mt in ('deepconn++', 'NeuMF'):
-        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
-    if mt == 'NARRE':
-        return 'model_type %r has a product-MLP head: NarreCatalogue serves it' % (mt,)
+    served = _served_before(mt, 3)
+    if served:
+        return served
     if mt not in ('transnet', 'transnet++'):
         why = _REFUSED.get(mt)
         return 'model_type %r has no ReLU-FM form: no class serves it%s' % (mt, ' (' + why + ')' if why else '')
@@ -774,38 +775,18 @@ class TransNetCatalogue(Catalogue):
     class; the TransNets are served here and through ``eval_catalogue(catalogue=TransNetCatalogue(...))``."""
 
     _form = 'rfm'
+    _limits = staticmethod(transnet_catalogue_limits)
 
-    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
-        why = transnet_catalogue_limits(hyper_params)
-        if why is not None:
-            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
-        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
-        self.mt = hyper_params['model_type']
+    def _shape(self):
         self.pp = self.mt == 'transnet++'
-        self.tower_batch = int(tower_batch)
-        self.dev = next(model.parameters()).device
-        if self.dev.type != 'cuda':
-            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
-                               'CPU fallback')
-        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
-        self.eligible = eligible_items(hyper_params, train_reader, candidates)
-        L = _latent_size(hyper_params)
+        L = _latent_size(self.hp)
         self.H, self.P, self.M = L, (FM_RANK if self.pp else 0), FM_RANK + L + 1
         self.D = self.H + self.P
-        self.n_c = self.n_items                                # candidate rows the kernel walks: one per item id
-        self._seen = None
-        self.refresh()
+        self.n_c = self.n_items                                # one row per item id
 
-    def _params(self):
-        return {k: v.detach() for k, v in self.model.named_parameters()}
-
-    def _tower(self, tower, idx):
-        """Eval-mode forward of a source tower over the target network's frozen word table."""
-        with torch.no_grad():
-            conv = tower.convs[0]
-            pooled, _ = ops.textcnn_fwd_raw(idx, self.model.target.word2vec.weight, conv.weight.detach(),
-                                            conv.bias.detach())
-            return ops.linear(pooled, tower.fc.weight.detach(), tower.fc.bias.detach())
+    def _words(self):
+        """The source towers read the target network's frozen word table."""
+        return self.model.target.word2vec.weight
 
     def _side(self, P, side, ids, sel):
         """``fold_transnet_head`` of the owners ``ids`` (a host int64 array; ``sel``: the same ids on the device)."""
@@ -817,16 +798,14 @@ class TransNetCatalogue(Catalogue):
         return fold_transnet_head(P, self.hp, side, z, emb=emb, head=False)      # (the head is refresh()'s)
 
     def refresh(self):
-        if self.engine is not None and hasattr(self.engine, 'flush'):
-            self.engine.flush()
+        self._flush()
         P = self._params()
-        elig = torch.from_numpy(self.eligible).to(self.dev)
+        elig, _, cb = self._eligible_rows()
         c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
-        cb = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for s in range(0, len(self.eligible), self.tower_batch):                              # token documents are
-                sel = elig[s:s + self.tower_batch]                                                # dropped chunk by chunk
-                c[sel], cb[sel] = self._side(P, 'item', self.eligible[s:s + self.tower_batch], sel)
+            for sl, ids in self._batches(self.eligible):
+                sel = elig[sl]
+                c[sel], cb[sel] = self._side(P, 'item', ids, sel)
             self.c, self.c_bias = c, cb
             # the head is the user side's; the fold of zero user rows yields it without a tower forward
             none = torch.zeros((0, self.H), dtype=torch.float32, device=self.dev)
@@ -837,13 +816,11 @@ class TransNetCatalogue(Catalogue):
         """(q [n, H + P], q_bias [n]) of the requested users from the current weights."""
         P = self._params()
         u = u_host.to(self.dev)
-        ids = u_host.numpy()
         q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
         qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for s in range(0, len(ids), self.tower_batch):
-                q[s:s + self.tower_batch], qb[s:s + self.tower_batch], _ = self._side(
-                    P, 'user', ids[s:s + self.tower_batch], u[s:s + self.tower_batch])
+            for sl, ids in self._batches(u_host.numpy()):
+                q[sl], qb[sl], _ = self._side(P, 'user', ids, u[sl])
         return q, qb
 
     def _head(self, q, n, qb):
@@ -859,14 +836,9 @@ def mf_catalogue_limits(hyper_params):
     texts for MF -- ``transnet_catalogue_limits``' "no class serves it" among them -- predate this class and are kept as
     they are.)"""
     mt = hyper_params['model_type']
-    if mt in SUPPORTED:
-        return 'model_type %r is a dot product plus two scalars: Catalogue serves it' % (mt,)
-    if mt in ('deepconn++', 'NeuMF'):
-        return 'model_type %r has a ReLU-sum head: ReluCatalogue serves it' % (mt,)
-    if mt == 'NARRE':
-        return 'model_type %r has a product-MLP head: NarreCatalogue serves it' % (mt,)
-    if mt in ('transnet', 'transnet++'):
-        return 'model_type %r has a ReLU-FM head: TransNetCatalogue serves it' % (mt,)
+    served = _served_before(mt, 4)
+    if served:
+        return served
     if mt != 'MF':
         return 'model_type %r has no product-FM form' % (mt,)
     if _latent_size(hyper_params) > PFM_MAX_L:
@@ -946,39 +918,22 @@ class MFCatalogue(Catalogue):
     class); MF is served here and through ``eval_catalogue(catalogue=MFCatalogue(...))``."""
 
     _form = 'pfm'
+    _limits = staticmethod(mf_catalogue_limits)
 
     def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None):
-        why = mf_catalogue_limits(hyper_params)
-        if why is not None:
-            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
-        self.model, self.hp, self.reader, self.engine = model, hyper_params, train_reader, engine
-        self.mt = hyper_params['model_type']
-        self.dev = next(model.parameters()).device
-        if self.dev.type != 'cuda':
-            raise RuntimeError('reviews4rec_amd.recommend: move the model to a ROCm device first; the HIP path has no '
-                               'CPU fallback')
-        self.n_users, self.n_items = int(hyper_params['total_users']), int(hyper_params['total_items'])
-        self.eligible = eligible_items(hyper_params, train_reader, candidates)
-        L = _latent_size(hyper_params)
+        super().__init__(model, hyper_params, train_reader, engine=engine, candidates=candidates)
+        del self.tower_batch                                   # no tower, nothing to batch
+
+    def _shape(self):
+        L = _latent_size(self.hp)
         self.H, self.G, self.M = L, L, 2 * L
         self.D = self.H + self.G
-        self.n_c = int(model.item_bias.numel())                # candidate rows the kernel walks: the item table as it is
-        self._seen = None
-        self.refresh()
-
-    def _params(self):
-        return {k: v.detach() for k, v in self.model.named_parameters()}
-
-    def _flush(self):
-        if self.engine is not None and hasattr(self.engine, 'flush'):
-            self.engine.flush()
+        self.n_c = int(self.model.item_bias.numel())           # the item table as it is
 
     def refresh(self):
         self._flush()
         m, P = self.model, self._params()
-        mask = torch.zeros(self.n_c, dtype=torch.bool, device=self.dev)
-        mask[torch.from_numpy(self.eligible).to(self.dev)] = True
-        ninf = torch.full((self.n_c,), float('-inf'), dtype=torch.float32, device=self.dev)
+        _, mask, ninf = self._eligible_rows()
         with torch.no_grad():
             c, cb = fold_mf_head(P, self.hp, 'item', m.item_embedding.weight.detach(), bias=m.item_bias.detach())
             self.c, self.c_bias = c.contiguous(), torch.where(mask, cb, ninf)

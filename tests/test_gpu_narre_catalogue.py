@@ -386,6 +386,34 @@ def test_ranks_are_the_count_of_candidates_ahead(n_p, n_c, D, H):
             assert np.array_equal(s.view(np.uint32), want_score.view(np.uint32))
 
 
+# ---------------------------------------------------------------- 7a. every dispatch class, lists and ranks
+def test_every_dispatch_class_gives_the_reference_lists_and_ranks():
+    """Both sides of every boundary of HMLP_DISPATCH crossed, each class through mfma_scan_kernel and
+    mfma_rank_scan_kernel once per chunking: n_q = 5 is a full tile and a ragged one, n_c = 37 two full slabs and five
+    rows; chunk 0 is one chunk, 16 three with the merge."""
+    n_q, n_c, K = 5, 37, 3
+    cases = []
+    for D in (8, 9, 16, 17, 32, 33, 64):                      # every reference first: exact on the host, no device call
+        for H in (16, 17, 32, 33, 48, 49, 64):
+            inputs = exact_inputs(np.random.default_rng(D * 7 + H * 1009), n_q, n_c, D, H)
+            S = ref_scores(*inputs, check_exact=True)
+            assert np.array_equal(S.astype(np.float32).astype(np.float64), S)         # exact in fp32
+            cases.append((D, H, inputs, S))
+    qi = np.arange(n_q)
+    ti = qi % n_c
+    for D, H, inputs, S in cases:
+        want_ids, want_sc = ref_lists(S, K)
+        want_rank = host_ranks(S, qi, ti, None)
+        t = Tables(*inputs)
+        for chunk in (0, 16):
+            ids, sc = topk(t, K, chunk)
+            assert np.array_equal(ids, want_ids), (D, H, chunk, np.argwhere(ids != want_ids)[:5])
+            assert np.array_equal(sc.view(np.uint32), want_sc.astype(np.float32).view(np.uint32)), (D, H, chunk)
+            r, rs = rank(t, qi, ti, chunk)
+            assert np.array_equal(r, want_rank), (D, H, chunk, r, want_rank)
+            assert np.array_equal(rs.view(np.uint32), S[qi, ti].astype(np.float32).view(np.uint32)), (D, H, chunk)
+
+
 # ---------------------------------------------------------------- 8. NARRE on tests/golden/tiny
 def _tiny(tmp_path):
     import reviews4rec_amd

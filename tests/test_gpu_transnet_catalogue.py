@@ -455,6 +455,34 @@ def test_ranks_are_the_count_of_candidates_ahead(n_p, n_c, H, P, M):
             assert np.array_equal(sc.view(np.uint32), want_score.view(np.uint32))
 
 
+# ---------------------------------------------------------------- 7a. every dispatch class, lists and ranks
+def test_every_dispatch_class_gives_the_reference_lists_and_ranks():
+    """Both sides of every rfm_kt / rfm_mt boundary crossed (the classes with two queries per wave among them), each
+    through mfma_scan_kernel and mfma_rank_scan_kernel once per chunking: n_q = 5 is a full tile and a ragged one at
+    either tile width, n_c = 37 two full slabs and five rows; chunk 0 is one chunk, 16 three with the merge."""
+    n_q, n_c, K = 5, 37, 3
+    shapes = [(min(D, 64), D - min(D, 64), M) for D in (8, 9, 16, 17, 40, 41, 80) for M in (16, 17, 32, 33, 48, 49, 80)]
+    cases = []
+    for H, P, M in shapes:                                    # every reference first: exact on the host, no device call
+        inputs = exact_inputs(np.random.default_rng(H * 7 + P * 3001 + M * 1009), n_q, n_c, H, P, M)
+        S = ref_scores(*inputs, H, check_exact=True)
+        assert np.array_equal(S.astype(np.float32).astype(np.float64), S)             # exact in fp32
+        cases.append((H, P, M, inputs, S))
+    qi = np.arange(n_q)
+    ti = qi % n_c
+    for H, P, M, inputs, S in cases:
+        want_ids, want_sc = ref_lists(S, K)
+        want_rank = host_ranks(S, qi, ti, None)
+        t = Tables(*inputs, H)
+        for chunk in (0, 16):
+            ids, sc = topk(t, K, chunk)
+            assert np.array_equal(ids, want_ids), (H, P, M, chunk, np.argwhere(ids != want_ids)[:5])
+            assert np.array_equal(sc.view(np.uint32), want_sc.astype(np.float32).view(np.uint32)), (H, P, M, chunk)
+            r, rs = rank(t, qi, ti, chunk)
+            assert np.array_equal(r, want_rank), (H, P, M, chunk, r, want_rank)
+            assert np.array_equal(rs.view(np.uint32), S[qi, ti].astype(np.float32).view(np.uint32)), (H, P, M, chunk)
+
+
 # ---------------------------------------------------------------- 8. both TransNets on tests/golden/tiny
 def _tiny(mt, tmp_path):
     import reviews4rec_amd
