@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import oracle
-from helpers import Golden, synthetic_review_batch
+from helpers import EXP_AVG_SQ_ATOL, Golden, STATE_RTOL, StepStateProbe, synthetic_review_batch
 from test_gpu_models import build_model
 
 pytestmark = pytest.mark.gpu
@@ -452,18 +452,22 @@ def test_mf_engine_large_batch_with_popular_rows(D, B):
         y = torch.randint(1, 6, (B,), generator=rng).float()
         batches.append((uid, iid, y))
 
-    def run():
+    def run(probe=False):
         model = reviews4rec_amd.get_model_class('MF_dot')(hp)
         model.load_state_dict(P0)
         model = model.to(DEV).train()
         eng = MFEngine(model, lr=hp['lr'], weight_decay=hp['weight_decay'])
+        state = StepStateProbe(eng, model, P0, hp) if probe else None
         out = []
         for uid, iid, y in batches:
             se = eng.train_step([None] * 5 + [uid.to(DEV), iid.to(DEV)], y.to(DEV)).cpu().clone()
             out.append((se, eng.dropout_multipliers(B).cpu()))
+            if probe:                                        # the popular rows' sums, as Adam's moments hold them
+                mult = out[-1][1]
+                state.after_step([None] * 5 + [uid, iid], y, {'dropout.user': mult[:, :D], 'dropout.item': mult[:, D:]})
         return {k: v.cpu().clone() for k, v in model.state_dict().items()}, out
 
-    sd, out = run()
+    sd, out = run(probe=True)
     P, state = {k: v.clone() for k, v in P0.items()}, oracle.AdamState()
     for (uid, iid, y), (se, mult) in zip(batches, out):
         masks = {'dropout.user': mult[:, :D], 'dropout.item': mult[:, D:]}
@@ -580,12 +584,13 @@ def test_narre_engine_wide_latent_uses_the_general_instantiation():
     model.load_state_dict(P)
     model = model.to(DEV).train()
     eng = NarreEngine(model, lr=hp['lr'], weight_decay=hp['weight_decay'])
-    state = oracle.AdamState()
+    state, probe = oracle.AdamState(), StepStateProbe(eng, model, P, hp)
     data, y = synthetic_review_batch(B, W, V, U, I, seed=2, R=R, W=W)
     data[1] = torch.randint(0, U + 2, (B, R))
     data[2] = torch.randint(0, I + 2, (B, R))
     for step in range(2):
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)
         sse, _ = oracle.train_step(P, data, y, hp, state)
         torch.testing.assert_close(se.sum(), torch.tensor(sse), rtol=1e-4, atol=1e-4)
     sd = model.state_dict()
@@ -610,7 +615,7 @@ def test_narre_engine_popular_id_rows_in_the_fused_step():
     model.load_state_dict(P)
     model = model.to(DEV).train()
     eng = NarreEngine(model, lr=hp['lr'], weight_decay=hp['weight_decay'])
-    state = oracle.AdamState()
+    state, probe = oracle.AdamState(), StepStateProbe(eng, model, P, hp)
     gen = torch.Generator().manual_seed(5)
     data, y = synthetic_review_batch(B, W, V, U, I, seed=4, R=R, W=W)
     who = torch.randint(0, U + 2, (B, R), generator=gen)
@@ -622,6 +627,7 @@ def test_narre_engine_popular_id_rows_in_the_fused_step():
     data[6] = torch.randint(0, I, (B,), generator=gen)
     for step in range(2):
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)                            # the popular rows' sums, as Adam's moments hold them
         sse, _ = oracle.train_step(P, data, y, hp, state)
         torch.testing.assert_close(se.sum(), torch.tensor(sse), rtol=1e-4, atol=1e-4)
     sd = model.state_dict()
@@ -908,11 +914,13 @@ def test_transnet_engine_wide_latent_and_larger_shapes(mt, T, L):
     model = model.to(DEV).train()
     eng = TransNetEngine(model, lr=hp['lr'], weight_decay=hp['weight_decay'], conv_algo=2)
     states = dict(source=oracle.AdamState(), source_fm=oracle.AdamState(), target=oracle.AdamState())
+    probe = StepStateProbe(eng, model, P, hp)
     data, y = synthetic_review_batch(B, T, V, U, I, seed=3)
     data[5][:4] = data[5][0]                                 # the same user four times, the same item three times
     data[6][5:8] = data[6][5]
     for step in range(2):
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)
         ref_se, lt, ltr = oracle.transnet_train_step(P, data, y, hp, states)
         torch.testing.assert_close(se, ref_se, rtol=1e-4, atol=1e-4)
         aux = eng.aux([d.to(DEV) for d in data]).cpu()
@@ -985,7 +993,8 @@ def test_native_engines_accept_an_empty_and_a_one_row_batch(case):
 
 @pytest.mark.parametrize('mt,L', [('deepconn', 24), ('deepconn', 32), ('deepconn++', 24), ('deepconn++', 32)])
 def test_deepconn_engines_wide_latent_use_the_general_instantiation(mt, L):
-    """latent_size 24 and 32 (> 16: the <= 32 head instantiations; 32 is the hard limit) with tall
+    """latent_size 24 and 32 (> 16: the <= 32 head instantiations; wider ones go up to 128 for DeepCoNN and 64 for
+    DeepCoNN++, tests/test_gpu_full_size.py) with tall
     documents (T = 1100: nine 128-position segments, past the head's one-round-trip pool-finish)
     against the CPU oracle: two steps, SE and updated weights."""
     from reviews4rec_amd import main as M
@@ -999,10 +1008,11 @@ def test_deepconn_engines_wide_latent_use_the_general_instantiation(mt, L):
     model.load_state_dict(P)
     model = model.to(DEV).train()
     eng = M.make_engine(dict(hp, engine='native'), model)
-    state = oracle.AdamState()
+    state, probe = oracle.AdamState(), StepStateProbe(eng, model, P, hp)
     data, y = synthetic_review_batch(B, T, V, U, I, seed=12)
     for step in range(2):
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)
         sse, _ = oracle.train_step(P, data, y, hp, state)
         torch.testing.assert_close(se.sum(), torch.tensor(sse), rtol=1e-4, atol=1e-4)
     sd = model.state_dict()
@@ -1263,35 +1273,39 @@ def test_idnet_engine_large_batches_with_popular_rows(kind, L, B):
     y = torch.randint(1, 6, (B,), generator=gen).float()
     data = [None, None, None, None, None, uid, iid]
 
-    def run():
+    def sites(mult):
+        if kind == 'NeuMF':
+            return {'dropout.gmf_user': mult[:, :L], 'dropout.gmf_item': mult[:, L:2 * L],
+                    'dropout.mlp_user': mult[:, 2 * L:3 * L], 'dropout.mlp_item': mult[:, 3 * L:4 * L],
+                    'project.0': mult[:, 4 * L:]}
+        masks = {'dropout.user': mult[:, :L], 'dropout.item': mult[:, L:2 * L]}
+        if kind != 'GMF':
+            masks['projection.0' if kind == 'MF' else 'project.0'] = mult[:, 2 * L:]
+        return masks
+
+    def run(probe=False):
         model = reviews4rec_amd.get_model_class(hp['model_type'])(hp)
         model.load_state_dict(P)
         model = model.to(DEV).train()
         eng = IdNetEngine(model, lr=hp['lr'], weight_decay=hp['weight_decay'], seed=9)
+        state = StepStateProbe(eng, model, P, hp) if probe else None
         dev = [None] * 5 + [uid.to(DEV), iid.to(DEV)]
         ses, mults = [], []
         for _ in range(2):
             ses.append(eng.train_step(dev, y.to(DEV)).clone())
             mults.append(eng.dropout_multipliers(B).cpu())
+            if probe:                                        # the popular rows' sums, as Adam's moments hold them
+                state.after_step(data, y, sites(mults[-1]))
         return model, eng, ses, mults
 
-    model, eng, ses, mults = run()
+    model, eng, ses, mults = run(probe=True)
     model2, eng2, ses2, _ = run()
     sd, sd2 = model.state_dict(), model2.state_dict()
     assert all(torch.equal(sd[k], sd2[k]) for k in sd) and torch.equal(ses[1], ses2[1])      # deterministic
     ref = {k: v.clone() for k, v in P.items()}
     state = oracle.AdamState()
     for step in range(2):
-        mult = mults[step]
-        if kind == 'NeuMF':
-            masks = {'dropout.gmf_user': mult[:, :L], 'dropout.gmf_item': mult[:, L:2 * L],
-                     'dropout.mlp_user': mult[:, 2 * L:3 * L], 'dropout.mlp_item': mult[:, 3 * L:4 * L],
-                     'project.0': mult[:, 4 * L:]}
-        else:
-            masks = {'dropout.user': mult[:, :L], 'dropout.item': mult[:, L:2 * L]}
-            if kind != 'GMF':
-                masks['projection.0' if kind == 'MF' else 'project.0'] = mult[:, 2 * L:]
-        sse, _ = oracle.train_step(ref, data, y, dict(hp), state, masks=masks)
+        sse, _ = oracle.train_step(ref, data, y, dict(hp), state, masks=sites(mults[step]))
         torch.testing.assert_close(ses[step].sum().cpu(), torch.tensor(sse), rtol=2e-4, atol=1e-2)
     for k, v in ref.items():
         diff = (sd[k].cpu() - v).abs()
@@ -1347,6 +1361,7 @@ def test_rows_apply_large_against_a_dense_adam_step(n, W, bias):
     refM, refV, refMb, refVb = torch.zeros(rows, W), torch.zeros(rows, W), torch.zeros(rows), torch.zeros(rows)
     lr, wd, b1, b2, eps = 0.002, 1e-6, 0.9, 0.999, 1e-8
     null = ctypes.c_void_p(None)
+    touched = torch.zeros(rows, dtype=torch.bool)
 
     def call(ids, g, gb, step, p, m, v, pb, mb, vb):
         rc = lib.r4r_rows_apply_large(ptr(ids), ptr(g), ptr(gb) if bias else null, n, W, ptr(p), ptr(m), ptr(v),
@@ -1385,14 +1400,23 @@ def test_rows_apply_large_against_a_dense_adam_step(n, W, bias):
             pn, mn, vn = p[named].clone(), m[named].clone(), v[named].clone()
             adam(pn, mn, vn, grad[named])
             p[named], m[named], v[named] = pn, mn, vn
+        touched[named] = True
     torch.testing.assert_close(P.cpu(), refP, rtol=1e-5, atol=5e-6)
     torch.testing.assert_close(M.cpu(), refM, rtol=1e-4, atol=1e-6)
+    torch.testing.assert_close(V.cpu(), refV, rtol=STATE_RTOL, atol=EXP_AVG_SQ_ATOL)
     if bias:
         torch.testing.assert_close(Pb.cpu(), refB, rtol=1e-5, atol=5e-6)
+        torch.testing.assert_close(Mb.cpu(), refMb, rtol=1e-4, atol=1e-6)
+        torch.testing.assert_close(Vb.cpu(), refVb, rtol=STATE_RTOL, atol=EXP_AVG_SQ_ATOL)
     else:
-        assert torch.equal(Pb.cpu(), bvec)
-    untouched = torch.ones(rows, dtype=torch.bool)
-    untouched[named] = False                                  # (rows neither step named keep their bits)
+        assert torch.equal(Pb.cpu(), bvec) and not bool(Mb.any()) and not bool(Vb.any())
+    untouched = ~touched                                      # rows neither step named (n = 3,001: 2,247 of them; 20,000: 25;
+    assert bool(untouched.any()) == (n <= 4 * rows)           # beyond: none) keep their bits: they are the caller's sweep
+    assert torch.equal(P.cpu()[untouched], tab[untouched])
+    assert not bool(M.cpu()[untouched].any()) and not bool(V.cpu()[untouched].any())
+    if bias:
+        assert torch.equal(Pb.cpu()[untouched], bvec[untouched])
+        assert not bool(Mb.cpu()[untouched].any()) and not bool(Vb.cpu()[untouched].any())
 
 
 @pytest.mark.parametrize('B', [512, 2048])
@@ -1400,7 +1424,15 @@ def test_narre_engine_beyond_the_fused_entry_caps_against_the_oracle(B):
     """NARRE steps with more ID entries per table than the fused launch's entry waves hold (4,096): B = 512 x (1 + 10)
     = 5,632 runs as gradients -> flat Adam -> r4r_narre_rows_apply; B = 2,048 -> 22,528 entries, past that launch's
     16,384 too: r4r_narre_rows_apply_large.  One process, two training steps, dropout 0, every parameter against
-    the oracle (hyper_params.py:60 puts no bound on batch_size)."""
+    the oracle (hyper_params.py:60 puts no bound on batch_size).
+
+    Adam's moments and the gradients after each step against float64 (assert_step_state), every tensor but the two
+    towers' conv weights: up to 45,056 distinct documents x 100 filters per step always hold a max-pool within rounding
+    of a tie, where float32 and float64 pick different windows and the filter's gradient row moves by one document's
+    share.  The float32 oracle itself leaves the tolerance there (item_conv.convs.0.weight at step 2: 2.4e-7 off at
+    B = 512, 9.0e-7 at B = 2,048, against 1e-7 + 1e-4 |g|), on other filters than a kernel would; nothing downstream of
+    the pool moves (its value is continuous).  tests/test_gpu_step_state.py holds those tensors to the tolerance at
+    the same entry counts, on documents drawn from a small pool."""
     import reviews4rec_amd
     from reviews4rec_amd import main as M
     from test_oracle_golden import ill_conditioned
@@ -1414,7 +1446,7 @@ def test_narre_engine_beyond_the_fused_entry_caps_against_the_oracle(B):
     model = model.to(DEV).train()
     eng = M.make_engine(dict(hp, engine='native'), model)
     assert eng is not None
-    state = oracle.AdamState()
+    state, probe = oracle.AdamState(), StepStateProbe(eng, model, P, hp)
     for step in range(2):
         data, y = synthetic_review_batch(B, W, V, U, I, seed=70 + step, R=R, W=W)
         gen = torch.Generator().manual_seed(step)
@@ -1423,6 +1455,7 @@ def test_narre_engine_beyond_the_fused_entry_caps_against_the_oracle(B):
         data[1][torch.rand(B, R, generator=gen) < 0.3] = U + 1       # the padding sentinel (data.py:275-276)
         data[2][torch.rand(B, R, generator=gen) < 0.3] = I + 1
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y, skip=lambda k: ill_conditioned(k) or k.endswith('_conv.convs.0.weight'))
         sse, grads = oracle.train_step(P, data, y, hp, state)
         torch.testing.assert_close(se.sum(), torch.tensor(sse), rtol=1e-4, atol=1e-3)
     sd = model.state_dict()

@@ -603,7 +603,7 @@ def test_narre_native_step_at_latent_sizes_and_review_counts_up_to_64(L, R):
     against the CPU oracle."""
     import reviews4rec_amd
     from reviews4rec_amd import main as M
-    from helpers import synthetic_review_batch
+    from helpers import StepStateProbe, synthetic_review_batch
     from test_oracle_golden import ill_conditioned
     B, W, E, V, U, I = 12, 20, 16, 300, 60, 50
     hp = dict(model_type='NARRE', latent_size=L, word_embed_size=E, input_length=W, dropout=0.0, total_users=U,
@@ -615,13 +615,14 @@ def test_narre_native_step_at_latent_sizes_and_review_counts_up_to_64(L, R):
     model = model.to(DEV).train()
     eng = M.make_engine(dict(hp, engine='auto', log_file=None), model)
     assert eng is not None and type(eng).__name__ == 'NarreEngine'
-    state = oracle.AdamState()
+    state, probe = oracle.AdamState(), StepStateProbe(eng, model, P, hp)
     for step in range(2):
         data, y = synthetic_review_batch(B, W, V, U, I, seed=110 + step, R=R, W=W)
         gen = torch.Generator().manual_seed(step)
         data[1] = torch.randint(0, U + 2, (B, R), generator=gen)
         data[2] = torch.randint(0, I + 2, (B, R), generator=gen)
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)                            # the rows' sums, as Adam's moments hold them
         sse, grads = oracle.train_step(P, data, y, hp, state)
         torch.testing.assert_close(se.sum(), torch.tensor(sse), rtol=1e-4, atol=1e-3)
     sd = model.state_dict()
@@ -701,7 +702,7 @@ def test_native_steps_of_the_other_text_families_at_latent_sizes_up_to_64(mt, L)
     training steps (TransNet: the three-optimiser step) and an eval forward against the CPU oracle."""
     import reviews4rec_amd
     from reviews4rec_amd import main as M
-    from helpers import synthetic_review_batch
+    from helpers import StepStateProbe, synthetic_review_batch
     from test_oracle_golden import ill_conditioned
     B, T, E, V, U, I = 12, 60, 32, 300, 40, 30
     hp = dict(model_type=mt, latent_size=L, word_embed_size=E, input_length=T, dropout=0.0, total_users=U,
@@ -717,9 +718,11 @@ def test_native_steps_of_the_other_text_families_at_latent_sizes_up_to_64(mt, L)
     is_tn = mt.startswith('transnet')
     states = dict(source=oracle.AdamState(), source_fm=oracle.AdamState(), target=oracle.AdamState()) if is_tn \
         else oracle.AdamState()
+    probe = StepStateProbe(eng, model, P, hp)
     for step in range(2):
         data, y = synthetic_review_batch(B, T, V, U, I, seed=140 + step)
         se = eng.train_step([d.to(DEV) for d in data], y.to(DEV)).cpu().clone()
+        probe.after_step(data, y)                            # (TransNet: the moments of its three optimisers' groups)
         if is_tn:
             ref_se, _, _ = oracle.transnet_train_step(P, data, y, hp, states)
             torch.testing.assert_close(se, ref_se, rtol=1e-4, atol=1e-4)
