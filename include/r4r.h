@@ -1371,6 +1371,52 @@ int r4r_rank_pfm(const float *q, int64_t n_q, const float *q_bias, const float *
                  int H, int G, int M, const int64_t *q_idx, const int64_t *t_idx, int64_t n_p, const int64_t *excl_off,
                  const int64_t *excl_ids, int64_t chunk, int64_t *out_rank, float *out_score, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Tower spans: one side's catalogue towers from the resident pools, enqueued from C (csrc/tower_span.hip).
+ * Replaces  the documents a rating outside the training split is scored with -- every review of the owner, nothing
+ *           removed                                                     data.py:240-246
+ *           pad_and_join / pad_only: cut / zero padded to input_length  data.py:181-210
+ *           NARRE's [R, W] review layout                                data.py:144-172
+ *           the 10-wide neighbour lists and their pad ids               data.py:275-279
+ *           as the catalogue classes evaluate them on the host (reviews4rec_amd/recommend.py: Catalogue._documents,
+ *           NarreCatalogue._attended -- numpy over the pools, one [n, T] int64 block copied per tower_batch owners), and
+ *           the per-chunk Python call sites of Catalogue._tower (r4r_textcnn_fwd + r4r_linear_fwd) in refresh() /
+ *           _queries() of Catalogue, ReluCatalogue, NarreCatalogue and TransNetCatalogue.
+ * One side's pool (r4r_batch_build's layout): tok [tokens + 1] int32, rev_off [reviews + 1], first [owners + 1],
+ * nb [reviews] (NULL for a pool without a single review: an empty array has no address; every neighbour is `pad` then);
+ * ids [n] int64 owner ids ON THE DEVICE, in any order, repeats allowed.
+ *
+ * r4r_tower_build: ONE launch, nothing removed.  R == 0: docs [n, T] = every review of owner ids[r] concatenated, cut /
+ *   zero padded to T; neigh is not written and may be NULL.  R > 0 (NARRE): docs [n, R, W], slot r = the r-th review cut
+ *   / padded to W, and neigh [n, 10] = the nb entries of the first 10 reviews, missing ones `pad`.  Integer for integer
+ *   what data._np_docs / _np_reviews / _np_neighbours return with skip = -1.  An id outside [0, owners) is an owner
+ *   without reviews (a zero document, `pad` neighbours): nothing outside the pool is read whatever ids holds.
+ *   n == 0 returns R4R_OK and enqueues nothing.  Shape rules: r4r_batch_build's (0 < n < 2^31; R > 0 and W > 0, or R == 0
+ *   and T > 0), owners >= 0.
+ *
+ * r4r_tower_span_fwd: the tower over n owners, `group` owners per round.  Round g covers owners [g group, min(n, (g + 1)
+ *   group)) and enqueues r4r_tower_build into the workspace, r4r_textcnn_fwd over the round's rows (owners x max(R, 1)
+ *   rows of T or W words) and r4r_linear_fwd (no ReLU) into latent + g group max(R, 1) L.  latent [n, L], or [n R, L]
+ *   with R > 0; neigh [n, 10] with R > 0, else NULL.  table [V, E], conv_w [F, 3, E], conv_b [F] as r4r_textcnn_fwd takes
+ *   them (E % 4 == 0: a caller with another width pads the table and the weight), fc_w [L, F], fc_b [L].  The kernels and
+ *   their arguments are those of the per-call entry points, and r4r_textcnn_fwd resolves its algorithm from the round's
+ *   rows as it does per call: a span over `group` gives the bits of one r4r_textcnn_fwd + r4r_linear_fwd call per chunk
+ *   of `group` owners.  ws: r4r_tower_span_ws_bytes(group, ...) bytes -- one round's documents, pooled values, argmax and
+ *   r4r_textcnn_ws_bytes of a full round; stream order makes its reuse across rounds safe.  groups_done (host, out,
+ *   nullable): rounds enqueued before an error.  Refused before the first launch, with r4r_last_error set: null
+ *   pointers, group < 1, E % 4 != 0, F > 112, r4r_tower_build's shape rules, a short workspace (R4R_ERR_WORKSPACE).
+ *   n == 0 returns R4R_OK and enqueues nothing.  Nothing allocates, nothing synchronises, no training state is touched.
+ * ---------------------------------------------------------------------- */
+int r4r_tower_build(const int32_t *tok, const int64_t *rev_off, const int64_t *first, const int64_t *nb,
+                    int64_t owners, const int64_t *ids, int64_t n, int T, int R, int W, int64_t pad,
+                    int64_t *docs, int64_t *neigh, void *stream);
+size_t r4r_tower_span_ws_bytes(int64_t group, int T, int R, int W, int E, int F, int L, int64_t V);
+int r4r_tower_span_fwd(const int32_t *tok, const int64_t *rev_off, const int64_t *first, const int64_t *nb,
+                   int64_t owners, const int64_t *ids, int64_t n, int64_t group, int T, int R, int W, int64_t pad,
+                   const float *table, int64_t V, const float *conv_w, const float *conv_b,
+                   const float *fc_w, const float *fc_b, int E, int F, int L,
+                   float *latent, int64_t *neigh, void *ws, size_t ws_bytes, int64_t *groups_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ and ``eval.eval_catalogue(catalogue=MFCatalogue(...))``.  ``main``'s hooks still
 ``_REFUSED`` still give the reason ``Catalogue`` cannot rank it, and ``transnet_catalogue_limits`` still says that no class
 serves it: those texts are pinned by tests and predate ``MFCatalogue``.
 
+Where the towers of the text families run from is ``Catalogue``'s ``towers``: 'host' builds every owner's document with
+numpy and calls the tower once per ``tower_batch`` owners; 'device' builds them from the HBM-resident pools and enqueues
+the same per-chunk launches from C (r4r_tower_span_fwd, csrc/tower_span.hip) -- the same bits, one call per pass.
+
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
 """
@@ -73,8 +77,10 @@ import torch
 
 from . import _lib, ops
 from ._lib import ptr
+from .data import NEIGHBOURS
 
 SUPPORTED = ('bias_only', 'MF_dot', 'deepconn')
+TOWERS = ('host', 'device')         # where a text catalogue builds its documents and enqueues its tower forwards from
 MAX_D, MAX_K, FM_RANK = 256, 128, 8
 
 _REFUSED = {
@@ -181,11 +187,19 @@ class Catalogue:
     training); ``recommend`` / ``score_pairs`` read the cache.  ``engine``: the native engine training the model,
     if any -- its pending table updates are flushed first (MFEngine's blocked sweeps); the model's Parameters are
     the engines' buffers, so nothing else is read back.  A pass leaves the training state where it found it: no
-    dropout draw, no step count, no conv-rule step, no token buffer of the engine is touched."""
+    dropout draw, no step count, no conv-rule step, no token buffer of the engine is touched.
+
+    ``towers``: 'host' (the default) builds every owner's document with numpy, copies it to the device and runs the
+    tower ``tower_batch`` owners per Python call; 'device' builds the documents from the HBM-resident pools and
+    enqueues the same per-chunk launches from C, one r4r_tower_span_fwd call per side and pass (csrc/tower_span.hip) --
+    the same bits.  A configuration without a tower (bias_only, MF_dot, NeuMF) takes either and is unchanged."""
 
     _limits = staticmethod(catalogue_limits)       # a subclass names its own
 
-    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256):
+    def __init__(self, model, hyper_params, train_reader, engine=None, candidates=None, tower_batch=256, towers='host'):
+        if towers not in TOWERS:
+            raise ValueError('catalogue: towers must be one of %r, got %r' % (TOWERS, towers))
+        self.towers = towers
         why = self._limits(hyper_params)
         if why is not None:
             raise RuntimeError('reviews4rec_amd.recommend: ' + why)
@@ -253,6 +267,55 @@ class Catalogue:
                         int(self.hp['input_length']))
         return torch.from_numpy(docs).to(self.dev)
 
+    def _span_latents(self, tower, pool, ids, narre_pad=None):
+        """The device path of ``_tower(tower, _documents(pool, chunk))`` over every ``tower_batch`` chunk of ``ids`` (a
+        host int64 array): ONE r4r_tower_span_fwd call -> latent [n, L].  ``narre_pad`` (NARRE: the pad id of the
+        neighbour lists): the reviews one by one -> (latent [n R, L], neigh [n, 10]).  The id check stays on the host
+        and raises before anything is enqueued; the pass has its own workspace and touches no engine buffer."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
+            raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        hp, conv, n = self.hp, tower.convs[0], len(ids)
+        narre = narre_pad is not None
+        T = int(hp['input_length'])
+        R, W = (int(hp['narre_num_reviews']), int(hp['narre_num_words'])) if narre else (0, 0)
+        per = R if narre else 1
+        fc_w, fc_b = ops._f32(tower.fc.weight.detach(), 'fc.weight'), ops._f32(tower.fc.bias.detach(), 'fc.bias')
+        L = int(fc_w.shape[0])
+        latent = torch.empty((n * per, L), dtype=torch.float32, device=self.dev)
+        neigh = torch.empty((n, NEIGHBOURS), dtype=torch.int64, device=self.dev) if narre else None
+        if n == 0:
+            return (latent, neigh) if narre else latent
+        table = ops._f32(self._words().detach(), 'table')
+        conv_w, conv_b = ops._f32(conv.weight.detach(), 'conv_w'), ops._f32(conv.bias.detach(), 'conv_b')
+        if table.shape[1] % 4:                                 # (ops.textcnn_fwd_raw's padding, once per pass)
+            E0 = table.shape[1]
+            table = ops._padded_table(self._words())
+            pw = torch.zeros(tuple(conv_w.shape[:-1]) + (table.shape[1],), dtype=conv_w.dtype, device=conv_w.device)
+            pw[..., :E0].copy_(conv_w)
+            conv_w = pw
+        V, E = (int(d) for d in table.shape)
+        F = int(conv_b.numel())
+        tok, rev_off, first, nb = pool.device(self.dev)
+        dev_ids = torch.from_numpy(ids).to(self.dev)
+        group = max(1, self.tower_batch)
+        ws = ops._workspace(_lib.lib().r4r_tower_span_ws_bytes(min(group, n), T, R, W, E, F, L, V), self.dev)
+        _lib.call('r4r_tower_span_fwd', ptr(tok), ptr(rev_off), ptr(first), ptr(nb), int(pool.owners), ptr(dev_ids), n, group,
+                  T, R, W, int(narre_pad or 0), ptr(table), V, ptr(conv_w), ptr(conv_b), ptr(fc_w), ptr(fc_b), E, F, L,
+                  ptr(latent), ptr(neigh), ptr(ws), ws.numel(), None)
+        return (latent, neigh) if narre else latent
+
+    def _latents(self, tower, pool, ids):
+        """(sl, ids[sl], latent [len, L]) over the ``tower_batch`` chunks of ``ids`` (a host int64 array): the tower
+        forward of each chunk's documents, per chunk from the host ('host') or as slices of one span ('device')."""
+        if self.towers == 'device':
+            z = self._span_latents(tower, pool, ids)
+            for sl, chunk in self._batches(ids):
+                yield sl, chunk, z[sl]
+        else:
+            for sl, chunk in self._batches(ids):
+                yield sl, chunk, self._tower(tower, self._documents(pool, chunk))
+
     def _fold(self, latent, side):
         fm, m = self.model.fm, self.model
         return fold_fm(fm.V, fm.lin.weight, fm.lin.bias, m.global_bias, latent, side)
@@ -267,8 +330,8 @@ class Catalogue:
                 self.c_bias = torch.where(mask, m.item_bias.detach(), ninf)
                 return
             c = torch.zeros((self.n_c, FM_RANK), dtype=torch.float32, device=self.dev)
-            for sl, ids in self._batches(self.eligible):
-                vec, bias = self._fold(self._tower(m.item_conv, self._documents(self.reader.store.items, ids)), 'item')
+            for sl, _, z in self._latents(m.item_conv, self.reader.store.items, self.eligible):
+                vec, bias = self._fold(z, 'item')
                 c[elig[sl]] = vec
                 ninf[elig[sl]] = bias
             self.c, self.c_bias = c, ninf
@@ -292,8 +355,8 @@ class Catalogue:
                 return q, (m.user_bias.detach()[u] + m.global_bias.detach()).contiguous()
             q = torch.empty((u.numel(), FM_RANK), dtype=torch.float32, device=self.dev)
             qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-            for sl, ids in self._batches(u_host.numpy()):
-                q[sl], qb[sl] = self._fold(self._tower(m.user_conv, self._documents(self.reader.store.users, ids)), 'user')
+            for sl, _, z in self._latents(m.user_conv, self.reader.store.users, u_host.numpy()):
+                q[sl], qb[sl] = self._fold(z, 'user')
             return q, qb
 
     @property
@@ -526,9 +589,8 @@ class ReluCatalogue(Catalogue):
                 self.c, self.c_bias = c.contiguous(), torch.where(mask, cb, ninf)
             else:
                 c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
-                for sl, ids in self._batches(self.eligible):
+                for sl, _, z in self._latents(m.item_conv, self.reader.store.items, self.eligible):
                     sel = elig[sl]
-                    z = self._tower(m.item_conv, self._documents(self.reader.store.items, ids))
                     c[sel], ninf[sel] = fold_relu_head(P, self.hp, 'item', x=z, bias=m.item_bias.detach()[sel])
                 self.c, self.c_bias = c, ninf
             # w is the user side's; the fold of zero user rows yields it without a tower forward
@@ -552,8 +614,7 @@ class ReluCatalogue(Catalogue):
                 return q.contiguous(), qb.contiguous()
             q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
             qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
-            for sl, ids in self._batches(u_host.numpy()):
-                z = self._tower(m.user_conv, self._documents(self.reader.store.users, ids))
+            for sl, _, z in self._latents(m.user_conv, self.reader.store.users, u_host.numpy()):
                 q[sl], qb[sl], _ = fold_relu_head(P, self.hp, 'user', x=z, bias=ub[sl])
             return q, qb
 
@@ -615,9 +676,8 @@ class NarreCatalogue(Catalogue):
         the OTHER side, data.py:275-276), one eval-mode tower forward per review, the eval-mode attention, the owner's
         id embedding."""
         from .data import _np_neighbours, _np_reviews
-        m, hp = self.model, self.hp
-        user = side == 'user'
-        pool = self.reader.store.users if user else self.reader.store.items
+        hp = self.hp
+        user, pool, conv, pad = self._narre_side(side)
         ids = np.asarray(ids, dtype=np.int64)
         if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
             raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
@@ -625,16 +685,42 @@ class NarreCatalogue(Catalogue):
         rb, re = pool.first[ids], pool.first[ids + 1]
         none = np.full(len(ids), -1, np.int64)
         reviews = _np_reviews(pool.tok, pool.rev_off, rb, re, none, R, Wd)
-        pad = (self.n_items if user else self.n_users) + 1
         nb = torch.from_numpy(_np_neighbours(pool.nb, rb, re, none, pad)).to(self.dev)
-        conv, scorer = (m.user_conv, m.attention_scorer_user) if user else (m.item_conv, m.attention_scorer_item)
-        own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
         with torch.no_grad():
             z = self._tower(conv, torch.from_numpy(reviews.reshape(len(ids) * R, Wd)).to(self.dev)).view(len(ids), R, -1)
+            return self._attend(side, z, nb, ids)
+
+    def _narre_side(self, side):
+        """(user, pool, tower, pad id of the neighbour lists: total + 1 of the OTHER side) of 'user' / 'item'."""
+        user, m = side == 'user', self.model
+        return ((True, self.reader.store.users, m.user_conv, self.n_items + 1) if user else
+                (False, self.reader.store.items, m.item_conv, self.n_users + 1))
+
+    def _attend(self, side, z, nb, ids):
+        """The eval-mode attention over review latents ``z`` [n, R, L] weighed by the neighbours ``nb`` [n, 10], plus
+        the id embedding of the owners ``ids`` (a host int64 array)."""
+        m, user = self.model, side == 'user'
+        scorer = m.attention_scorer_user if user else m.attention_scorer_item
+        own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
+        with torch.no_grad():
             att = ops.narre_attention(z, other.weight.detach()[nb].contiguous(), scorer[0].weight.detach(),
                                       scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach(),
                                       0.0, False, None)
-            return att + own.weight.detach()[torch.from_numpy(ids).to(self.dev)]
+            return att + own.weight.detach()[torch.from_numpy(np.asarray(ids, dtype=np.int64)).to(self.dev)]
+
+    def _attended_chunks(self, side, ids):
+        """(sl, ``_attended(side, ids[sl])``) over the ``tower_batch`` chunks of ``ids`` (a host int64 array); with
+        towers 'device' the review latents and the neighbour ids are slices of one r4r_tower_span_fwd pass."""
+        if self.towers != 'device' or len(ids) == 0:
+            for sl, chunk in self._batches(ids):
+                yield sl, self._attended(side, chunk)
+            return
+        _, pool, conv, pad = self._narre_side(side)
+        R = int(self.hp['narre_num_reviews'])
+        z, nb = self._span_latents(conv, pool, ids, narre_pad=pad)
+        z = z.view(len(ids), R, -1)
+        for sl, chunk in self._batches(ids):
+            yield sl, self._attend(side, z[sl], nb[sl], chunk)
 
     def refresh(self):
         self._flush()
@@ -642,8 +728,8 @@ class NarreCatalogue(Catalogue):
         elig, _, cb = self._eligible_rows()
         c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for sl, ids in self._batches(self.eligible):
-                c[elig[sl]] = self._attended('item', ids)
+            for sl, a in self._attended_chunks('item', self.eligible):
+                c[elig[sl]] = a
             cb[elig] = m.item_bias.detach()[elig]
             self.c, self.c_bias = c, cb
             self.W = m.final[1].weight.detach().to(torch.float32).contiguous().clone()
@@ -656,8 +742,8 @@ class NarreCatalogue(Catalogue):
         u = u_host.to(self.dev)
         q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for sl, ids in self._batches(u_host.numpy()):
-                q[sl] = self._attended('user', ids)
+            for sl, a in self._attended_chunks('user', u_host.numpy()):
+                q[sl] = a
             qb = (m.user_bias.detach()[u] + m.global_bias.detach()) + m.final[3].bias.detach().reshape(())
         return q, qb.contiguous()
 
@@ -788,12 +874,18 @@ class TransNetCatalogue(Catalogue):
         """The source towers read the target network's frozen word table."""
         return self.model.target.word2vec.weight
 
-    def _side(self, P, side, ids, sel):
-        """``fold_transnet_head`` of the owners ``ids`` (a host int64 array; ``sel``: the same ids on the device)."""
+    def _source(self, side):
+        """(pool, source tower, name of the id embedding table) of 'user' / 'item'."""
         src = self.model.source
-        pool, tower, table = ((self.reader.store.users, src.user_conv, 'user_embedding') if side == 'user' else
-                              (self.reader.store.items, src.item_conv, 'item_embedding'))
-        z = self._tower(tower, self._documents(pool, ids))
+        return ((self.reader.store.users, src.user_conv, 'user_embedding') if side == 'user' else
+                (self.reader.store.items, src.item_conv, 'item_embedding'))
+
+    def _side(self, P, side, ids, sel, z=None):
+        """``fold_transnet_head`` of the owners ``ids`` (a host int64 array; ``sel``: the same ids on the device;
+        ``z``: their tower latents where the caller holds them)."""
+        pool, tower, table = self._source(side)
+        if z is None:
+            z = self._tower(tower, self._documents(pool, ids))
         emb = getattr(self.model, table).weight.detach()[sel] if self.pp else None
         return fold_transnet_head(P, self.hp, side, z, emb=emb, head=False)      # (the head is refresh()'s)
 
@@ -803,9 +895,10 @@ class TransNetCatalogue(Catalogue):
         elig, _, cb = self._eligible_rows()
         c = torch.zeros((self.n_c, self.D), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for sl, ids in self._batches(self.eligible):
+            pool, tower, _ = self._source('item')
+            for sl, ids, z in self._latents(tower, pool, self.eligible):
                 sel = elig[sl]
-                c[sel], cb[sel] = self._side(P, 'item', ids, sel)
+                c[sel], cb[sel] = self._side(P, 'item', ids, sel, z=z)
             self.c, self.c_bias = c, cb
             # the head is the user side's; the fold of zero user rows yields it without a tower forward
             none = torch.zeros((0, self.H), dtype=torch.float32, device=self.dev)
@@ -819,8 +912,9 @@ class TransNetCatalogue(Catalogue):
         q = torch.empty((u.numel(), self.D), dtype=torch.float32, device=self.dev)
         qb = torch.empty((u.numel(),), dtype=torch.float32, device=self.dev)
         with torch.no_grad():
-            for sl, ids in self._batches(u_host.numpy()):
-                q[sl], qb[sl], _ = self._side(P, 'user', ids, u[sl])
+            pool, tower, _ = self._source('user')
+            for sl, ids, z in self._latents(tower, pool, u_host.numpy()):
+                q[sl], qb[sl], _ = self._side(P, 'user', ids, u[sl], z=z)
         return q, qb
 
     def _head(self, q, n, qb):
@@ -968,7 +1062,7 @@ def hook_limits(hyper_params):
 def make_catalogue(model, hyper_params, train_reader, engine=None):
     """The class that serves main's hooks: ``Catalogue`` where ``catalogue_limits`` accepts, else ``ReluCatalogue``."""
     cls = Catalogue if catalogue_limits(hyper_params) is None else ReluCatalogue
-    return cls(model, hyper_params, train_reader, engine=engine)
+    return cls(model, hyper_params, train_reader, engine=engine, towers=hyper_params.get('catalogue_towers', 'host'))
 
 
 def ranking_metrics(ranks, ks):
@@ -995,6 +1089,13 @@ def ranking_metrics(ranks, ks):
     return out
 
 
+def _check_towers_request(hyper_params):
+    """hyper_params['catalogue_towers'] (``Catalogue``'s ``towers``; absent: 'host') of a request main's hooks will serve."""
+    towers = hyper_params.get('catalogue_towers', 'host')
+    if towers not in TOWERS:
+        raise RuntimeError("hyper_params['catalogue_towers'] must be one of %r, got %r" % (TOWERS, towers))
+
+
 def check_catalogue_metrics_request(hyper_params):
     """main's hook asked for (hyper_params['catalogue_metrics_k'])?  Then refuse, BEFORE anything is loaded, a list that
     is not a non-empty list of positive ints and a model type without a catalogue form (``catalogue_limits``' reason)."""
@@ -1007,6 +1108,7 @@ def check_catalogue_metrics_request(hyper_params):
     why_not = hook_limits(hyper_params)
     if why_not is not None:
         raise RuntimeError("hyper_params['catalogue_metrics_k']: " + why_not)
+    _check_towers_request(hyper_params)
 
 
 def check_recommend_request(hyper_params):
@@ -1019,6 +1121,7 @@ def check_recommend_request(hyper_params):
         raise RuntimeError("hyper_params['recommend_k']: " + why_not)
     if not hyper_params.get('recommend_path'):
         raise RuntimeError("hyper_params['recommend_k'] needs hyper_params['recommend_path'] (the .npz to write)")
+    _check_towers_request(hyper_params)
 
 
 def write_recommendations(path, model, hyper_params, train_reader, k, engine=None):
