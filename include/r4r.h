@@ -1417,6 +1417,101 @@ int r4r_tower_span_fwd(const int32_t *tok, const int64_t *rev_off, const int64_t
                    const float *fc_w, const float *fc_b, int E, int F, int L,
                    float *latent, int64_t *neigh, void *ws, size_t ws_bytes, int64_t *groups_done, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Slates: the K best of, and the place of a target among, a per-query candidate LIST (csrc/slate_device.h).
+ * A slate is the candidate list of one query: what a retrieval stage, a category filter or a basket hands to a
+ * re-ranker, or the sampled negatives of a ranking metric.  The reference's only ranking metric is of the second kind,
+ * HR@1 of one positive against five sampled negatives (eval.py:64-92, the rows built by data.py:375-447), one forward
+ * per candidate; the calls below rank a positive against N given negatives at any K from the cached two sides, with
+ * no forward at all, and order the K best of any list without a scan of the catalogue.
+ *
+ * <form> is one of dot, relu, hmlp, rfm, pfm; the leading arguments are exactly r4r_pair_<form>'s and score(u, i) is
+ * that form's ONE fixed fp32 expression (the sections above), computed here as the scalar chain r4r_pair_<form> runs.
+ *   Slates   slate s belongs to query row q_idx[s] (several slates may share a row); its entries are
+ *            slate_ids[slate_off[s] .. slate_off[s + 1]), in any order.  The ids of one slate are distinct: the
+ *            caller's duty, like the range of q_idx.  slate_off [n_s + 1] (r4r_slate_rank_<form>: [n_p + 1], one slate
+ *            per pair).
+ *   max_len  the caller's upper bound on a slate's length: the host knows it, and it spares a device read.  Understated,
+ *            time is lost and no entry is: the last piece of a slate runs to the slate's end.
+ *   Order    the existing one, in the existing words: score descending, ties by ascending id.  out_scores / out_score
+ *            are r4r_pair_<form>'s bits.  An entry is never listed or counted when it is outside [0, n_c), on the
+ *            ascending CSR exclusion list of the slate's query ROW (excl_off [n_q + 1], excl_ids; both NULL = none), or
+ *            scored -inf or NaN.  Unused slots of a list hold id -1 and score -inf.
+ *   Ranks    pair p = (query row q_idx[p], target t_idx[p], slate p): out_rank[p] = the number of entries != t of the
+ *            slate that are ahead of t; the target need not be in the slate, and is never counted against itself.
+ *            -1 for a target whose own score is -inf or NaN.  t_idx out of range is the caller's error.
+ * The results depend on the inputs only: not on max_len, not on the order of the entries within a slate, not on which
+ * slates share a call -- the order is total, a score's bits depend on its own pair only, ranks are integer atomics.
+ * With slate = 0 .. n_c - 1 the lists and ranks are r4r_topk_<form>'s and r4r_rank_<form>'s, bit for bit.
+ * Limits: 1 <= K <= 128, n_s, n_p, max_len >= 0, and the form's own width limits.  n_s == 0, n_p == 0 or n_c == 0
+ * returns R4R_OK, enqueues nothing and leaves the outputs untouched.  Every refusal precedes the first launch and the
+ * first dereference, in the entry point's own name; a short workspace is R4R_ERR_WORKSPACE; the grid product (slates x
+ * pieces) is checked.  Nothing allocates, nothing synchronises.
+ *
+ * r4r_slate_piece: the entries one wave ranks at a time (a compile-time constant of the library; for callers and tests).
+ * r4r_slate_ws_bytes: the partial lists [n_s, ceil(max_len / piece), K] of (score, id), 12 bytes each; 0 when max_len
+ *   fits a single piece.
+ * r4r_slate_topk_<form>: out_ids / out_scores [n_s, K].  One launch (a wave per slate and piece: the scores of the piece
+ *   staged in LDS, a place = the count of entries ahead, places below K stored at their place), plus r4r_topk_dot's merge
+ *   when a slate has several pieces.
+ * r4r_slate_rank_<form>: out_rank / out_score [n_p].  Two launches: r4r_rank_<form>'s target kernel, then a wave per
+ *   pair and piece that counts and adds one 64-bit integer atomic.  No workspace, no correction launch: exclusions are
+ *   tested per entry.
+ * Scored by scalar chains: for hmlp / rfm / pfm at their largest heads that is r4r_pair_<form>'s cost per entry (of the
+ * order of 50 ms per 10^6 entries); scoring the entries 16 at a time in the columns of an MFMA tile is not built.
+ * ---------------------------------------------------------------------- */
+int r4r_slate_piece(void);
+size_t r4r_slate_ws_bytes(int64_t n_s, int64_t max_len, int K);
+int r4r_slate_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, int D, const int64_t *q_idx, const int64_t *slate_off,
+                       const int64_t *slate_ids, int64_t n_s, int64_t max_len, const int64_t *excl_off,
+                       const int64_t *excl_ids, int K, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores,
+                       void *stream);
+int r4r_slate_rank_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, int D, const int64_t *q_idx, const int64_t *t_idx, const int64_t *slate_off,
+                       const int64_t *slate_ids, int64_t n_p, int64_t max_len, const int64_t *excl_off,
+                       const int64_t *excl_ids, int64_t *out_rank, float *out_score, void *stream);
+int r4r_slate_topk_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                        const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *slate_off,
+                        const int64_t *slate_ids, int64_t n_s, int64_t max_len, const int64_t *excl_off,
+                        const int64_t *excl_ids, int K, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores,
+                        void *stream);
+int r4r_slate_rank_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                        const float *c_bias, const float *w, int H, int P, const int64_t *q_idx, const int64_t *t_idx,
+                        const int64_t *slate_off, const int64_t *slate_ids, int64_t n_p, int64_t max_len,
+                        const int64_t *excl_off, const int64_t *excl_ids, int64_t *out_rank, float *out_score,
+                        void *stream);
+int r4r_slate_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                        const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                        const int64_t *q_idx, const int64_t *slate_off, const int64_t *slate_ids, int64_t n_s,
+                        int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids, int K, void *ws,
+                        size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_slate_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                        const float *c_bias, const float *W, const float *b, const float *w, int D, int H,
+                        const int64_t *q_idx, const int64_t *t_idx, const int64_t *slate_off, const int64_t *slate_ids,
+                        int64_t n_p, int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids,
+                        int64_t *out_rank, float *out_score, void *stream);
+int r4r_slate_topk_rfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, const float *W, const float *b, const float *s, const float *l, int H, int P,
+                       int M, const int64_t *q_idx, const int64_t *slate_off, const int64_t *slate_ids, int64_t n_s,
+                       int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids, int K, void *ws,
+                       size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_slate_rank_rfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, const float *W, const float *b, const float *s, const float *l, int H, int P,
+                       int M, const int64_t *q_idx, const int64_t *t_idx, const int64_t *slate_off,
+                       const int64_t *slate_ids, int64_t n_p, int64_t max_len, const int64_t *excl_off,
+                       const int64_t *excl_ids, int64_t *out_rank, float *out_score, void *stream);
+int r4r_slate_topk_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, const float *W, const float *b, const float *s, const float *g, const float *e,
+                       int H, int G, int M, const int64_t *q_idx, const int64_t *slate_off, const int64_t *slate_ids,
+                       int64_t n_s, int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids, int K, void *ws,
+                       size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream);
+int r4r_slate_rank_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c, int64_t c_stride,
+                       const float *c_bias, const float *W, const float *b, const float *s, const float *g, const float *e,
+                       int H, int G, int M, const int64_t *q_idx, const int64_t *t_idx, const int64_t *slate_off,
+                       const int64_t *slate_ids, int64_t n_p, int64_t max_len, const int64_t *excl_off,
+                       const int64_t *excl_ids, int64_t *out_rank, float *out_score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

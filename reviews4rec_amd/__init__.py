@@ -14,7 +14,10 @@ Layout
                    (ReluCatalogue, relu_catalogue_limits, fold_relu_head) over csrc/topk_relu.hip, and for NARRE's
                    product-MLP head (NarreCatalogue, narre_catalogue_limits) over csrc/topk_hmlp.hip, and for the TransNets'
                    ReLU-FM head (TransNetCatalogue, transnet_catalogue_limits, fold_transnet_head) over csrc/topk_rfm.hip,
-                   and for MF's product-FM head (MFCatalogue, mf_catalogue_limits, fold_mf_head) over csrc/topk_pfm.hip
+                   and for MF's product-FM head (MFCatalogue, mf_catalogue_limits, fold_mf_head) over csrc/topk_pfm.hip;
+                   slates -- the K best of, and the place of an item among, a candidate list per user, for every class
+                   (Catalogue.recommend_among / rank_among, slates_csr, sample_negatives; eval.eval_sampled: the
+                   sampled-negative protocol at any number of negatives and any K) over csrc/slate_device.h
 """
 __version__ = '0.1.0'
 
@@ -41,4 +44,5 @@ from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # n
 from .recommend import NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
 from .recommend import TransNetCatalogue, fold_transnet_head, transnet_catalogue_limits  # noqa: E402,F401
 from .recommend import MFCatalogue, fold_mf_head, mf_catalogue_limits  # noqa: E402,F401
-from .eval import eval_catalogue  # noqa: E402,F401
+from .recommend import sample_negatives, slates_csr  # noqa: E402,F401
+from .eval import eval_catalogue, eval_sampled  # noqa: E402,F401

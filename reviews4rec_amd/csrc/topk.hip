@@ -26,6 +26,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "slate_device.h"
 #include "topk_device.h"
 
 namespace r4r {
@@ -562,3 +563,28 @@ extern "C" int r4r_rank_dot(const float *q, int64_t n_q, const float *q_bias, co
     rc = NQ == 4 ? launch_rank_d<4>(a, p.parts, st) : launch_rank_d<1>(a, p.parts, st);
     return rank_finish(h, rc, q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
 }
+
+// Slates (slate_device.h): the K best of, and the place of a target among, per-query candidate lists
+extern "C" int r4r_slate_topk_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                  int64_t c_stride, const float *c_bias, int D, const int64_t *q_idx,
+                                  const int64_t *slate_off, const int64_t *slate_ids, int64_t n_s, int64_t max_len,
+                                  const int64_t *excl_off, const int64_t *excl_ids, int K, void *ws, size_t ws_bytes,
+                                  int64_t *out_ids, float *out_scores, void *stream) {
+    const DotHead h = dot_head(q, q_bias, c, n_c, c_stride, c_bias, D);
+    return slate_topk_call("slate_topk_dot", h, n_q, q_idx, slate_off, slate_ids, n_s, max_len, excl_off, excl_ids, K,
+                           ws, ws_bytes, out_ids, out_scores, stream);
+}
+
+extern "C" int r4r_slate_rank_dot(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                  int64_t c_stride, const float *c_bias, int D, const int64_t *q_idx,
+                                  const int64_t *t_idx, const int64_t *slate_off, const int64_t *slate_ids, int64_t n_p,
+                                  int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids, int64_t *out_rank,
+                                  float *out_score, void *stream) {
+    const DotHead h = dot_head(q, q_bias, c, n_c, c_stride, c_bias, D);
+    return slate_rank_call("slate_rank_dot", h, n_q, q_idx, t_idx, slate_off, slate_ids, n_p, max_len, excl_off,
+                           excl_ids, out_rank, out_score, stream);
+}
+
+extern "C" int r4r_slate_piece(void) { return SLATE_PIECE; }
+
+extern "C" size_t r4r_slate_ws_bytes(int64_t n_s, int64_t max_len, int K) { return slate_lists_ws_bytes(n_s, max_len, K); }

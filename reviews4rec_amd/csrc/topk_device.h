@@ -8,6 +8,8 @@
 // topk_mfma_device.h.  They call chunk_geom and is_excluded, which leave their instructions as they
 // were (profiles/topk_shared_isa.txt); clearing and writing back the lists, what a ranked pair waits for and the wave
 // sum of its counters did not, and stay written out in each kernel.
+// slate_device.h builds on this file: lists and ranks among per-query candidate lists (r4r_slate_topk_<form>,
+// r4r_slate_rank_<form>), two more scalar kernels over a head with their own checks and call sequence.
 //
 // A score head is a trivially copyable struct, passed to kernels by value:
 //   q, c, n_c, c_stride             the two tables (rows of width() columns)

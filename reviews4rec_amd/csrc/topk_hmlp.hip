@@ -253,3 +253,26 @@ extern "C" int r4r_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, c
     return mfma_rank_call("rank_hmlp", h, HMLP_QT, HMLP_QT, dispatch_hmlp_rank, n_q, q_idx, t_idx, n_p, excl_off, excl_ids,
                           chunk, out_rank, out_score, stream);
 }
+
+// Slates (slate_device.h): the K best of, and the place of a target among, per-query candidate lists
+extern "C" int r4r_slate_topk_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                   int64_t c_stride, const float *c_bias, const float *W, const float *b,
+                                   const float *w, int D, int H, const int64_t *q_idx, const int64_t *slate_off,
+                                   const int64_t *slate_ids, int64_t n_s, int64_t max_len, const int64_t *excl_off,
+                                   const int64_t *excl_ids, int K, void *ws, size_t ws_bytes, int64_t *out_ids,
+                                   float *out_scores, void *stream) {
+    const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    return mfma_slate_topk_call("slate_topk_hmlp", h, n_q, q_idx, slate_off, slate_ids, n_s, max_len, excl_off,
+                                excl_ids, K, ws, ws_bytes, out_ids, out_scores, stream);
+}
+
+extern "C" int r4r_slate_rank_hmlp(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                   int64_t c_stride, const float *c_bias, const float *W, const float *b,
+                                   const float *w, int D, int H, const int64_t *q_idx, const int64_t *t_idx,
+                                   const int64_t *slate_off, const int64_t *slate_ids, int64_t n_p, int64_t max_len,
+                                   const int64_t *excl_off, const int64_t *excl_ids, int64_t *out_rank,
+                                   float *out_score, void *stream) {
+    const HmlpHead h = hmlp_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, w, D, H);
+    return mfma_slate_rank_call("slate_rank_hmlp", h, n_q, q_idx, t_idx, slate_off, slate_ids, n_p, max_len, excl_off,
+                                excl_ids, out_rank, out_score, stream);
+}

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "slate_device.h"
 #include "topk_device.h"
 
 namespace r4r {
@@ -297,6 +298,25 @@ int mfma_rank_call(const char *fn, const Head &h, int chunk_tile, int tile,
     rc = launch_rank_targets(a.h, q_idx, t_idx, n_p, out_score, out_rank, st);
     if (rc != R4R_OK) return rc;
     return rank_finish(a.h, dispatch(a, p.parts, st), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
+}
+
+// The two slate calls of a form (slate_device.h): scalar chains over the head, no stream and no dispatch table
+template <class Head>
+int mfma_slate_topk_call(const char *fn, const Head &h, int64_t n_q, const int64_t *q_idx, const int64_t *slate_off,
+                         const int64_t *slate_ids, int64_t n_s, int64_t max_len, const int64_t *excl_off,
+                         const int64_t *excl_ids, int K, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores,
+                         void *stream) {
+    return slate_topk_call(fn, h, n_q, q_idx, slate_off, slate_ids, n_s, max_len, excl_off, excl_ids, K, ws, ws_bytes,
+                           out_ids, out_scores, stream);
+}
+
+template <class Head>
+int mfma_slate_rank_call(const char *fn, const Head &h, int64_t n_q, const int64_t *q_idx, const int64_t *t_idx,
+                         const int64_t *slate_off, const int64_t *slate_ids, int64_t n_p, int64_t max_len,
+                         const int64_t *excl_off, const int64_t *excl_ids, int64_t *out_rank, float *out_score,
+                         void *stream) {
+    return slate_rank_call(fn, h, n_q, q_idx, t_idx, slate_off, slate_ids, n_p, max_len, excl_off, excl_ids, out_rank,
+                           out_score, stream);
 }
 
 }  // namespace r4r

@@ -32,6 +32,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "slate_device.h"
 #include "topk_device.h"
 
 namespace r4r {
@@ -719,4 +720,27 @@ extern "C" int r4r_rank_pfm(const float *q, int64_t n_q, const float *q_bias, co
     rc = launch_rank_targets(a.h, q_idx, t_idx, n_p, out_score, out_rank, st);
     if (rc != R4R_OK) return rc;
     return rank_finish(a.h, dispatch_pfm_rank(a, grid, st), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
+}
+
+// Slates (slate_device.h): the K best of, and the place of a target among, per-query candidate lists
+extern "C" int r4r_slate_topk_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                  int64_t c_stride, const float *c_bias, const float *W, const float *b, const float *s,
+                                  const float *g, const float *e, int H, int G, int M, const int64_t *q_idx,
+                                  const int64_t *slate_off, const int64_t *slate_ids, int64_t n_s, int64_t max_len,
+                                  const int64_t *excl_off, const int64_t *excl_ids, int K, void *ws, size_t ws_bytes,
+                                  int64_t *out_ids, float *out_scores, void *stream) {
+    const PfmHead h = pfm_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, s, g, e, H, G, M);
+    return slate_topk_call("slate_topk_pfm", h, n_q, q_idx, slate_off, slate_ids, n_s, max_len, excl_off, excl_ids, K,
+                           ws, ws_bytes, out_ids, out_scores, stream);
+}
+
+extern "C" int r4r_slate_rank_pfm(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                  int64_t c_stride, const float *c_bias, const float *W, const float *b, const float *s,
+                                  const float *g, const float *e, int H, int G, int M, const int64_t *q_idx,
+                                  const int64_t *t_idx, const int64_t *slate_off, const int64_t *slate_ids, int64_t n_p,
+                                  int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids, int64_t *out_rank,
+                                  float *out_score, void *stream) {
+    const PfmHead h = pfm_head(q, q_bias, c, n_c, c_stride, c_bias, W, b, s, g, e, H, G, M);
+    return slate_rank_call("slate_rank_pfm", h, n_q, q_idx, t_idx, slate_off, slate_ids, n_p, max_len, excl_off,
+                           excl_ids, out_rank, out_score, stream);
 }

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "slate_device.h"
 #include "topk_device.h"
 
 namespace r4r {
@@ -367,4 +368,25 @@ extern "C" int r4r_rank_relu(const float *q, int64_t n_q, const float *q_bias, c
     if (rc != R4R_OK) return rc;
     hipLaunchKernelGGL(rank_relu_scan_kernel, dim3((unsigned)(p.parts * p.tiles)), dim3(64), relu_stage_floats(H, P) * 4, st, a);
     return rank_finish(h, check_launch("rank_relu_scan_kernel"), q_idx, t_idx, n_p, excl_off, excl_ids, out_score, out_rank, st);
+}
+
+// Slates (slate_device.h): the K best of, and the place of a target among, per-query candidate lists
+extern "C" int r4r_slate_topk_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                   int64_t c_stride, const float *c_bias, const float *w, int H, int P,
+                                   const int64_t *q_idx, const int64_t *slate_off, const int64_t *slate_ids,
+                                   int64_t n_s, int64_t max_len, const int64_t *excl_off, const int64_t *excl_ids,
+                                   int K, void *ws, size_t ws_bytes, int64_t *out_ids, float *out_scores, void *stream) {
+    const ReluHead h = relu_head(q, q_bias, c, n_c, c_stride, c_bias, w, H, P);
+    return slate_topk_call("slate_topk_relu", h, n_q, q_idx, slate_off, slate_ids, n_s, max_len, excl_off, excl_ids, K,
+                           ws, ws_bytes, out_ids, out_scores, stream);
+}
+
+extern "C" int r4r_slate_rank_relu(const float *q, int64_t n_q, const float *q_bias, const float *c, int64_t n_c,
+                                   int64_t c_stride, const float *c_bias, const float *w, int H, int P,
+                                   const int64_t *q_idx, const int64_t *t_idx, const int64_t *slate_off,
+                                   const int64_t *slate_ids, int64_t n_p, int64_t max_len, const int64_t *excl_off,
+                                   const int64_t *excl_ids, int64_t *out_rank, float *out_score, void *stream) {
+    const ReluHead h = relu_head(q, q_bias, c, n_c, c_stride, c_bias, w, H, P);
+    return slate_rank_call("slate_rank_relu", h, n_q, q_idx, t_idx, slate_off, slate_ids, n_p, max_len, excl_off,
+                           excl_ids, out_rank, out_score, stream);
 }

@@ -247,3 +247,47 @@ def eval_catalogue(model, train_reader, test_reader, hyper_params, ks=(1, 5, 10)
     out = {'cat_' + k: round(100.0 * v, 2) for k, v in m.items() if k not in ('ranked', 'unranked')}
     out['cat_ranked'], out['cat_unranked'] = m['ranked'], m['unranked']
     return out
+
+
+def eval_sampled(model, train_reader, test_reader, hyper_params, n_negatives=99, ks=(1, 5, 10), seed=0, engine=None,
+                 catalogue=None, negatives=None):
+    """Sampled-negative ranking metrics -- the protocol of eval.py:64-92 (HR@1 of one positive against five sampled
+    negatives, rows from data.py:375-447) at any number of negatives and any K, NeuMF's 99 negatives with HR@10 /
+    NDCG@10 by default: every row (u, i) of ``test_reader.data`` is placed among ``n_negatives`` items drawn from the
+    eligible items u has no training rating for (recommend.sample_negatives, a function of ``seed``).  ONE
+    Catalogue.rank_among call over the cached two sides -- no forward per candidate -- then recommend.ranking_metrics.
+    ``negatives='dataset'`` takes the reference's own rows instead: per ranking user of ``test_reader.negs``, u ->
+    ([positive, ...], [five negatives]), the first positive against those negatives (repeats dropped).  The slates are
+    ranked as given: nothing further is excluded.
+    -> {'samp_HR@k', 'samp_NDCG@k', 'samp_MRR'} as percentages rounded to two places like cat_* and HR@1, and
+    'samp_ranked' / 'samp_unranked' (a row whose positive has no training rating cannot be ranked; it is counted, not
+    averaged) / 'samp_short' (rows that got fewer than the negatives asked for: the user's pool is smaller).  No ranked
+    row: ZeroDivisionError, like eval.py:90."""
+    import numpy as np
+    from .recommend import Catalogue, ranking_metrics, sample_negatives
+    if negatives not in (None, 'dataset'):
+        raise ValueError("eval_sampled: negatives must be None or 'dataset', got %r" % (negatives,))
+    cat = catalogue if catalogue is not None else Catalogue(model, hyper_params, train_reader, engine=engine)
+    if negatives == 'dataset':
+        rows = [(int(u), int(v[0][0]), np.unique(np.asarray(v[1], dtype=np.int64))) for u, v in test_reader.negs.items()]
+        users = np.array([r[0] for r in rows], np.int64)
+        items = np.array([r[1] for r in rows], np.int64)
+        rows = [r[2][r[2] != r[1]] for r in rows]
+        off = np.zeros(len(rows) + 1, np.int64)
+        np.cumsum([len(r) for r in rows], out=off[1:])
+        ids = np.concatenate(rows + [np.zeros(0, np.int64)])
+        asked = max([len(v[1]) for v in test_reader.negs.values()] + [0])
+    else:
+        data = np.asarray(test_reader.data)
+        if len(data):
+            users, items = data[:, 0].astype(np.int64), data[:, 1].astype(np.int64)
+        else:
+            users = items = np.zeros(0, np.int64)
+        off, ids = sample_negatives(users, items, cat.eligible, cat.seen, n_negatives, seed)
+        asked = int(n_negatives)
+    ranks, _ = cat.rank_among(users, items, (off, ids), exclude_seen=False)
+    m = ranking_metrics(ranks, ks)
+    out = {'samp_' + k: round(100.0 * v, 2) for k, v in m.items() if k not in ('ranked', 'unranked')}
+    out['samp_ranked'], out['samp_unranked'] = m['ranked'], m['unranked']
+    out['samp_short'] = int((np.diff(off) < asked).sum())
+    return out

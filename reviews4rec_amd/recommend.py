@@ -69,6 +69,13 @@ Where the towers of the text families run from is ``Catalogue``'s ``towers``: 'h
 numpy and calls the tower once per ``tower_batch`` owners; 'device' builds them from the HBM-resident pools and enqueues
 the same per-chunk launches from C (r4r_tower_span_fwd, csrc/tower_span.hip) -- the same bits, one call per pass.
 
+Slates -- a candidate list per user -- are ranked by every class: ``recommend_among`` gives the k best of each user's
+own list (re-ranking what a retrieval stage, a filter or a basket hands over) and ``rank_among`` the place of an item
+among given candidates, the sampled-negative protocol of eval.py:64-92 at any number of negatives and any K
+(``sample_negatives`` draws them, ``eval.eval_sampled`` reports the metrics, ``slates_csr`` checks a list).  Both go
+through r4r_slate_topk_<form> / r4r_slate_rank_<form> (csrc/slate_device.h): scalar chains over the cached two sides, in
+``score_pairs``' bits and the same order, without a scan of the catalogue.
+
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
 """
@@ -178,6 +185,129 @@ def seen_csr(train_reader, n_users):
     off = np.zeros(n_users + 1, np.int64)
     np.cumsum(np.bincount(pairs[:, 0], minlength=n_users), out=off[1:])
     return off, np.ascontiguousarray(pairs[:, 1])
+
+
+def _host_ints(a):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('slates: integer ids expected, got %s' % a.dtype)
+    return a.astype(np.int64)
+
+
+def _csr_rows(off):
+    """The row of every entry of a CSR."""
+    return np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+
+
+def slates_csr(slates, n, n_c):
+    """Per-query candidate lists ("slates", include/r4r.h) as what r4r_slate_*_<form> take
+    -> (off int64 [n + 1], ids int64, longest): host arrays and the length of the longest slate.
+
+    ``slates``: a 2-D integer array or tensor [n, C] whose negative entries are padding, or a TUPLE (off, ids).  The
+    entries keep their order.  ValueError for another row count than ``n``, an id outside [0, n_c) and an id repeated
+    within one slate (the kernels count on distinct ids).  Vectorised: no Python loop per row."""
+    n = int(n)
+    if isinstance(slates, tuple):
+        if len(slates) != 2:
+            raise ValueError('slates: a tuple is (off, ids), got %d members' % len(slates))
+        off, ids = _host_ints(slates[0]).reshape(-1), _host_ints(slates[1]).reshape(-1)
+        if len(off) != n + 1:
+            raise ValueError('slates: off has %d entries for %d rows (n + 1 expected)' % (len(off), n))
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != len(ids):
+            raise ValueError('slates: off must ascend from 0 to len(ids) = %d' % len(ids))
+        if len(ids) and ids.min() < 0:
+            raise ValueError('slates: id %d outside [0, %d)' % (ids.min(), n_c))
+    else:
+        a = _host_ints(slates)
+        if a.ndim != 2:
+            if a.size or n:
+                raise ValueError('slates: a 2-D array [n, C] or a tuple (off, ids) expected, got shape %r' % (a.shape,))
+            a = a.reshape(0, 0)                                # (an empty list of rows)
+        if a.shape[0] != n:
+            raise ValueError('slates: %d rows for %d queries' % (a.shape[0], n))
+        keep = a >= 0
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(keep.sum(1), out=off[1:])
+        ids = a[keep]                                          # (row-major: each slate in its own order)
+    if len(ids) and ids.max() >= n_c:
+        raise ValueError('slates: id %d outside [0, %d)' % (ids.max(), n_c))
+    if len(ids):
+        rows = _csr_rows(off)
+        order = np.lexsort((ids, rows))
+        r, i = rows[order], ids[order]
+        twice = (r[1:] == r[:-1]) & (i[1:] == i[:-1])
+        if twice.any():
+            w = int(np.argmax(twice))
+            raise ValueError('slates: id %d repeated in slate %d' % (i[w], r[w]))
+    lens = np.diff(off)
+    return np.ascontiguousarray(off), np.ascontiguousarray(ids), int(lens.max()) if n else 0
+
+
+_SAMPLE_BLOCK = 1 << 22             # draws held at a time by sample_negatives
+
+
+def sample_negatives(users, items, eligible, seen, n_negatives, seed):
+    """The slates of the sampled-negative protocol (NeuMF's: 99 negatives, HR@10 / NDCG@10; the reference's own rows,
+    data.py:375-447, hold five): for row p = (users[p], items[p]) draw min(n_negatives, |pool|) DISTINCT ids uniformly
+    from pool = eligible \\ seen(users[p]) \\ {items[p]}  -> the slate CSR (off int64 [n + 1], ids int64), ids ascending
+    within a slate.  ``eligible``: ids (``Catalogue.eligible``); ``seen``: (off, ids), per user ascending
+    (``seen_csr``).  On the host; a function of its arguments only (numpy.random.default_rng(seed)).
+
+    Vectorised: every row takes the first n_negatives distinct pool members of 2 n_negatives + 16 uniform draws from
+    ``eligible`` -- sequential rejection, so every subset of the pool is equally likely -- and only the rows that do
+    not get there (a pool below n_negatives always, any other seldom) are redrawn one by one from their pool."""
+    N = int(n_negatives)
+    if N < 0:
+        raise ValueError('sample_negatives: n_negatives = %d is negative' % N)
+    u, it = _host_ints(users).reshape(-1), _host_ints(items).reshape(-1)
+    if len(u) != len(it):
+        raise ValueError('sample_negatives: %d users against %d items' % (len(u), len(it)))
+    el = np.unique(_host_ints(eligible).reshape(-1))
+    s_off, s_ids = _host_ints(seen[0]).reshape(-1), _host_ints(seen[1]).reshape(-1)
+    if len(u) and (u.min() < 0 or u.max() >= len(s_off) - 1):
+        raise ValueError('sample_negatives: user id outside the %d rows of seen' % (len(s_off) - 1))
+    n, E = len(u), len(el)
+    rng = np.random.default_rng(seed)
+    lens = np.zeros(n, np.int64)
+    picked = np.zeros((n, N), np.int64)
+    span = int(max(el.max() if E else 0, s_ids.max() if len(s_ids) else 0, it.max() if n else 0)) + 1
+    seen_keys = _csr_rows(s_off) * span + s_ids                # ascending: users in order, ids ascending within each
+    redo = np.ones(n, bool)
+    if N and E:
+        M = 2 * N + 16
+        step = max(1, _SAMPLE_BLOCK // M)
+        for a in range(0, n, step):
+            ub, ib = u[a:a + step], it[a:a + step]
+            draw = el[rng.integers(0, E, size=(len(ub), M))]
+            keys = ub[:, None] * span + draw
+            at = np.searchsorted(seen_keys, keys)
+            ok = (seen_keys[np.minimum(at, len(seen_keys) - 1)] != keys) if len(seen_keys) else np.ones_like(keys, bool)
+            ok &= draw != ib[:, None]
+            order = np.argsort(draw, axis=1, kind='stable')    # (stable: of equal ids the earliest draw comes first)
+            srt = np.take_along_axis(draw, order, 1)
+            again = np.zeros_like(ok)
+            np.put_along_axis(again, order[:, 1:], srt[:, 1:] == srt[:, :-1], 1)
+            ok &= ~again
+            count = np.cumsum(ok, axis=1)
+            full = count[:, -1] >= N
+            take = ok & (count <= N) & full[:, None]
+            picked[a:a + step][full] = np.sort(draw[take].reshape(-1, N), axis=1)
+            lens[a:a + step][full] = N
+            redo[a:a + step] = ~full
+    slow = {}                                                  # the rows left: one by one, the pool once per user
+    for p in np.nonzero(redo)[0] if N else ():
+        uu = int(u[p])
+        if uu not in slow:
+            slow[uu] = np.setdiff1d(el, s_ids[s_off[uu]:s_off[uu + 1]])
+        pool = slow[uu][slow[uu] != it[p]]
+        k = min(N, len(pool))
+        picked[p, :k] = pool if k == len(pool) else np.sort(rng.choice(pool, size=k, replace=False))
+        lens[p] = k
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    return off, np.ascontiguousarray(picked[np.arange(N)[None, :] < lens[:, None]])
 
 
 class Catalogue:
@@ -449,6 +579,61 @@ class Catalogue:
         qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
         _lib.call('r4r_rank_' + self._form, *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ti), n, ptr(eo), ptr(ei),
                   0, ptr(ranks), ptr(scores))
+        return ranks, scores
+
+    # ------------------------------------------------------------------ slates: a candidate list per query
+    def _slates(self, slates, n):
+        """``slates_csr`` of ``slates`` on the device: (off, ids, longest); ids with one spare entry (never a null
+        pointer)."""
+        off, ids, longest = slates_csr(slates, n, self.n_c)
+        ids = np.concatenate([ids, np.zeros(1, np.int64)])
+        return torch.from_numpy(off).to(self.dev), torch.from_numpy(ids).to(self.dev), longest
+
+    def recommend_among(self, users, slates, k=10, exclude_seen=True):
+        """Re-ranking: the k best of each user's OWN candidate list.  ``users``: n ids (a user may come twice, with two
+        lists); ``slates``: what ``slates_csr`` takes, n rows, ids in [0, n_c).
+        -> (items int64 [n, k], scores float32 [n, k]) on the device: score descending, ties by ascending id, in
+        ``score_pairs``' bits; an item that is not eligible (and, with ``exclude_seen``, a training item of the user) is
+        never listed; unused slots hold (-1, -inf).  One r4r_slate_topk_<form> call, queries per DISTINCT user."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError('catalogue: k = %d outside 1 .. %d' % (k, MAX_K))
+        u = self._users(users)
+        n = int(u.numel())
+        off, ids, longest = self._slates(slates, n)
+        items = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n, k), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return items, scores
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
+        qi = inv.to(self.dev)                                  # (named: the pointers must outlive the call)
+        ws = ops._workspace(_lib.lib().r4r_slate_ws_bytes(n, longest, k), self.dev)
+        _lib.call('r4r_slate_topk_' + self._form, *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(off), ptr(ids), n,
+                  longest, ptr(eo), ptr(ei), k, ptr(ws), ws.numel(), ptr(items), ptr(scores))
+        return items, scores
+
+    def rank_among(self, users, items, slates, exclude_seen=True):
+        """The sampled-negative protocol (eval.py:64-92 at any number of negatives and any K): the place of item
+        ``items[p]`` among the candidates ``slates`` row p holds for user ``users[p]``
+        -> (ranks int64 [n], scores float32 [n]) on the device: the number of listed items other than ``items[p]`` that
+        are ahead of it (eligible ones only; with ``exclude_seen`` not the user's training items), -1 where the item
+        itself is not eligible; the item need not be listed.  The scores are ``score_pairs``' bits.  One
+        r4r_slate_rank_<form> call, queries per DISTINCT user."""
+        u, i = self._pairs(users, items)
+        n = int(u.numel())
+        off, ids, longest = self._slates(slates, n)
+        ranks = torch.full((n,), -1, dtype=torch.int64, device=self.dev)
+        scores = torch.full((n,), float('-inf'), dtype=torch.float32, device=self.dev)
+        if n == 0 or self.n_c == 0:
+            return ranks, scores
+        uniq, inv = torch.unique(u, return_inverse=True)
+        q, qb = self._queries(uniq)
+        eo, ei = self._exclusions(uniq) if exclude_seen else (None, None)
+        qi, ti = inv.to(self.dev), i.to(self.dev)              # (named: the pointers must outlive the call)
+        _lib.call('r4r_slate_rank_' + self._form, *self._head(q, int(uniq.numel()), qb), ptr(qi), ptr(ti), ptr(off),
+                  ptr(ids), n, longest, ptr(eo), ptr(ei), ptr(ranks), ptr(scores))
         return ranks, scores
 
 
