@@ -224,8 +224,8 @@ def native_step_limits(hyper_params, world=1):
 
 
 def module_path_limits(hyper_params):
-    """Same question for the op-by-op HIP path (csrc/smallops.hip: FM input width and rank <= 64, a
-    dense layer's input width <= 255, TextCNN rows 16-byte aligned)."""
+    """Same question for the op-by-op HIP path (csrc/smallops.hip: FM input width <= 512 and rank <= 4096, a
+    dense layer's input width <= 255; csrc/narre.hip: at most 32 reviews and 32 latent dimensions)."""
     mt = hyper_params['model_type']
     L = int(hyper_params.get('latent_size', 10))
     E = int(hyper_params.get('word_embed_size', 64))
