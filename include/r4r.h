@@ -1512,6 +1512,41 @@ int r4r_slate_rank_pfm(const float *q, int64_t n_q, const float *q_bias, const f
                        const int64_t *slate_ids, int64_t n_p, int64_t max_len, const int64_t *excl_off,
                        const int64_t *excl_ids, int64_t *out_rank, float *out_score, void *stream);
 
+/* ------------------------------------------------------------------------
+ * NARRE explanations: the eval-mode review attention that KEEPS its weights (csrc/narre_explain.hip).
+ * NARRE is rating regression "with review-level explanations": the attention of NARRE.attention, NARRE.py:53-64, says
+ * which reviews of an item (which of a user's own reviews) carry a prediction.  r4r_narre_attn_fwd saves the weights as
+ * backward state only and stops at 32 x 32; this call is forward only, reaches every R and L in 1..64, gathers the
+ * neighbour rows by id (no [N, R, L] `other` block is built), adds the owner's own row and lists the K heaviest REAL
+ * reviews of every owner.  The arithmetic is r4r_narre_attn_fwd's with mult = NULL:
+ *   h      = relu(W0 [z_r ; other_table[nb_r]] + b0)      W0 [L, 2L]; b0 [L]; w3 [L]; b3 [1]
+ *   a      = softmax_R(w3 . h + b3)                        padded reviews are NOT masked out of the softmax
+ *   out[n] = sum_r a[n, r] z[n, r, :]  (+ own_table[owner[n]])
+ * An nb id outside [0, other_rows) reads as a row of zeros: no id makes the kernel read outside other_table.  owner[n]
+ * is a row of own_table, whose height the call is not told: its range is the caller's duty, like q_idx elsewhere.
+ *   Lists   slot r of owner n is listed only if r < live[n] (live NULL: every slot; a value outside 0..R is clamped):
+ *           weight descending, ties by ascending slot; top_w holds the bits of attn[n, slot] -- the model's own weights,
+ *           not renormalised over the live slots.  A place is the count of live slots ahead (R <= 64 is one wave's worth
+ *           of slots).  Places beyond min(K, live[n]) hold (-1, 0.0f).
+ * An owner's out, attn and list depend on that owner's inputs and the weights only: not on N, not on which owners share
+ * a call, not on K, not on which outputs are NULL.  A slot's logit depends on that slot's inputs only, by one instruction
+ * sequence for every slot: slots with equal z rows and equal neighbour ids get equal bits.
+ * Limits: 1 <= R <= 64, 1 <= L <= 64, 0 <= K <= R, N >= 0, other_rows >= 0.  own_table and owner both or neither,
+ * top_slot and top_w both or neither (K > 0 needs them), at least one output.  N == 0 returns R4R_OK and enqueues
+ * nothing.  Every refusal precedes the launch and the first dereference, in the entry point's own name.  One launch;
+ * nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_narre_explain(const float *z,            /* [N, R, L] review latents                              */
+                      const int64_t *nb,         /* [N, R] neighbour ids, rows of other_table             */
+                      const float *other_table, int64_t other_rows,   /* [other_rows, L]                  */
+                      const float *own_table, const int64_t *owner,   /* [*, L], [N]; both NULL: no add   */
+                      const int32_t *live,       /* [N] real reviews of the owner, 0..R; NULL: all R      */
+                      const float *W0, const float *b0, const float *w3, const float *b3,
+                      float *out,                /* [N, L]  sum_r a_r z_r (+ own_table[owner]); may be NULL */
+                      float *attn,               /* [N, R]  softmax weights, padded slots included; may be NULL */
+                      int32_t *top_slot, float *top_w, int K,         /* [N, K] each; K = 0: both NULL    */
+                      int64_t N, int R, int L, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

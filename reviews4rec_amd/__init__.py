@@ -41,7 +41,7 @@ def get_model_class(model_type):
 
 from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
 from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
-from .recommend import NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
+from .recommend import Explanation, NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
 from .recommend import TransNetCatalogue, fold_transnet_head, transnet_catalogue_limits  # noqa: E402,F401
 from .recommend import MFCatalogue, fold_mf_head, mf_catalogue_limits  # noqa: E402,F401
 from .recommend import sample_negatives, slates_csr  # noqa: E402,F401

@@ -463,6 +463,47 @@ def narre_attention(x, other, W0, b0, w3, b3, p=0.0, training=False, site=None):
     return NarreAttention.apply(x, other, W0, b0, w3, b3, p, training, site)
 
 
+def narre_explain(z, nb, other_table, W0, b0, w3, b3, own_table=None, owner=None, live=None, k=0, want_out=True,
+                  want_attn=True):
+    """r4r_narre_explain (include/r4r.h, "NARRE explanations"): the eval-mode attention over review latents ``z``
+    [N, R, L] weighed by the rows ``nb`` [N, R] (int64) of ``other_table`` [rows, L], R and L up to 64, forward only and
+    without autograd -> (out [N, L] or None, attn [N, R] or None, top_slot int32 [N, k] or None, top_w [N, k] or None).
+    ``own_table`` with ``owner`` (int64 [N], rows of it): out += own_table[owner].  ``live`` (int32 [N]): the slots
+    that may be listed, the first live[n] of each owner; None: all R."""
+    z, other_table = _f32(z, 'z'), _f32(other_table, 'other_table')
+    W0, b0, w3, b3 = _f32(W0, 'W0'), _f32(b0, 'b0'), _f32(w3, 'w3'), _f32(b3, 'b3')
+    nb = _i64(nb, 'nb')
+    if z.dim() != 3 or tuple(nb.shape) != tuple(z.shape[:2]):
+        raise RuntimeError('reviews4rec_amd.ops: narre_explain takes z [N, R, L] and nb [N, R], got %s and %s'
+                           % (tuple(z.shape), tuple(nb.shape)))
+    N, R, L = (int(d) for d in z.shape)
+    if other_table.dim() != 2 or other_table.shape[1] != L or tuple(W0.shape) != (L, 2 * L) or b0.numel() != L \
+            or w3.numel() != L or b3.numel() != 1:
+        raise RuntimeError('reviews4rec_amd.ops: narre_explain: other_table [*, L], W0 [L, 2L], b0 [L], w3 [L], b3 [1] '
+                           'with L = %d expected' % L)
+    if (own_table is None) != (owner is None):
+        raise RuntimeError('reviews4rec_amd.ops: narre_explain: own_table and owner go together')
+    if own_table is not None:
+        own_table, owner = _f32(own_table, 'own_table'), _i64(owner, 'owner')
+        if own_table.dim() != 2 or own_table.shape[1] != L or owner.numel() != N:
+            raise RuntimeError('reviews4rec_amd.ops: narre_explain: own_table [*, L] and owner [N] expected')
+        if N and (int(owner.min()) < 0 or int(owner.max()) >= own_table.shape[0]):
+            raise RuntimeError('reviews4rec_amd.ops: narre_explain: owner outside own_table\'s %d rows' % own_table.shape[0])
+    if live is not None:
+        if not live.is_cuda or live.dtype != torch.int32 or live.numel() != N:
+            raise RuntimeError('reviews4rec_amd.ops: live must be int32 [N] on a ROCm device')
+        live = live.contiguous()
+    k = int(k)
+    dev = z.device
+    out = torch.empty((N, L), dtype=torch.float32, device=dev) if want_out else None
+    attn = torch.empty((N, R), dtype=torch.float32, device=dev) if want_attn else None
+    top_slot = torch.empty((N, k), dtype=torch.int32, device=dev) if k > 0 else None
+    top_w = torch.empty((N, k), dtype=torch.float32, device=dev) if k > 0 else None
+    call('r4r_narre_explain', ptr(z), ptr(nb), ptr(other_table), int(other_table.shape[0]), ptr(own_table), ptr(owner),
+         ptr(live), ptr(W0), ptr(b0), ptr(w3), ptr(b3), ptr(out), ptr(attn), ptr(top_slot), ptr(top_w), k, N, R, L)
+    return out, attn, top_slot, top_w
+
+
 class TransformLoss(Function):
     """mean_n ||a_n - b_n||^2 (TransNet's source/target representation loss)."""
 

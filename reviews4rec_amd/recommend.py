@@ -76,9 +76,15 @@ among given candidates, the sampled-negative protocol of eval.py:64-92 at any nu
 through r4r_slate_topk_<form> / r4r_slate_rank_<form> (csrc/slate_device.h): scalar chains over the cached two sides, in
 ``score_pairs``' bits and the same order, without a scan of the catalogue.
 
+NARRE's review-level explanations -- which reviews of an item, which of a user's own, carry its attended vector -- are
+``NarreCatalogue.explain``: the k heaviest real reviews per owner by the model's attention weights, from
+r4r_narre_explain (csrc/narre_explain.hip), the eval-mode attention for R, L up to 64 that keeps its weights.
+
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -808,6 +814,8 @@ class ReluCatalogue(Catalogue):
 
 
 HMLP_MAX_L = 64                     # r4r_topk_hmlp: D <= 64, H <= 64
+NARRE_ATTN_MAX = 32                 # r4r_narre_attn_fwd: R <= 32, L <= 32; beyond, r4r_narre_explain (R, L <= 64)
+Explanation = namedtuple('Explanation', 'slots reviews reviewers weights attention live')   # NarreCatalogue.explain
 
 
 def narre_catalogue_limits(hyper_params):
@@ -845,8 +853,13 @@ class NarreCatalogue(Catalogue):
     ``refresh()`` flushes the engine's pending row updates and caches the item side (``c`` = ai, ``c_bias`` = item_bias
     with -inf in ineligible rows, ``W``, ``b``, ``w`` from final.1 / final.3), ``tower_batch`` items at a time: one tower
     forward per review and the eval-mode attention.  The query side is computed per call from the current weights.  A
-    pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s hooks do not reach this
-    class; NARRE is served here and through ``eval_catalogue(catalogue=NarreCatalogue(...))``."""
+    pass leaves the training state untouched.  No CPU and no torch fallback.  ``main``'s ``recommend_k`` /
+    ``catalogue_metrics_k`` hooks do not reach this class; NARRE is served here and through
+    ``eval_catalogue(catalogue=NarreCatalogue(...))``.
+
+    The attention runs through r4r_narre_attn_fwd where that takes the shape (R and L up to 32) and through
+    r4r_narre_explain (csrc/narre_explain.hip: R and L up to 64) beyond.  ``explain`` returns what the attention says:
+    each owner's most useful reviews (``main``'s ``explain_k`` hook writes them for every eligible item)."""
 
     _form = 'hmlp'
     _limits = staticmethod(narre_catalogue_limits)
@@ -855,11 +868,11 @@ class NarreCatalogue(Catalogue):
         self.D = self.H = _latent_size(self.hp)
         self.n_c = self.n_items                                # one row per item id
 
-    def _attended(self, side, ids):
+    def _attended(self, side, ids, **how):
         """au (side 'user') or ai ('item') [n, L] of the owners ``ids`` (a host int64 array) from the current weights:
         every review of the owner and its neighbour ids with nothing removed (data.py:240-246; pad id total + 1 of
         the OTHER side, data.py:275-276), one eval-mode tower forward per review, the eval-mode attention, the owner's
-        id embedding."""
+        id embedding.  ``how``: ``_attend``'s ``explain_k``."""
         from .data import _np_neighbours, _np_reviews
         hp = self.hp
         user, pool, conv, pad = self._narre_side(side)
@@ -873,7 +886,7 @@ class NarreCatalogue(Catalogue):
         nb = torch.from_numpy(_np_neighbours(pool.nb, rb, re, none, pad)).to(self.dev)
         with torch.no_grad():
             z = self._tower(conv, torch.from_numpy(reviews.reshape(len(ids) * R, Wd)).to(self.dev)).view(len(ids), R, -1)
-            return self._attend(side, z, nb, ids)
+            return self._attend(side, z, nb, ids, **how)
 
     def _narre_side(self, side):
         """(user, pool, tower, pad id of the neighbour lists: total + 1 of the OTHER side) of 'user' / 'item'."""
@@ -881,31 +894,91 @@ class NarreCatalogue(Catalogue):
         return ((True, self.reader.store.users, m.user_conv, self.n_items + 1) if user else
                 (False, self.reader.store.items, m.item_conv, self.n_users + 1))
 
-    def _attend(self, side, z, nb, ids):
+    def _attend(self, side, z, nb, ids, explain_k=None):
         """The eval-mode attention over review latents ``z`` [n, R, L] weighed by the neighbours ``nb`` [n, 10], plus
-        the id embedding of the owners ``ids`` (a host int64 array)."""
+        the id embedding of the owners ``ids`` (a host int64 array).  Where r4r_narre_attn_fwd takes the shape (R and L
+        up to 32) it is that call, as before; beyond, r4r_narre_explain's ``out`` with the owners' rows added in the
+        kernel.  ``explain_k``: no pooled vector but ``explain``'s pieces of these owners, from r4r_narre_explain at
+        every L -> (attention [n, R], top_slot int32 [n, k], top_w [n, k], live int32 [n], nb)."""
         m, user = self.model, side == 'user'
         scorer = m.attention_scorer_user if user else m.attention_scorer_item
         own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
+        weights = (scorer[0].weight.detach(), scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach())
+        ids = np.asarray(ids, dtype=np.int64)
         with torch.no_grad():
-            att = ops.narre_attention(z, other.weight.detach()[nb].contiguous(), scorer[0].weight.detach(),
-                                      scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach(),
-                                      0.0, False, None)
-            return att + own.weight.detach()[torch.from_numpy(np.asarray(ids, dtype=np.int64)).to(self.dev)]
+            if explain_k is not None:
+                first = self._narre_side(side)[1].first
+                live = torch.from_numpy(np.minimum(first[ids + 1] - first[ids], z.shape[1]).astype(np.int32)).to(self.dev)
+                _, attn, top_slot, top_w = ops.narre_explain(z, nb, other.weight.detach(), *weights, live=live,
+                                                             k=explain_k, want_out=False)
+                return attn, top_slot, top_w, live, nb
+            owners = torch.from_numpy(ids).to(self.dev)
+            if z.shape[1] > NARRE_ATTN_MAX or z.shape[2] > NARRE_ATTN_MAX:
+                return ops.narre_explain(z, nb, other.weight.detach(), *weights, own_table=own.weight.detach(),
+                                         owner=owners, want_attn=False)[0]
+            att = ops.narre_attention(z, other.weight.detach()[nb].contiguous(), *weights, 0.0, False, None)
+            return att + own.weight.detach()[owners]
 
-    def _attended_chunks(self, side, ids):
+    def _attended_chunks(self, side, ids, **how):
         """(sl, ``_attended(side, ids[sl])``) over the ``tower_batch`` chunks of ``ids`` (a host int64 array); with
         towers 'device' the review latents and the neighbour ids are slices of one r4r_tower_span_fwd pass."""
         if self.towers != 'device' or len(ids) == 0:
             for sl, chunk in self._batches(ids):
-                yield sl, self._attended(side, chunk)
+                yield sl, self._attended(side, chunk, **how)
             return
         _, pool, conv, pad = self._narre_side(side)
         R = int(self.hp['narre_num_reviews'])
         z, nb = self._span_latents(conv, pool, ids, narre_pad=pad)
         z = z.view(len(ids), R, -1)
         for sl, chunk in self._batches(ids):
-            yield sl, self._attend(side, z[sl], nb[sl], chunk)
+            yield sl, self._attend(side, z[sl], nb[sl], chunk, **how)
+
+    def explain(self, ids, k=3, side='item'):
+        """The reviews that carry an owner's attended vector: per item (``side='item'``; 'user': per user, among the
+        user's own reviews) the ``k`` heaviest REAL reviews by NARRE's attention (NARRE.py:53-64, eval mode, from the
+        current weights) -> ``Explanation`` of device tensors, n = len(ids):
+
+            slots      int64 [n, k]    the review's slot among the owner's first R reviews; fill -1
+            reviews    int64 [n, k]    its index in that side's pool, ``pool.first[id] + slot`` (``pool.rev_off`` /
+                                       ``pool.tok`` give its tokens); fill -1
+            reviewers  int64 [n, k]    the slot's neighbour id: the user who wrote the review ('item'), the item it is
+                                       about ('user'); fill -1
+            weights    float32 [n, k]  the slots' attention weights, descending, ties by ascending slot; fill 0
+            attention  float32 [n, R]  the model's weights of every slot, padded slots included: rows sum to 1
+            live       int64 [n]       min(number of reviews, R): only an owner's first R reviews take part
+                                       (data.py:144-172)
+
+        The weights are the model's own: the softmax runs over all R slots, padded ones included (the reference does
+        not mask them), and nothing is renormalised over the live slots -- a padded slot is never LISTED, but the
+        listed weights of an owner with fewer than R reviews sum to less than 1.  One r4r_narre_explain call per
+        ``tower_batch`` chunk at every latent size, for both ``towers`` modes.  ``ids``: a list, an array or a tensor
+        on any device; an id outside the side's pool raises KeyError, ``k`` outside 1..R and a ``side`` other than
+        'item' / 'user' raise ValueError.  The engine's pending updates are flushed first, as ``refresh()`` does; the
+        training state is left untouched."""
+        if side not in ('item', 'user'):
+            raise ValueError("catalogue: side must be 'item' or 'user', got %r" % (side,))
+        R = int(self.hp['narre_num_reviews'])
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= R:
+            raise ValueError('catalogue: explain k = %r outside 1 .. %d' % (k, R))
+        k = int(k)
+        ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu().numpy()
+        pool = self.reader.store.users if side == 'user' else self.reader.store.items
+        if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
+            raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        self._flush()
+        n = len(ids)
+        slots = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        weights = torch.zeros((n, k), dtype=torch.float32, device=self.dev)
+        attention = torch.empty((n, R), dtype=torch.float32, device=self.dev)
+        live = torch.zeros((n,), dtype=torch.int64, device=self.dev)
+        reviewers = torch.full((n, k), -1, dtype=torch.int64, device=self.dev)
+        for sl, (attn, top_slot, top_w, lv, nb) in self._attended_chunks(side, ids, explain_k=k):
+            s = top_slot.to(torch.int64)
+            slots[sl], weights[sl], attention[sl], live[sl] = s, top_w, attn, lv
+            reviewers[sl] = torch.where(s >= 0, nb.gather(1, s.clamp(min=0)), s)
+        first = torch.from_numpy(pool.first[ids]).to(self.dev)
+        reviews = torch.where(slots >= 0, first[:, None] + slots, slots)
+        return Explanation(slots, reviews, reviewers, weights, attention, live)
 
     def refresh(self):
         self._flush()
@@ -1316,4 +1389,33 @@ def write_recommendations(path, model, hyper_params, train_reader, k, engine=Non
     items, scores = cat.recommend(users, k=int(k))
     with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
         np.savez(f, users=users, items=items.cpu().numpy(), scores=scores.cpu().numpy())
+    return path
+
+
+def check_explain_request(hyper_params):
+    """main's hook asked for (hyper_params['explain_k'])?  Then refuse, BEFORE any training, a configuration
+    ``NarreCatalogue`` cannot serve (``narre_catalogue_limits``' reason: only NARRE has review-level attention), a k
+    that is no int in 1 .. narre_num_reviews and a request without a file to write."""
+    if not hyper_params.get('explain_k'):
+        return
+    why_not = narre_catalogue_limits(hyper_params)
+    if why_not is not None:
+        raise RuntimeError("hyper_params['explain_k']: " + why_not)
+    k, R = hyper_params['explain_k'], int(hyper_params.get('narre_num_reviews', NEIGHBOURS))
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= R:
+        raise RuntimeError("hyper_params['explain_k'] must be an int in 1 .. narre_num_reviews = %d, got %r" % (R, k))
+    if not hyper_params.get('explain_path'):
+        raise RuntimeError("hyper_params['explain_k'] needs hyper_params['explain_path'] (the .npz to write)")
+    _check_towers_request(hyper_params)
+
+
+def write_explanations(path, model, hyper_params, train_reader, k, engine=None):
+    """main.main's hook: the k most useful reviews of every eligible item (``NarreCatalogue.explain``) -> an .npz of
+    items / slots / reviews / reviewers / weights."""
+    cat = NarreCatalogue(model, hyper_params, train_reader, engine=engine,
+                         towers=hyper_params.get('catalogue_towers', 'host'))
+    e = cat.explain(cat.eligible, k=int(k), side='item')
+    with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
+        np.savez(f, items=cat.eligible, slots=e.slots.cpu().numpy(), reviews=e.reviews.cpu().numpy(),
+                 reviewers=e.reviewers.cpu().numpy(), weights=e.weights.cpu().numpy())
     return path
