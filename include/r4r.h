@@ -468,7 +468,8 @@ int r4r_sse_accumulate(const float *se, int64_t n, float *accum, void *stream);
  * r4r_mf_apply(blocks [world], ...): row tags + owner election over the gathered entries, then the
  *   same tagged sweep as r4r_mf_step -- identical bits on every rank, and identical to the
  *   single-process step on the concatenated batch.  ws: r4r_mf_ws_bytes(world * B_pad, ...), zeroed
- *   once; world * B_pad <= 16384. */
+ *   once; world * B_pad <= 1,048,576 (csrc/mf_engine.hip: MF_MAX_B_STEP, r4r_mf_step's own limit -- owners come from
+ *   the election slots, ids from global memory; main.native_step_limits admits the same global batch). */
 size_t r4r_mf_dp_block_bytes(int64_t B_pad, int D);
 int r4r_mf_grad(const int64_t *uid, const int64_t *iid, const float *y, const uint64_t *p,
                 const uint64_t *m, const uint64_t *v,

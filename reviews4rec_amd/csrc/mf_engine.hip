@@ -270,6 +270,10 @@ struct MfSweep {
     unsigned long long max_ticks = 0;
     unsigned wait_epoch = 0;
     int world = 0;
+    // data parallel (r4r_mf_apply, both forms): the gathered entries are gb_world blocks of gb_pad, a rank's own ratings
+    // first and id -1 behind them; the global-bias workgroup walks the real entries only (0: every entry is real)
+    int gb_world = 0;
+    int64_t gb_pad = 0;
     MfTimeBlock tb = MfTimeBlock{};    // temporally blocked sweep (rows_device.h); tb.rlast_u == NULL: off
     AdamScalars s;
 };
@@ -704,7 +708,27 @@ __device__ __forceinline__ void mf_adam_body(const MfSweep &w) {
         wait_peers();
         float a = 0.f, e = 0.f;
         const int64_t se_n = w.se ? (w.se_n >= 0 ? w.se_n : w.B) : 0;
-        for (int64_t b = tid; b < w.B; b += MF_THREADS) a += w.g[mf_eoff<SCAN>(w, b, 1)];
+        if (w.gb_world > 1) {
+            // data parallel: thread t adds the entries whose index AMONG THE REAL ONES is t, t + 256, ... -- the per-thread
+            // sums and the tree below are then those of the single-process step on the concatenated batch, wherever
+            // the ranks' padding sits (summed by position, a ragged shard moved every later entry to another thread:
+            // the same terms in another association, the global bias alone off by an ulp)
+            int64_t base = 0;                               // real entries of the ranks before r
+            for (int r = 0; r < w.gb_world; ++r) {
+                const int64_t e0 = (int64_t)r * w.gb_pad;
+                int64_t n = 0, hi = w.gb_pad;               // block r: n real entries (id >= 0), then id -1
+                while (n < hi) {
+                    const int64_t mid = (n + hi) >> 1;
+                    if (w.uid32[mf_eoff<SCAN>(w, e0 + mid, 1)] >= 0) n = mid + 1; else hi = mid;
+                }
+                int64_t j = (int64_t)tid - base % MF_THREADS;
+                if (j < 0) j += MF_THREADS;
+                for (; j < n; j += MF_THREADS) a += w.g[mf_eoff<SCAN>(w, e0 + j, 1)];
+                base += n;
+            }
+        } else {
+            for (int64_t b = tid; b < w.B; b += MF_THREADS) a += w.g[mf_eoff<SCAN>(w, b, 1)];
+        }
         for (int64_t b = tid; b < se_n; b += MF_THREADS) e += w.se[b];
         red[tid] = a;
         __syncthreads();
@@ -1746,6 +1770,7 @@ static int mf_apply_impl(const void *blocks, int world, int64_t B_pad, const uin
     }
     sw.se = sse_accum ? se : nullptr; sw.se_n = se_n; sw.sse_accum = sse_accum;   // this rank's share of the running metric rides on the global-bias workgroup
     sw.tag_u = w.tag_u; sw.tag_i = w.tag_i; sw.B = B; sw.D = D; sw.now = (int)adam_step;
+    sw.gb_world = world; sw.gb_pad = B_pad;                 // (one rank: every gathered entry is in its single-process place)
     sw.s = adam_make_scalars(lr, beta1, beta2, eps, weight_decay, adam_step, nullptr);
     if (tb_on) {
         sw.ctag_u = w.ctag_u; sw.ctag_i = w.ctag_i;
