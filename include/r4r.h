@@ -1548,6 +1548,56 @@ int r4r_narre_explain(const float *z,            /* [N, R, L] review latents    
                       int32_t *top_slot, float *top_w, int K,         /* [N, K] each; K = 0: both NULL    */
                       int64_t N, int R, int L, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Phrase explanations: the word windows that win a TextCNN tower's max-pool (csrc/phrases.hip, csrc/tower_span.hip).
+ * Every tower is conv 3 x E (pad 2) -> ReLU -> global max-pool (common_pytorch_models.py:29-31): filter f of a document
+ * contributes the activation of ONE three-word window, the one at argmax[n, f], and an owner's latent vector is a
+ * linear image of those F numbers -- DeepCoNN.py:53-54, NARRE.py:95-96 (per review), TransNet.py:100-102.  Nothing else
+ * of the document reaches the prediction, so "which phrases carry this vector" has a model-faithful answer, and
+ * r4r_textcnn_fwd already returns it: pooled [N, F] and argmax [N, F].  These calls list it; nothing is recomputed.
+ *   Live     filter f of row n is live iff 0 <= argmax[n, f] < T + 2 (the conv's output positions).  Anything else is
+ *            dead and contributes nothing: -1 (what the conv writes where pooled == 0) included.
+ *   Window   the window of a live filter is its position p = argmax[n, f]; it covers the words p - 2 .. p of the row.
+ *   Score    over the live filters with that position in ASCENDING f, starting from 0.0f:
+ *            wt == NULL: acc = acc + pooled[n, f] (plain fp32 adds); else acc = fmaf(wt[n * wt_stride + f], pooled[n, f],
+ *            acc).  wt_stride 0: one [F] vector for every row; wt_stride F: [N, F].  Finite weights are the caller's duty.
+ *   Lists    a row's distinct windows, score descending, ties by ascending position: top_pos, top_score (the bits of
+ *            the chain above), top_filters (the number of live filters the window won).  A place is the count of windows
+ *            ahead; F <= 112 is two filters per lane of one wave.  Entries min(K, windows) .. K hold (-1, 0.0f, 0).
+ *            n_windows[n] = the number of distinct windows, 0 for a row of dead filters.
+ *   Tokens   top_tok[n, k, j] = idx[n, p - 2 + j] where 0 <= p - 2 + j < T, else -1: -1 is the conv's zero padding, as
+ *            distinct from the pad word id 0.  A fill entry is three -1.
+ * A row's outputs depend on that row's inputs only: not on N, not on which rows share a call, not on which outputs are
+ * NULL; the list at K is the first K entries of the list at any larger K.
+ *
+ * r4r_textcnn_phrases: ONE launch.  Refused before it, in the entry point's name: null pooled / argmax, F outside
+ *   1 .. 112, K outside 1 .. F, T < 1, N < 0 or N >= 2^31, wt_stride other than 0 or F, top_tok without idx.  N == 0
+ *   returns R4R_OK and enqueues nothing.  Every output is nullable.
+ * r4r_tower_span_phrases: r4r_tower_span_fwd's rounds (the same pools, ids, group, T / R / W / pad, table, conv
+ *   arguments and workspace: r4r_tower_span_ws_bytes, which alone is told a latent size) with the lists in the place of
+ *   the latents.  Round g enqueues r4r_tower_build, r4r_textcnn_fwd over the round's rows and r4r_textcnn_phrases over
+ *   the round's pooled / argmax / documents (T = the row's width: input_length, or W with R > 0) into the round's slice
+ *   of the outputs, which hold one row per document: n rows, or n R rows in the span's order with R > 0.  With
+ *   wt_stride == F the weights are indexed by the span's global row.  neigh [n, 10] is r4r_tower_build's, needed with
+ *   R > 0.  A span over `group` gives the bits of one host-built chunk + r4r_textcnn_fwd + r4r_textcnn_phrases call per
+ *   chunk of `group` owners.  Refusals, groups_done, n == 0: r4r_tower_span_fwd's, plus K and wt_stride as above and
+ *   n max(R, 1) >= 2^31.  Nothing allocates, nothing synchronises, no training state is touched.
+ * ---------------------------------------------------------------------- */
+int r4r_textcnn_phrases(const float *pooled, const int32_t *argmax,   /* [N, F] as r4r_textcnn_fwd wrote them        */
+                        const float *wt, int64_t wt_stride,           /* NULL = 1; stride 0: [F]; stride F: [N, F]    */
+                        const int64_t *idx,                           /* [N, T] the documents; only for top_tok       */
+                        int64_t N, int T, int F, int K,
+                        int32_t *top_pos, float *top_score, int32_t *top_filters,   /* [N, K] each, nullable          */
+                        int64_t *top_tok,                             /* [N, K, 3], nullable; needs idx               */
+                        int32_t *n_windows,                           /* [N], nullable                                */
+                        void *stream);
+int r4r_tower_span_phrases(const int32_t *tok, const int64_t *rev_off, const int64_t *first, const int64_t *nb,
+                           int64_t owners, const int64_t *ids, int64_t n, int64_t group, int T, int R, int W, int64_t pad,
+                           const float *table, int64_t V, const float *conv_w, const float *conv_b, int E, int F,
+                           const float *wt, int64_t wt_stride, int K,
+                           int32_t *top_pos, float *top_score, int32_t *top_filters, int64_t *top_tok, int32_t *n_windows,
+                           int64_t *neigh, void *ws, size_t ws_bytes, int64_t *groups_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,7 @@ def get_model_class(model_type):
 from .recommend import Catalogue, catalogue_limits, fold_fm, ranking_metrics  # noqa: E402,F401
 from .recommend import ReluCatalogue, fold_relu_head, relu_catalogue_limits  # noqa: E402,F401
 from .recommend import Explanation, NarreCatalogue, narre_catalogue_limits  # noqa: E402,F401
+from .recommend import Phrases, check_explain_words_request, phrase_limits, write_phrases  # noqa: E402,F401
 from .recommend import TransNetCatalogue, fold_transnet_head, transnet_catalogue_limits  # noqa: E402,F401
 from .recommend import MFCatalogue, fold_mf_head, mf_catalogue_limits  # noqa: E402,F401
 from .recommend import sample_negatives, slates_csr  # noqa: E402,F401

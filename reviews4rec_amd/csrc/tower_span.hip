@@ -140,3 +140,69 @@ extern "C" int r4r_tower_span_fwd(const int32_t *tok, const int64_t *rev_off, co
     }
     return R4R_OK;
 }
+
+// The phrase span (include/r4r.h, "Phrase explanations"): r4r_tower_span_fwd's rounds with r4r_textcnn_phrases in the
+// place of r4r_linear_fwd -- the round's pooled / argmax / documents are listed before the next round overwrites them.
+extern "C" int r4r_tower_span_phrases(const int32_t *tok, const int64_t *rev_off, const int64_t *first,
+                                      const int64_t *nb, int64_t owners, const int64_t *ids, int64_t n, int64_t group,
+                                      int T, int R, int W, int64_t pad, const float *table, int64_t V,
+                                      const float *conv_w, const float *conv_b, int E, int F, const float *wt,
+                                      int64_t wt_stride, int K, int32_t *top_pos, float *top_score,
+                                      int32_t *top_filters, int64_t *top_tok, int32_t *n_windows, int64_t *neigh,
+                                      void *ws, size_t ws_bytes, int64_t *groups_done, void *stream) {
+    if (groups_done) *groups_done = 0;
+    if (n == 0) return R4R_OK;
+    // ---- everything that can be refused, before the first launch
+    R4R_REQUIRE(tok && rev_off && first && ids && table && conv_w && conv_b && ws && (R <= 0 || neigh),
+                "r4r_tower_span_phrases: null pointer");
+    R4R_REQUIRE(group >= 1, "r4r_tower_span_phrases: group = %lld owners per round, at least 1", (long long)group);
+    if (int rc = check_build_shape("r4r_tower_span_phrases", owners, n, T, R, W)) return rc;
+    R4R_REQUIRE(E > 0 && E % 4 == 0, "r4r_tower_span_phrases: word_embed_size %d must be a positive multiple of 4 (pad "
+                                     "the frozen table and the conv weight on the host otherwise)", E);
+    R4R_REQUIRE(F > 0 && F <= 112, "r4r_tower_span_phrases: %d filters > 112 supported", F);
+    R4R_REQUIRE(V > 0, "r4r_tower_span_phrases: bad size V=%lld", (long long)V);
+    R4R_REQUIRE(K >= 1 && K <= F, "r4r_tower_span_phrases: K=%d outside 1..F=%d", K, F);
+    R4R_REQUIRE(wt_stride == 0 || wt_stride == F, "r4r_tower_span_phrases: wt_stride=%lld is neither 0 nor F=%d",
+                (long long)wt_stride, F);
+    const int per = R > 0 ? R : 1, width = R > 0 ? W : T;
+    R4R_REQUIRE(n * per < (1ll << 31), "r4r_tower_span_phrases: %lld rows, 2^31 and more", (long long)(n * per));
+    const int64_t G = group < n ? group : n;                // owners of the largest round
+    const int64_t rows_max = G * per;
+    R4R_REQUIRE(rows_max * (int64_t)((width + 2 + 127) / 128) < (1ll << 31),
+                "r4r_tower_span_phrases: %lld rows of %d words per round: the conv's grid is too large",
+                (long long)rows_max, width);
+    // r4r_tower_span_fwd's layout: the largest round's, the conv's part sized for a smaller last round too
+    const TowerWs use = tower_ws(rows_max, width, E, F, V);
+    const int64_t tail = n % G;
+    const size_t tail_conv = tail ? r4r_textcnn_ws_bytes(tail * per, width, E, F, V) : 0;
+    const size_t want = use.total() - use.conv + (tail_conv > use.conv ? tail_conv : use.conv);
+    if (ws_bytes < want) {
+        set_error("r4r_tower_span_phrases: workspace %zu < %zu bytes (r4r_tower_span_ws_bytes)", ws_bytes, want);
+        return R4R_ERR_WORKSPACE;
+    }
+    const size_t conv_bytes = ws_bytes - (use.total() - use.conv);
+    char *base = static_cast<char *>(ws);
+    int64_t *docs = reinterpret_cast<int64_t *>(base);
+    float *pooled = reinterpret_cast<float *>(base + use.docs);
+    int32_t *argmax = reinterpret_cast<int32_t *>(base + use.docs + use.pooled);
+    void *conv_ws = base + use.docs + use.pooled + use.argmax;
+    // ---- round g: owners [g group, min(n, (g + 1) group)); the ONE stream orders the workspace's reuse
+    for (int64_t g = 0, at = 0; at < n; ++g, at += G) {
+        const int64_t m = n - at < G ? n - at : G, rows = m * per, row0 = at * per;
+        if (int rc = r4r_tower_build(tok, rev_off, first, nb, owners, ids + at, m, T, R, W, pad, docs,
+                                     R > 0 ? neigh + at * NEIGHBOURS : nullptr, stream))
+            return rc;
+        if (int rc = r4r_textcnn_fwd(table, V, docs, conv_w, conv_b, pooled, argmax, conv_ws, conv_bytes, rows, width, E, F,
+                                     stream))
+            return rc;
+        if (int rc = r4r_textcnn_phrases(pooled, argmax, wt && wt_stride ? wt + row0 * wt_stride : wt, wt_stride, docs, rows,
+                                         width, F, K, top_pos ? top_pos + row0 * K : nullptr,
+                                         top_score ? top_score + row0 * K : nullptr,
+                                         top_filters ? top_filters + row0 * K : nullptr,
+                                         top_tok ? top_tok + row0 * K * 3 : nullptr,
+                                         n_windows ? n_windows + row0 : nullptr, stream))
+            return rc;
+        if (groups_done) *groups_done = g + 1;
+    }
+    return R4R_OK;
+}

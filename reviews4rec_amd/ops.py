@@ -84,6 +84,53 @@ def textcnn_fwd_raw(idx, table, conv_w, conv_b):
     return pooled, argmax
 
 
+def _phrase_weights(weights, N, F):
+    """``weights`` of a phrase call as (tensor or None, wt_stride): None, one [F] vector or [N, F]."""
+    if weights is None:
+        return None, 0
+    weights = _f32(weights, 'weights')
+    if tuple(weights.shape) == (F,):
+        return weights, 0
+    if tuple(weights.shape) == (N, F):
+        return weights, F
+    raise RuntimeError('reviews4rec_amd.ops: weights must be [F] or [N, F] with N = %d, F = %d, got %s'
+                       % (N, F, tuple(weights.shape)))
+
+
+def textcnn_phrases(pooled, argmax, k, T, weights=None, idx=None):
+    """r4r_textcnn_phrases (include/r4r.h, "Phrase explanations"): the ``k`` heaviest word windows of every row of
+    ``pooled`` [N, F] fp32 / ``argmax`` [N, F] int32 as ``textcnn_fwd_raw`` returns them for documents of ``T`` words.
+    ``weights``: None (activation mass), [F] or [N, F] fp32; ``idx`` [N, T] int64: the documents, for the tokens.
+    No autograd -> (positions int32 [N, k], scores fp32 [N, k], filters int32 [N, k], tokens int64 [N, k, 3] or None
+    without ``idx``, windows int32 [N])."""
+    pooled = _f32(pooled, 'pooled')
+    if not argmax.is_cuda or argmax.dtype != torch.int32:
+        raise RuntimeError('reviews4rec_amd.ops: argmax must be int32 on a ROCm device, got %s on %s'
+                           % (argmax.dtype, argmax.device))
+    argmax = argmax.contiguous()
+    if pooled.dim() != 2 or tuple(argmax.shape) != tuple(pooled.shape):
+        raise RuntimeError('reviews4rec_amd.ops: textcnn_phrases takes pooled [N, F] and argmax [N, F], got %s and %s'
+                           % (tuple(pooled.shape), tuple(argmax.shape)))
+    N, F = (int(d) for d in pooled.shape)
+    k, T = int(k), int(T)
+    weights, stride = _phrase_weights(weights, N, F)
+    if idx is not None:
+        idx = _i64(idx, 'idx')
+        if tuple(idx.shape) != (N, T):
+            raise RuntimeError('reviews4rec_amd.ops: idx must be [N, T] = [%d, %d], got %s' % (N, T, tuple(idx.shape)))
+    dev = pooled.device
+    rows = max(k, 0)
+    pos = torch.empty((N, rows), dtype=torch.int32, device=dev)
+    score = torch.empty((N, rows), dtype=torch.float32, device=dev)
+    filters = torch.empty((N, rows), dtype=torch.int32, device=dev)
+    tokens = torch.empty((N, rows, 3), dtype=torch.int64, device=dev) if idx is not None else None
+    windows = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N:                                                       # (an empty tensor has no address to pass)
+        call('r4r_textcnn_phrases', ptr(pooled), ptr(argmax), ptr(weights), stride, ptr(idx), N, T, F, k, ptr(pos),
+             ptr(score), ptr(filters), ptr(tokens), ptr(windows))
+    return pos, score, filters, tokens, windows
+
+
 def textcnn_wgrad_raw(idx, table, g_pooled, argmax, conv_w_shape):
     idx, table, g_pooled = _i64(idx, 'idx'), _f32(table, 'table'), _f32(g_pooled, 'g_pooled')
     E_model = table.shape[1]

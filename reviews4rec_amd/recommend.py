@@ -80,6 +80,11 @@ NARRE's review-level explanations -- which reviews of an item, which of a user's
 ``NarreCatalogue.explain``: the k heaviest real reviews per owner by the model's attention weights, from
 r4r_narre_explain (csrc/narre_explain.hip), the eval-mode attention for R, L up to 64 that keeps its weights.
 
+Phrase explanations -- which three-word windows of an owner's reviews carry its latent vector -- are ``explain_words`` on
+every text class: the windows that won the max-pool of the side's TextCNN tower (common_pytorch_models.py:29-31), listed
+by r4r_textcnn_phrases (csrc/phrases.hip) from the pooled values and argmax positions the tower forward returns, per chunk
+from the host or inside one r4r_tower_span_phrases call; NARRE gets one list per review, e.g. of the reviews ``explain`` names.
+
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
 """
@@ -642,8 +647,159 @@ class Catalogue:
                   ptr(ids), n, longest, ptr(eo), ptr(ei), ptr(ranks), ptr(scores))
         return ranks, scores
 
+    # ------------------------------------------------------------------ phrase explanations: the windows that win the pool
+    def _phrase_side(self, side):
+        """(pool, TextCNN tower, NARRE's neighbour pad id or None) of 'user' / 'item'; a configuration without a tower
+        is refused with the reason."""
+        why = phrase_limits(self.hp)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        m = self.model
+        return (self.reader.store.users, m.user_conv, None) if side == 'user' else (self.reader.store.items, m.item_conv, None)
 
-RELU_MAX_L = 128                    # r4r_topk_relu: H <= 128, P <= 128
+    def _phrase_weights(self, tower, weights, n, per):
+        """``explain_words``' ``weights`` as what the kernel takes: None, [F] or one row per document [n per, F]."""
+        F = int(tower.convs[0].bias.numel())
+        if weights is None:
+            return None
+        if isinstance(weights, str):
+            if weights != 'latent':
+                raise ValueError("catalogue: weights must be None, 'latent' or a tensor [F] / [n, F], got %r" % (weights,))
+            return tower.fc.weight.detach().norm(dim=0).to(torch.float32).contiguous()
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or \
+                tuple(weights.shape) not in ((F,), (n, F)):
+            raise ValueError("catalogue: weights must be None, 'latent' or a float32 tensor [%d] / [%d, %d], got %s"
+                             % (F, n, F, tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__))
+        weights = weights.detach().to(self.dev).contiguous()
+        if weights.dim() == 2 and per > 1:
+            weights = weights.repeat_interleave(per, dim=0).contiguous()      # an owner's row for each of its reviews
+        return weights
+
+    def _phrase_rows(self, tower, pool, ids, k, wt, narre_pad=None):
+        """r4r_textcnn_phrases over the documents of ``ids`` (a host int64 array; NARRE: over each owner's R reviews)
+        -> (positions, scores, filters, tokens, windows), one row per document.  'host': numpy documents and one
+        textcnn_fwd_raw + textcnn_phrases call per ``tower_batch`` owners; 'device': ONE r4r_tower_span_phrases call,
+        the same bits."""
+        hp, conv, n = self.hp, tower.convs[0], len(ids)
+        narre = narre_pad is not None
+        T = int(hp['narre_num_words']) if narre else int(hp['input_length'])
+        R = int(hp['narre_num_reviews']) if narre else 0
+        per = R if narre else 1
+        rows = n * per
+        i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=self.dev)
+        pos, filt, win = i32(rows, k), i32(rows, k), i32(rows)
+        score = torch.empty((rows, k), dtype=torch.float32, device=self.dev)
+        tokens = torch.empty((rows, k, 3), dtype=torch.int64, device=self.dev)
+        if n == 0:
+            return pos, score, filt, tokens, win
+        per_row = wt is not None and wt.dim() == 2
+        if self.towers != 'device':
+            from .data import _np_reviews
+            for sl, chunk in self._batches(ids):
+                if narre:
+                    none = np.full(len(chunk), -1, np.int64)
+                    docs = _np_reviews(pool.tok, pool.rev_off, pool.first[chunk], pool.first[chunk + 1], none, R, T)
+                    docs = torch.from_numpy(docs.reshape(len(chunk) * R, T)).to(self.dev)
+                else:
+                    docs = self._documents(pool, chunk)
+                rs = slice(sl.start * per, sl.start * per + len(chunk) * per)
+                pooled, argmax = ops.textcnn_fwd_raw(docs, self._words(), conv.weight.detach(), conv.bias.detach())
+                pos[rs], score[rs], filt[rs], tokens[rs], win[rs] = ops.textcnn_phrases(
+                    pooled, argmax, k, T, weights=wt[rs] if per_row else wt, idx=docs)
+            return pos, score, filt, tokens, win
+        table = ops._f32(self._words().detach(), 'table')
+        conv_w, conv_b = ops._f32(conv.weight.detach(), 'conv_w'), ops._f32(conv.bias.detach(), 'conv_b')
+        if table.shape[1] % 4:                                 # (ops.textcnn_fwd_raw's padding, once per pass)
+            E0 = table.shape[1]
+            table = ops._padded_table(self._words())
+            pw = torch.zeros(tuple(conv_w.shape[:-1]) + (table.shape[1],), dtype=conv_w.dtype, device=conv_w.device)
+            pw[..., :E0].copy_(conv_w)
+            conv_w = pw
+        V, E = (int(d) for d in table.shape)
+        F, L = int(conv_b.numel()), int(tower.fc.weight.shape[0])
+        tok, rev_off, first, nb = pool.device(self.dev)
+        dev_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)).to(self.dev)
+        neigh = torch.empty((n, NEIGHBOURS), dtype=torch.int64, device=self.dev) if narre else None
+        group = max(1, self.tower_batch)
+        ws = ops._workspace(_lib.lib().r4r_tower_span_ws_bytes(min(group, n), 0 if narre else T, R, T if narre else 0, E, F,
+                                                               L, V), self.dev)
+        _lib.call('r4r_tower_span_phrases', ptr(tok), ptr(rev_off), ptr(first), ptr(nb), int(pool.owners), ptr(dev_ids), n,
+                  group, 0 if narre else T, R, T if narre else 0, int(narre_pad or 0), ptr(table), V, ptr(conv_w),
+                  ptr(conv_b), E, F, ptr(wt), F if per_row else 0, k, ptr(pos), ptr(score), ptr(filt), ptr(tokens),
+                  ptr(win), ptr(neigh), ptr(ws), ws.numel(), None)
+        return pos, score, filt, tokens, win
+
+    def _phrase_request(self, ids, k, side, weights, per=1):
+        """``explain_words``' checks, in order, before anything runs -> (ids as a host array, pool, tower, pad, wt)."""
+        if side not in ('item', 'user'):
+            raise ValueError("catalogue: side must be 'item' or 'user', got %r" % (side,))
+        pool, tower, pad = self._phrase_side(side)
+        F = int(tower.convs[0].bias.numel())
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= F:
+            raise ValueError('catalogue: explain_words k = %r outside 1 .. %d' % (k, F))
+        ids = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).cpu().numpy()
+        wt = self._phrase_weights(tower, weights, len(ids), per)
+        if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
+            raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        return ids, pool, tower, pad, wt
+
+    def explain_words(self, ids, k=5, side='item', weights=None):
+        """The phrases that carry an owner's latent vector: per item (``side='item'``; 'user': per user) the ``k``
+        heaviest three-word windows of its document, i.e. the windows that won the max-pool of the side's TextCNN tower
+        (common_pytorch_models.py:29-31; include/r4r.h, "Phrase explanations"), from the current weights
+        -> ``Phrases`` of device tensors, n = len(ids):
+
+            positions  int32 [n, k]     the window's conv position p: it covers the words p - 2 .. p; fill -1
+            scores     float32 [n, k]   the window's weight, descending, ties by ascending position; fill 0
+            filters    int32 [n, k]     the number of filters whose maximum the window is; fill 0
+            tokens     int64 [n, k, 3]  the window's word ids; -1 in the conv's zero padding and in a fill entry
+            reviews    int64 [n, k]     the index in that side's pool of the review holding the window's first
+                                        in-document token (``pool.rev_off`` / ``pool.tok`` give its tokens); -1 for a
+                                        window that lies wholly in padding
+            offsets    int64 [n, k]     that token's word offset inside the review; -1 with reviews == -1
+            windows    int32 [n]        the number of distinct windows of the owner
+
+        ``weights``: None -- a window's score is the activation mass it won, the sum of its filters' pooled values;
+        'latent' -- each filter weighed by ``tower.fc.weight.norm(dim=0)``, how far a unit of the feature moves the
+        latent vector; a float32 tensor [F] or [n, F] -- the caller's own, e.g. the gradient of a pair's score.
+        One r4r_textcnn_phrases call per ``tower_batch`` chunk ('host') or one r4r_tower_span_phrases call ('device'):
+        the same bits.  An id outside the side's pool raises KeyError; ``k`` outside 1 .. F, a bad ``side`` and bad
+        ``weights`` raise ValueError; a configuration without a tower is refused with the reason.  The engine's pending
+        updates are flushed first, as ``refresh()`` does; the training state is left untouched."""
+        ids, pool, tower, _, wt = self._phrase_request(ids, k, side, weights)
+        k = int(k)
+        self._flush()
+        with torch.no_grad():
+            pos, score, filt, tokens, win = self._phrase_rows(tower, pool, ids, k, wt)
+        _, rev_off, first, _ = pool.device(self.dev)
+        own = torch.from_numpy(ids).to(self.dev)
+        begin, end = rev_off[first[own]], rev_off[first[own + 1]]                 # the owner's tokens in the pool
+        t0 = (pos.to(torch.int64) - 2).clamp(min=0)                              # the first in-document word (p < T + 2)
+        at = begin[:, None] + t0
+        inside = (pos >= 0) & (at < end[:, None])
+        review = torch.searchsorted(rev_off, at.contiguous(), right=True) - 1
+        minus = torch.full_like(at, -1)
+        reviews = torch.where(inside, review, minus)
+        offsets = torch.where(inside, at - rev_off[review.clamp(min=0, max=rev_off.numel() - 1)], minus)
+        return Phrases(pos, score, filt, tokens, reviews, offsets, win)
+
+
+PHRASE_FILTERS = 100                # every TextCNN tower's filter count (common_pytorch_models.py:11)
+_PHRASE_TYPES = ('deepconn', 'deepconn++', 'transnet', 'transnet++', 'NARRE')
+Phrases = namedtuple('Phrases', 'positions scores filters tokens reviews offsets windows slots weights',
+                     defaults=(None, None))        # Catalogue.explain_words; slots / weights: NarreCatalogue's
+
+
+def phrase_limits(hyper_params):
+    """None when this configuration has a TextCNN tower whose windows ``explain_words`` can list, else the reason."""
+    mt = hyper_params['model_type']
+    if mt not in _PHRASE_TYPES:
+        return ('model_type %r has no TextCNN tower (its two sides are id embeddings): there are no word windows to '
+                'explain' % (mt,))
+    return None
+
+
+RELU_MAX_L = 128                   # r4r_topk_relu: H <= 128, P <= 128
 _NEUMF_STAGES = ('GMF', 'MLP', 'NeuMF')
 
 
@@ -980,6 +1136,59 @@ class NarreCatalogue(Catalogue):
         reviews = torch.where(slots >= 0, first[:, None] + slots, slots)
         return Explanation(slots, reviews, reviewers, weights, attention, live)
 
+    def _phrase_side(self, side):
+        _, pool, tower, pad = self._narre_side(side)
+        return pool, tower, pad
+
+    def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
+        """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
+        (NARRE.py:95-96), so there is one list of windows per (owner, slot) -> ``Phrases`` with [n, R, k] (tokens
+        [n, R, k, 3], windows [n, R]); ``reviews=k_r``: [n, k_r, k], the phrases of the ``k_r`` reviews ``explain``
+        lists, in its order, with its ``slots`` [n, k_r] and ``weights`` [n, k_r] alongside (a slot of -1 -- an owner
+        with fewer than k_r reviews -- holds the fill: positions -1, scores 0, filters 0, tokens -1, windows 0).
+
+            reviews    int64  ``pool.first[id] + slot`` where the slot holds a review and the window's first in-review
+                              word lies inside it, else -1
+            offsets    int64  that word's offset inside the review, max(p - 2, 0); -1 with reviews == -1
+
+        ``weights``: as ``Catalogue.explain_words``; a tensor [n, F] weighs every review of owner n alike."""
+        R = int(self.hp['narre_num_reviews'])
+        if reviews is not None and (isinstance(reviews, bool) or not isinstance(reviews, (int, np.integer))
+                                    or not 1 <= reviews <= R):
+            raise ValueError('catalogue: explain_words reviews = %r outside 1 .. %d' % (reviews, R))
+        ids, pool, tower, pad, wt = self._phrase_request(ids, k, side, weights, per=R)
+        k, n, W = int(k), len(ids), int(self.hp['narre_num_words'])
+        self._flush()
+        with torch.no_grad():
+            pos, score, filt, tokens, win = self._phrase_rows(tower, pool, ids, k, wt, narre_pad=pad)
+        pos, score, filt, tokens, win = (pos.view(n, R, k), score.view(n, R, k), filt.view(n, R, k),
+                                         tokens.view(n, R, k, 3), win.view(n, R))
+        slot = torch.arange(R, dtype=torch.int64, device=self.dev)[None, :].expand(n, R)
+        listed = None
+        if reviews is not None:
+            e = self.explain(ids, k=int(reviews), side=side)
+            listed, slot = e, e.slots
+            take, none = slot.clamp(min=0), slot < 0
+
+            def pick(t, fill):                                 # the rows of the listed slots; the fill where none is
+                tail = (1,) * (t.dim() - 2)
+                rows = t.gather(1, take.view(take.shape + tail).expand(take.shape + t.shape[2:]))
+                return rows.masked_fill(none.view(none.shape + tail), fill)
+            pos, score, filt, tokens, win = pick(pos, -1), pick(score, 0), pick(filt, 0), pick(tokens, -1), pick(win, 0)
+        _, rev_off, first, _ = pool.device(self.dev)
+        own = torch.from_numpy(ids).to(self.dev)
+        rev = first[own][:, None] + slot                                           # the slot's review in the pool
+        held = (slot >= 0) & (rev < first[own + 1][:, None])
+        rev = torch.where(held, rev, torch.zeros_like(rev)).clamp(max=max(rev_off.numel() - 2, 0))
+        length = (rev_off[(rev + 1).clamp(max=rev_off.numel() - 1)] - rev_off[rev]).clamp(max=W)
+        t0 = (pos.to(torch.int64) - 2).clamp(min=0)
+        inside = (pos >= 0) & held[:, :, None] & (t0 < length[:, :, None])
+        minus = torch.full_like(t0, -1)
+        out_rev = torch.where(inside, rev[:, :, None].expand_as(t0), minus)
+        out_off = torch.where(inside, t0, minus)
+        return Phrases(pos.contiguous(), score.contiguous(), filt.contiguous(), tokens.contiguous(), out_rev, out_off,
+                       win.contiguous(), None if listed is None else listed.slots, None if listed is None else listed.weights)
+
     def refresh(self):
         self._flush()
         m = self.model
@@ -1137,6 +1346,11 @@ class TransNetCatalogue(Catalogue):
         src = self.model.source
         return ((self.reader.store.users, src.user_conv, 'user_embedding') if side == 'user' else
                 (self.reader.store.items, src.item_conv, 'item_embedding'))
+
+    def _phrase_side(self, side):
+        """``explain_words`` reads the SOURCE towers: they are what scores a pair at test time."""
+        pool, tower, _ = self._source(side)
+        return pool, tower, None
 
     def _side(self, P, side, ids, sel, z=None):
         """``fold_transnet_head`` of the owners ``ids`` (a host int64 array; ``sel``: the same ids on the device;
@@ -1418,4 +1632,40 @@ def write_explanations(path, model, hyper_params, train_reader, k, engine=None):
     with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
         np.savez(f, items=cat.eligible, slots=e.slots.cpu().numpy(), reviews=e.reviews.cpu().numpy(),
                  reviewers=e.reviewers.cpu().numpy(), weights=e.weights.cpu().numpy())
+    return path
+
+
+def _phrase_class(hyper_params):
+    """The class whose ``explain_words`` serves this model type (``phrase_limits`` accepted it)."""
+    mt = hyper_params['model_type']
+    return {'deepconn': Catalogue, 'deepconn++': ReluCatalogue, 'NARRE': NarreCatalogue}.get(mt, TransNetCatalogue)
+
+
+def check_explain_words_request(hyper_params):
+    """main's hook asked for (hyper_params['explain_words_k'])?  Then refuse, BEFORE any training, a model type without
+    a TextCNN tower (``phrase_limits``' reason) or that its class cannot serve, a k that is no int in 1 .. 100 (the
+    towers' filter count), a request without a file to write and an unknown ``catalogue_towers``."""
+    if not hyper_params.get('explain_words_k'):
+        return
+    why_not = phrase_limits(hyper_params) or _phrase_class(hyper_params)._limits(hyper_params)
+    if why_not is not None:
+        raise RuntimeError("hyper_params['explain_words_k']: " + why_not)
+    k = hyper_params['explain_words_k']
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PHRASE_FILTERS:
+        raise RuntimeError("hyper_params['explain_words_k'] must be an int in 1 .. %d, got %r" % (PHRASE_FILTERS, k))
+    if not hyper_params.get('explain_words_path'):
+        raise RuntimeError("hyper_params['explain_words_k'] needs hyper_params['explain_words_path'] (the .npz to write)")
+    _check_towers_request(hyper_params)
+
+
+def write_phrases(path, model, hyper_params, train_reader, k, engine=None):
+    """main.main's hook: the k heaviest word windows of every eligible item (``explain_words``; NARRE: of each of its R
+    reviews) -> an .npz of items / positions / scores / filters / tokens / reviews / offsets."""
+    cat = _phrase_class(hyper_params)(model, hyper_params, train_reader, engine=engine,
+                                      towers=hyper_params.get('catalogue_towers', 'host'))
+    p = cat.explain_words(cat.eligible, k=int(k), side='item')
+    with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
+        np.savez(f, items=cat.eligible, positions=p.positions.cpu().numpy(), scores=p.scores.cpu().numpy(),
+                 filters=p.filters.cpu().numpy(), tokens=p.tokens.cpu().numpy(), reviews=p.reviews.cpu().numpy(),
+                 offsets=p.offsets.cpu().numpy())
     return path
