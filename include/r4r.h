@@ -1598,6 +1598,63 @@ int r4r_tower_span_phrases(const int32_t *tok, const int64_t *rev_off, const int
                            int32_t *top_pos, float *top_score, int32_t *top_filters, int64_t *top_tok, int32_t *n_windows,
                            int64_t *neigh, void *ws, size_t ws_bytes, int64_t *groups_done, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Pair gradients: the model's prediction for explicit (user, item) pairs, its gradient with respect to the two tower
+ * latents, and that gradient carried back to each tower's pooled features (csrc/pair_grad.hip).  The last is the
+ * per-row filter weight r4r_textcnn_phrases takes (wt_stride == F): the windows listed with it are the words behind ONE
+ * pair's score, not behind an owner.  One launch over the model's RAW head parameters; nothing is folded.
+ *   zu [n_u, L], zi [n_i, L]  the eval-mode tower outputs z = fc.weight pooled + fc.bias (the dropout of
+ *                             common_pytorch_models.py:37 is the identity in eval mode); x = [zu[u_idx[p]] ; zi[i_idx[p]]]
+ *   fc_u, fc_i [L, F]         the towers' fc.weight:  w_user[p, f] = sum_l g_user[p, l] fc_u[l, f], w_item likewise
+ *   q_bias [n_u], c_bias [n_i]  every scalar of the score (bias tables, global bias, lin.bias, final.3.bias), indexed as
+ *                             zu / zi are; NULL counts as 0: the convention of r4r_pair_<form>
+ *   kind R4R_PAIR_GRAD_FM -- deepconn (DeepCoNN.py:61-66; TorchFM, common_pytorch_models.py:49-57).  V [2L, 8], lw [2L]:
+ *     s_k = sum_j x_j V_jk      score = q_bias + c_bias + sum_j lw_j x_j + 1/2 (sum_k s_k^2 - sum_j x_j^2 sum_k V_jk^2)
+ *     g_j = lw_j + sum_k s_k V_jk - x_j sum_k V_jk^2
+ *   kind R4R_PAIR_GRAD_MLP -- deepconn++ (DeepCoNN.py:68-72).  W0 [L, 2L], b0 [L], w3 [L]:
+ *     a = W0 x + b0             score = sum_m w3_m max(a_m, 0) + q_bias + c_bias
+ *     g_j = sum_m [a_m > 0] w3_m W0[m, j]                       (the ReLU's derivative at 0 is 0, as in torch)
+ *   kind R4R_PAIR_GRAD_PFM -- transnet / transnet++ at test time (TransNet.py:25-35, 105-114).  W0, b0 as above,
+ *     W2 [L, L], b2 [L], V [2P + L, 8], lw [2P + L]; xu [*, P], xi [*, P] the id-embedding tables, rows u_idx / i_idx
+ *     (P = 5 for transnet++, TransNet.py:75-76, 108-110; P = 0: no row is read and xu, xi may be NULL):
+ *     a = W0 x + b0, ir = W2 max(a, 0) + b2, y = [xu[u] ; xi[i] ; ir]; the score is the fm expression over y, gy the fm
+ *     gradient over y, and g = W0^T ([a > 0] o (W2^T gy[2P:])).
+ * Fixed fp32 order (one wave per pair; "chain": fmaf accumulation from 0.0f in ascending index):
+ *   rows   a_m (and ir_m): 16 lanes per m, lane c chains j = c, c + 16, ..; the 16 partials are added by the steps
+ *          xor 1, xor 2, rotate 4, rotate 8 within the 16 (v += partner each time); then + b_m.
+ *   cols   g_j = chain over m of upstream_m W0[m, j]; W2^T gy and w = g fc likewise (chain over the row index).  A
+ *          masked unit enters the chain as 0.0f.
+ *   fm     lane (jg, k), jg = lane / 8, k = lane % 8, chains j = jg, jg + 8, ..; s_k = ((p_0k + p_1k) + ..) + p_7k.
+ *          Per j: v2_j = chain over k of V_jk^2, dot_j = chain over k of s_k V_jk, g_j = fmaf(-x_j, v2_j, lw_j + dot_j).
+ *          lin = wave sum of the lanes' chains (j = lane, lane + 64, ..) of lw_j x_j; q2 likewise of fmaf(x_j x_j, v2_j, .)
+ *          with x_j x_j rounded first; wave sum = the four steps above, then (r_0 + r_16) + (r_32 + r_48) over the four
+ *          16-lane totals.  ss = chain over k of s_k^2.  fm = fmaf(0.5f, ss - q2, lin).
+ *   mlp    score's sum = wave sum of w3_m max(a_m, 0), lane = m.
+ *   score  out_score = (head + q_bias) + c_bias.
+ * A pair's outputs depend on that pair's inputs only: not on n_p, not on which pairs share the call, not on the grid, not
+ * on which outputs are NULL; the same pair gives the same bits alone, inside a batch and in a permuted batch.
+ * Limits: fm 1 <= L <= 128; mlp, pfm 1 <= L <= 64 (the native steps' limits); 0 <= P <= 8 (0 unless pfm);
+ * 1 <= F <= 112; n_u, n_i >= 0; 0 <= n_p < 2^31.  Refused before the launch and before the first dereference, in the
+ * entry point's own name: an unknown kind, a limit above, a null pointer among the kind's parameters (xu / xi with
+ * P > 0), w_user without fc_u, w_item without fc_i and, with n_p > 0, null zu / zi / u_idx / i_idx or n_u / n_i == 0.
+ * n_p == 0 returns R4R_OK and enqueues nothing.  Every output may be NULL.  An index outside [0, n_u) / [0, n_i) is the
+ * caller's error, as in r4r_pair_dot.  Nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+#define R4R_PAIR_GRAD_FM 0
+#define R4R_PAIR_GRAD_MLP 1
+#define R4R_PAIR_GRAD_PFM 2
+int r4r_pair_grad(int kind, const float *zu, int64_t n_u, const float *zi, int64_t n_i,
+                  const int64_t *u_idx, const int64_t *i_idx, int64_t n_p,     /* [n_p] rows of zu / zi             */
+                  const float *q_bias, const float *c_bias,                     /* [n_u], [n_i]; NULL = 0            */
+                  const float *W0, const float *b0, const float *W2, const float *b2, const float *w3,
+                  const float *V, const float *lw,
+                  const float *xu, const float *xi, int P,                      /* pfm's id embeddings [*, P]        */
+                  const float *fc_u, const float *fc_i, int L, int F,           /* [L, F] each                       */
+                  float *out_score,                                             /* [n_p], nullable                   */
+                  float *g_user, float *g_item,                                 /* [n_p, L] each, nullable           */
+                  float *w_user, float *w_item,                                 /* [n_p, F] each, nullable           */
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

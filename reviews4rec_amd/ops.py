@@ -131,6 +131,74 @@ def textcnn_phrases(pooled, argmax, k, T, weights=None, idx=None):
     return pos, score, filters, tokens, windows
 
 
+PAIR_GRAD_KINDS = {'fm': 0, 'mlp': 1, 'pfm': 2}              # R4R_PAIR_GRAD_* of include/r4r.h
+PAIR_GRAD_OUTPUTS = ('score', 'g_user', 'g_item', 'w_user', 'w_item')
+_PAIR_GRAD_PARAMS = {'fm': ('V', 'lw'), 'mlp': ('W0', 'b0', 'w3'), 'pfm': ('W0', 'b0', 'W2', 'b2', 'V', 'lw')}
+
+
+def pair_grad(kind, zu, zi, u_idx, i_idx, q_bias=None, c_bias=None, W0=None, b0=None, W2=None, b2=None, w3=None, V=None,
+              lw=None, xu=None, xi=None, fc_u=None, fc_i=None, want=PAIR_GRAD_OUTPUTS):
+    """r4r_pair_grad (include/r4r.h, "Pair gradients"): for the pairs (u_idx[p], i_idx[p]) over the eval-mode tower
+    latents ``zu`` [n_u, L] / ``zi`` [n_i, L], the prediction, its gradient with respect to both latents and that
+    gradient carried back through ``fc_u`` / ``fc_i`` [L, F] (the towers' fc.weight) to the pooled features.
+
+    ``kind``: 'fm' (deepconn: ``V`` [2L, 8], ``lw`` [2L]), 'mlp' (deepconn++: ``W0`` [L, 2L], ``b0`` [L], ``w3`` [L]) or
+    'pfm' (transnet(++): ``W0``, ``b0``, ``W2`` [L, L], ``b2`` [L], ``V`` [2P + L, 8], ``lw`` [2P + L] and, with P > 0,
+    the id-embedding rows ``xu`` [n_u, P] / ``xi`` [n_i, P]).  ``q_bias`` [n_u] / ``c_bias`` [n_i]: the score's scalars,
+    None = 0.  ``want``: the outputs to compute, names of ``PAIR_GRAD_OUTPUTS``.  No autograd
+    -> a dict name -> tensor: score [n_p], g_user / g_item [n_p, L], w_user / w_item [n_p, F]."""
+    if kind not in PAIR_GRAD_KINDS:
+        raise RuntimeError('reviews4rec_amd.ops: pair_grad kind must be one of %r, got %r' % (tuple(PAIR_GRAD_KINDS), kind))
+    want = tuple(want)
+    if not want or set(want) - set(PAIR_GRAD_OUTPUTS):
+        raise RuntimeError('reviews4rec_amd.ops: pair_grad want must name some of %r, got %r' % (PAIR_GRAD_OUTPUTS, want))
+    zu, zi = _f32(zu, 'zu'), _f32(zi, 'zi')
+    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
+    if zu.dim() != 2 or zi.dim() != 2 or zu.shape[1] != zi.shape[1] or u_idx.numel() != i_idx.numel():
+        raise RuntimeError('reviews4rec_amd.ops: pair_grad takes zu [n_u, L], zi [n_i, L] and equally long u_idx / i_idx, '
+                           'got %s, %s, %d and %d' % (tuple(zu.shape), tuple(zi.shape), u_idx.numel(), i_idx.numel()))
+    n_u, n_i, L, n_p = int(zu.shape[0]), int(zi.shape[0]), int(zu.shape[1]), int(u_idx.numel())
+    given = dict(W0=W0, b0=b0, W2=W2, b2=b2, w3=w3, V=V, lw=lw, xu=xu, xi=xi, fc_u=fc_u, fc_i=fc_i, q_bias=q_bias,
+                 c_bias=c_bias)
+    given = {k: None if v is None else _f32(v, k) for k, v in given.items()}
+    P = 0
+    if kind == 'pfm' and given['xu'] is not None:
+        P = int(given['xu'].shape[1])
+    n = 2 * L if kind == 'fm' else 2 * P + L
+    shapes = dict(W0=(L, 2 * L), b0=(L,), W2=(L, L), b2=(L,), w3=(L,), V=(n, 8), lw=(n,), xu=(n_u, P), xi=(n_i, P),
+                  q_bias=(n_u,), c_bias=(n_i,))
+    for name in _PAIR_GRAD_PARAMS[kind]:
+        if given[name] is None:
+            raise RuntimeError('reviews4rec_amd.ops: pair_grad kind %r needs %s' % (kind, name))
+    for name, shape in shapes.items():
+        t = given[name]
+        if t is not None and name in ('w3', 'lw', 'b0', 'b2', 'q_bias', 'c_bias'):
+            t = given[name] = t.reshape(-1)
+        if t is not None and tuple(t.shape) != shape:
+            raise RuntimeError('reviews4rec_amd.ops: pair_grad %s must be %s, got %s' % (name, shape, tuple(t.shape)))
+    F = 1
+    for name, out in (('fc_u', 'w_user'), ('fc_i', 'w_item')):
+        t = given[name]
+        if t is None:
+            if out in want:
+                raise RuntimeError('reviews4rec_amd.ops: pair_grad %s needs %s' % (out, name))
+        elif t.dim() != 2 or t.shape[0] != L:
+            raise RuntimeError('reviews4rec_amd.ops: pair_grad %s must be [L, F] = [%d, F], got %s' % (name, L, tuple(t.shape)))
+        else:
+            F = int(t.shape[1])
+    if given['fc_u'] is not None and given['fc_i'] is not None and given['fc_u'].shape != given['fc_i'].shape:
+        raise RuntimeError('reviews4rec_amd.ops: pair_grad fc_u and fc_i must share a shape')
+    dev = zu.device
+    sizes = dict(score=(n_p,), g_user=(n_p, L), g_item=(n_p, L), w_user=(n_p, F), w_item=(n_p, F))
+    out = {name: torch.empty(sizes[name], dtype=torch.float32, device=dev) for name in PAIR_GRAD_OUTPUTS if name in want}
+    g = given
+    call('r4r_pair_grad', PAIR_GRAD_KINDS[kind], ptr(zu), n_u, ptr(zi), n_i, ptr(u_idx), ptr(i_idx), n_p, ptr(g['q_bias']),
+         ptr(g['c_bias']), ptr(g['W0']), ptr(g['b0']), ptr(g['W2']), ptr(g['b2']), ptr(g['w3']), ptr(g['V']), ptr(g['lw']),
+         ptr(g['xu']) if P else None, ptr(g['xi']) if P else None, P, ptr(g['fc_u']), ptr(g['fc_i']), L, F,
+         *(ptr(out.get(name)) for name in PAIR_GRAD_OUTPUTS))
+    return out
+
+
 def textcnn_wgrad_raw(idx, table, g_pooled, argmax, conv_w_shape):
     idx, table, g_pooled = _i64(idx, 'idx'), _f32(table, 'table'), _f32(g_pooled, 'g_pooled')
     E_model = table.shape[1]

@@ -85,6 +85,11 @@ every text class: the windows that won the max-pool of the side's TextCNN tower 
 by r4r_textcnn_phrases (csrc/phrases.hip) from the pooled values and argmax positions the tower forward returns, per chunk
 from the host or inside one r4r_tower_span_phrases call; NARRE gets one list per review, e.g. of the reviews ``explain`` names.
 
+Pair explanations -- why THIS item for THIS user -- are ``pair_weights`` / ``explain_pair`` on ``Catalogue`` (deepconn),
+``ReluCatalogue`` (deepconn++) and ``TransNetCatalogue``: the gradient of one pair's predicted rating with respect to each
+tower's pooled features, from r4r_pair_grad (csrc/pair_grad.hip) over the model's raw head parameters, handed to
+``explain_words`` as its per-row weights.  NARRE is refused (its gradient runs through the attention's softmax).
+
 There is no torch fallback: the order (score descending, ties by ascending item id, include/r4r.h) has one
 definition, the kernels'.
 """
@@ -783,7 +788,108 @@ class Catalogue:
         offsets = torch.where(inside, at - rev_off[review.clamp(min=0, max=rev_off.numel() - 1)], minus)
         return Phrases(pos, score, filt, tokens, reviews, offsets, win)
 
+    # ------------------------------------------------------------------ pair explanations: the words behind ONE score
+    _pair_kind = 'fm'      # r4r_pair_grad's kind for this class's head (ops.PAIR_GRAD_KINDS)
 
+    def _pair_limits(self):
+        """None when ``pair_weights`` / ``explain_pair`` serve this configuration, else the reason."""
+        return phrase_limits(self.hp)
+
+    def _pair_head(self, u, i):
+        """The RAW head parameters ``ops.pair_grad`` takes for this class's kind, with the score's scalars of the users
+        ``u`` / the items ``i`` (device int64, the rows of zu / zi) summed in float64 and rounded once.  deepconn
+        (DeepCoNN.py:61-66): the FM over [user | item]; lin.bias and the global bias are the only scalars."""
+        m = self.model
+        f64 = lambda t: t.detach().to(torch.float64).reshape(())
+        qb = (f64(m.fm.lin.bias) + f64(m.global_bias)).to(torch.float32)
+        return dict(V=m.fm.V.detach(), lw=m.fm.lin.weight.detach().reshape(-1), q_bias=qb.expand(u.numel()).contiguous())
+
+    def _pair_request(self, users, items):
+        """``pair_weights``' checks of the ids, before anything runs -> (users, items) as host int64 tensors: equally
+        long, every id an owner of its side's review pool."""
+        u = torch.as_tensor(users, dtype=torch.int64).reshape(-1).cpu()
+        i = torch.as_tensor(items, dtype=torch.int64).reshape(-1).cpu()
+        if i.numel() != u.numel():
+            raise ValueError('catalogue: %d users against %d items' % (u.numel(), i.numel()))
+        for ids, side in ((u, 'user'), (i, 'item')):
+            pool = self._phrase_side(side)[0]
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= pool.owners):
+                raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
+        return u, i
+
+    def _pair_weights(self, u, i):
+        """``pair_weights`` of checked host id tensors: the towers of the DISTINCT users and items through ``_latents``,
+        then ONE r4r_pair_grad call."""
+        self._flush()
+        (pool_u, tower_u, _), (pool_i, tower_i, _) = self._phrase_side('user'), self._phrase_side('item')
+        fc_u, fc_i = tower_u.fc.weight.detach(), tower_i.fc.weight.detach()
+        L, F = (int(d) for d in fc_u.shape)
+        n = int(u.numel())
+        if n == 0:
+            none = torch.empty((0, F), dtype=torch.float32, device=self.dev)
+            return none, none.clone(), torch.empty((0,), dtype=torch.float32, device=self.dev)
+        uu, u_inv = torch.unique(u, return_inverse=True)
+        ui, i_inv = torch.unique(i, return_inverse=True)
+        with torch.no_grad():
+            zu = torch.empty((uu.numel(), L), dtype=torch.float32, device=self.dev)
+            zi = torch.empty((ui.numel(), L), dtype=torch.float32, device=self.dev)
+            for sl, _, z in self._latents(tower_u, pool_u, uu.numpy()):
+                zu[sl] = z
+            for sl, _, z in self._latents(tower_i, pool_i, ui.numpy()):
+                zi[sl] = z
+            out = ops.pair_grad(self._pair_kind, zu, zi, u_inv.to(self.dev), i_inv.to(self.dev), fc_u=fc_u, fc_i=fc_i,
+                                want=('score', 'w_user', 'w_item'), **self._pair_head(uu.to(self.dev), ui.to(self.dev)))
+        return out['w_user'], out['w_item'], out['score']
+
+    def pair_weights(self, users, items):
+        """Why THIS item for THIS user: for the pairs (users[p], items[p]) (lists, arrays or tensors on any device,
+        equally long; owners of the review pools, with or without a training rating)
+        -> (w_user float32 [n, F], w_item float32 [n, F], scores float32 [n]) on the device:
+
+            w_user[p, f]   d score(users[p], items[p]) / d pooled_f of the user tower: how much a unit of filter f's
+                           max-pooled activation moves the pair's predicted rating; w_item: the same of the item tower
+            scores[p]      the model's eval-mode prediction for the pair, from the raw head parameters (``score_pairs``
+                           reads the catalogue's folds: the same number by another fp32 chain, and -inf for an item
+                           that is not eligible, which this call does not look at)
+
+        The rows are what ``explain_words(..., weights=)`` takes.  The towers of the distinct users and items run once
+        through ``_latents`` (``towers`` 'host' and 'device': the same bits), then ONE r4r_pair_grad call (include/r4r.h,
+        "Pair gradients") over the model's current weights.  The engine's pending updates are flushed first, as
+        ``refresh()`` does; the training state is left untouched.  Unequal lengths raise ValueError, an id outside its
+        side's pool KeyError; a configuration without a tower is refused with the reason."""
+        why = self._pair_limits()
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        return self._pair_weights(*self._pair_request(users, items))
+
+    def explain_pair(self, users, items, k=5, direction='up'):
+        """The words behind one user-item score: for every pair, the ``k`` three-word windows of the USER's reviews and
+        the ``k`` windows of the ITEM's reviews that move the pair's predicted rating most
+        -> ``PairPhrases(user, item, scores)``: ``user`` is ``explain_words(users, k, 'user', weights=+-w_user)`` and
+        ``item`` is ``explain_words(items, k, 'item', weights=+-w_item)`` of ``pair_weights(users, items)``, bit for
+        bit (they are made by those calls), and ``scores`` its scores.  ``direction``: 'up' lists the windows that
+        RAISE the prediction most (+w: a window's score is the first-order change of the rating per unit of its
+        filters' activations, times those activations), 'down' the ones that lower it most (-w).  A window score below
+        zero under 'up' is a window that lowers the rating: the lists are sorted, not cut at zero.  Refusals as
+        ``pair_weights``', then a ``direction`` other than 'up' / 'down', ``k`` outside 1 .. F, unequal lengths
+        (ValueError) and an id outside its side's pool (KeyError), before anything is enqueued."""
+        why = self._pair_limits()
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        F = int(self._phrase_side('item')[1].convs[0].bias.numel())
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= F:
+            raise ValueError('catalogue: explain_pair k = %r outside 1 .. %d' % (k, F))
+        u, i = self._pair_request(users, items)
+        w_user, w_item, scores = self._pair_weights(u, i)
+        if direction == 'down':
+            w_user, w_item = -w_user, -w_item
+        return PairPhrases(self.explain_words(u, k=int(k), side='user', weights=w_user),
+                           self.explain_words(i, k=int(k), side='item', weights=w_item), scores)
+
+
+PairPhrases = namedtuple('PairPhrases', 'user item scores')      # Catalogue.explain_pair: two ``Phrases`` and [n] scores
 PHRASE_FILTERS = 100                # every TextCNN tower's filter count (common_pytorch_models.py:11)
 _PHRASE_TYPES = ('deepconn', 'deepconn++', 'transnet', 'transnet++', 'NARRE')
 Phrases = namedtuple('Phrases', 'positions scores filters tokens reviews offsets windows slots weights',
@@ -968,6 +1074,17 @@ class ReluCatalogue(Catalogue):
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.w), self.H, self.P)
 
+    _pair_kind = 'mlp'
+
+    def _pair_head(self, u, i):
+        """deepconn++ (DeepCoNN.py:68-72): final.0 / final.3 as they are; q_bias = user_bias + global_bias +
+        final.3.bias, c_bias = item_bias.  (NeuMF has no tower: ``_pair_limits`` refuses it before this is reached.)"""
+        m, P = self.model, self._params()
+        f64 = lambda t: t.detach().to(torch.float64)
+        qb = f64(m.user_bias)[u] + f64(P['global_bias']).reshape(()) + f64(P['final.3.bias']).reshape(())
+        return dict(W0=P['final.0.weight'], b0=P['final.0.bias'], w3=P['final.3.weight'].reshape(-1),
+                    q_bias=qb.to(torch.float32).contiguous(), c_bias=m.item_bias.detach()[i].contiguous())
+
 
 HMLP_MAX_L = 64                     # r4r_topk_hmlp: D <= 64, H <= 64
 NARRE_ATTN_MAX = 32                 # r4r_narre_attn_fwd: R <= 32, L <= 32; beyond, r4r_narre_explain (R, L <= 64)
@@ -1139,6 +1256,10 @@ class NarreCatalogue(Catalogue):
     def _phrase_side(self, side):
         _, pool, tower, pad = self._narre_side(side)
         return pool, tower, pad
+
+    def _pair_limits(self):
+        return ("model_type 'NARRE' has no pair explanation: its review latents reach the score through the softmax "
+                "of the review attention (NARRE.py:53-64), and a gradient through it is not built")
 
     def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
         """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
@@ -1392,6 +1513,20 @@ class TransNetCatalogue(Catalogue):
     def _head(self, q, n, qb):
         return (ptr(q), n, ptr(qb), ptr(self.c), self.n_c, self.D, ptr(self.c_bias), ptr(self.W), ptr(self.b), ptr(self.s),
                 ptr(self.l), self.H, self.P, self.M)
+
+    _pair_kind = 'pfm'
+
+    def _pair_head(self, u, i):
+        """The TransNets at test time (TransNet.py:25-35, 105-114): source.project and source_fm as they are, and for
+        transnet++ the id-embedding rows of the owners; source_fm.lin.bias is the only scalar."""
+        m, P = self.model, self._params()
+        qb = P['source_fm.lin.bias'].to(torch.float32).reshape(1).expand(u.numel()).contiguous()
+        head = dict(W0=P['source.project.0.weight'], b0=P['source.project.0.bias'], W2=P['source.project.2.weight'],
+                    b2=P['source.project.2.bias'], V=P['source_fm.V'], lw=P['source_fm.lin.weight'].reshape(-1), q_bias=qb)
+        if self.pp:
+            head.update(xu=getattr(m, self._source('user')[2]).weight.detach()[u].contiguous(),
+                        xi=getattr(m, self._source('item')[2]).weight.detach()[i].contiguous())
+        return head
 
 
 PFM_MAX_L = 64                      # r4r_topk_pfm: H <= 64, G <= 64, M <= 128
@@ -1668,4 +1803,50 @@ def write_phrases(path, model, hyper_params, train_reader, k, engine=None):
         np.savez(f, items=cat.eligible, positions=p.positions.cpu().numpy(), scores=p.scores.cpu().numpy(),
                  filters=p.filters.cpu().numpy(), tokens=p.tokens.cpu().numpy(), reviews=p.reviews.cpu().numpy(),
                  offsets=p.offsets.cpu().numpy())
+    return path
+
+
+def check_explain_pairs_request(hyper_params):
+    """main's hook asked for (hyper_params['explain_pairs_k'])?  Then refuse, BEFORE any training, a model type the
+    hooks' classes cannot explain (``phrase_limits``' reason, else ``hook_limits``': deepconn and deepconn++ are the types
+    ``make_catalogue`` serves), a k that is no int in 1 .. 100 (the towers' filter count), a request without a file to
+    write, one without ``recommend_k`` (the pairs explained are the recommended ones) and an unknown ``catalogue_towers``."""
+    if not hyper_params.get('explain_pairs_k'):
+        return
+    why_not = phrase_limits(hyper_params) or hook_limits(hyper_params)
+    if why_not is not None:
+        raise RuntimeError("hyper_params['explain_pairs_k']: " + why_not)
+    k = hyper_params['explain_pairs_k']
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= PHRASE_FILTERS:
+        raise RuntimeError("hyper_params['explain_pairs_k'] must be an int in 1 .. %d, got %r" % (PHRASE_FILTERS, k))
+    if not hyper_params.get('explain_pairs_path'):
+        raise RuntimeError("hyper_params['explain_pairs_k'] needs hyper_params['explain_pairs_path'] (the .npz to write)")
+    if not hyper_params.get('recommend_k'):
+        raise RuntimeError("hyper_params['explain_pairs_k'] needs hyper_params['recommend_k']: the pairs it explains are "
+                           "every user's recommended items")
+    _check_towers_request(hyper_params)
+
+
+def recommended_pairs(cat, k):
+    """(users, items) int64 host arrays: every training user's ``recommend(k)`` list, row-major, unused slots dropped."""
+    users = np.array(sorted(int(u) for u in cat.reader.user_count), dtype=np.int64)
+    items = cat.recommend(users, k=int(k))[0].cpu().numpy()
+    keep = items >= 0
+    return np.repeat(users, items.shape[1]).reshape(items.shape)[keep], items[keep]
+
+
+def write_pair_phrases(path, model, hyper_params, train_reader, k, engine=None):
+    """main.main's hook: ``explain_pair`` ('up') of every training user's ``recommend_k`` list -> an .npz whose rows are
+    the n pairs' user sides followed by the n pairs' item sides: users / items (the row's pair), side (0: the windows of
+    the user's reviews, 1: of the item's), pair_scores (the pair's prediction), and ``write_phrases``' positions / scores
+    / filters / tokens / reviews / offsets of that side."""
+    cat = make_catalogue(model, hyper_params, train_reader, engine=engine)
+    users, items = recommended_pairs(cat, hyper_params['recommend_k'])
+    e = cat.explain_pair(users, items, k=int(k))
+    both = lambda name: np.concatenate([getattr(e.user, name).cpu().numpy(), getattr(e.item, name).cpu().numpy()])
+    n = len(users)
+    with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
+        np.savez(f, users=np.tile(users, 2), items=np.tile(items, 2), side=np.repeat(np.array([0, 1], np.int8), n),
+                 pair_scores=np.tile(e.scores.cpu().numpy(), 2), positions=both('positions'), scores=both('scores'),
+                 filters=both('filters'), tokens=both('tokens'), reviews=both('reviews'), offsets=both('offsets'))
     return path
