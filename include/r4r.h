@@ -1655,6 +1655,83 @@ int r4r_pair_grad(int kind, const float *zu, int64_t n_u, const float *zi, int64
                   float *w_user, float *w_item,                                 /* [n_p, F] each, nullable           */
                   void *stream);
 
+/* ------------------------------------------------------------------------
+ * NARRE pair gradients: the reviews and the words behind ONE user-item score of NARRE (csrc/narre_pair.hip).  NARRE's
+ * review latents reach the score through the softmax of the review attention (NARRE.attention, NARRE.py:53-64; the
+ * scorer of NARRE.py:24-36), so the gradient of a score with respect to a review's pooled features has a direct part
+ * (through a_r z_r) and a part through the review's logit.  It splits into a pass per OWNER, which does all the matrix
+ * work of a review once, and a pass per PAIR, which is two L x L and two L x F matvecs plus O(R (L + F)) combining.
+ * One side (user or item), eval mode, with z_r = fc pooled_r + fc.bias, fc [L, F] the side's tower fc.weight:
+ *   pre_r = W0 [z_r ; other_table[nb_r]] + b0     a = softmax_R(w3 . relu(pre_r) + b3)     o = sum_r a_r z_r
+ *   p = o + own_table[owner]
+ * The head (NARRE.py:38-46, 115-124; dropout is the identity in eval mode): x = p_u o p_i, t = W1 x + b1 (final.1),
+ * score = w . relu(t) + scalars (final.3 and the three biases).
+ *   per pair    gx = W1^T ([t > 0] o w),  g_u = gx o p_i,  g_i = gx o p_u;  per side with its g:
+ *               ga_r = g . z_r,  dot = sum_r a_r ga_r,  delta_r = a_r (ga_r - dot)  (= d score / d logit_r; sums to 0)
+ *   per owner   D_r = sum_m [pre_rm > 0] w3_m W0[m, 0:L]   [R, L]   (the ReLU's derivative at 0 is 0, as in torch)
+ *               E_r = D_r fc   [R, F]          dz_r = D_r . z_r   [R]
+ *   result      w[r, f] = d score / d pooled[r, f] = a_r (g fc)_f + delta_r E[r, f]: the per-review filter weights
+ *               r4r_textcnn_phrases takes (wt_stride == F, one row per review)
+ *               rev_r = a_r ga_r + delta_r dz_r  (gradient . input): how much review r carries THIS pair's score
+ *
+ * r4r_narre_attn_jac -- the owner pass: r4r_narre_explain's inputs plus fc; one wave per owner, one launch.
+ *   attn, out   r4r_narre_explain's bits for the same inputs (the same instruction sequence); pooled_attn is out before
+ *               the own row is added (o above).  An nb id outside [0, other_rows) reads as a row of zeros.
+ *   Fixed fp32 order of the new outputs ("chain": fmaf accumulation from 0.0f in ascending index):
+ *     D[r, j]   chain over m of c_m W0[m, j], c_m = w3_m where pre_rm > 0 (the bits of r4r_narre_explain's pre), else
+ *               0.0f: a masked unit enters the chain as 0.0f
+ *     dz[r]     wave sum over the lanes j of D[r, j] z[r, j] (the product rounded; 0 in the lanes past L): the steps
+ *               xor 1, xor 2, rotate 4, rotate 8 within each 16 lanes, then (r_0 + r_16) + (r_32 + r_48)
+ *     E[r, f]   chain over l of D[r, l] fc[l, f]
+ *   An owner's outputs depend on that owner's inputs and the weights only: not on N, not on which owners share a call,
+ *   not on which outputs are NULL.  Limits: 1 <= R <= 64, 1 <= L <= 64, 1 <= F <= 112, N >= 0, other_rows >= 0;
+ *   own_table and owner both or neither; E needs fc; at least one output.  N == 0 returns R4R_OK and enqueues nothing.
+ *
+ * r4r_narre_pair_grad -- the pair pass over the owner pass's outputs of both sides (p = its `out`); one wave per pair,
+ *   one launch.  The two sides may have different R.  Fixed fp32 order:
+ *     x_l = p_u[l] p_i[l];  t_m: "rows" of the Pair gradients section (16 lanes per m, lane c chains j = c, c + 16, ..,
+ *     the steps xor 1, xor 2, rotate 4, rotate 8, then + b1_m);  head = wave sum of w_m max(t_m, 0), lane = m;
+ *     gx_j = chain over m of ([t_m > 0] w_m) W1[m, j];  g_u[l] = gx_l p_i[l],  g_i[l] = gx_l p_u[l]
+ *     ga_r: "rows" over z_r without a bias;  dot = chain over r of a_r ga_r;  delta_r = a_r (ga_r - dot): exactly 0 at
+ *     R == 1 (a_0 == 1.0f);  b_f = chain over l of g_l fc[l, f]
+ *     w[r, f] = fmaf(delta_r, E[r, f], a_r b_f)        rev_r = fmaf(delta_r, dz_r, a_r ga_r)   (products rounded first)
+ *     out_score = (head + q_bias) + c_bias;  q_bias [n_u] / c_bias [n_i] hold every scalar of the score, NULL counts as 0
+ *   A pair's outputs depend on that pair's inputs only: not on n_p, the grid, the other pairs or which outputs are NULL;
+ *   the same pair gives the same bits alone, inside a batch and in a permuted batch.  Every output is indexed with 64-bit
+ *   offsets; a pair's [R, F] block is stored contiguously by full waves.
+ *   Limits: the owner pass's for R_u, R_i, L, F; n_u, n_i >= 0; 0 <= n_p < 2^31.  Refused before the launch and the first
+ *   dereference, in the entry point's own name: a limit; w_user without fc_u or E_u, rev_user without dz_u, any of
+ *   glogit_user / rev_user / w_user without z_u and attn_u (the item side likewise); with n_p > 0 a null p_u, p_i,
+ *   u_idx, i_idx, W1, b1 or w, and n_u or n_i == 0.  n_p == 0 returns R4R_OK and enqueues nothing.  An index outside
+ *   [0, n_u) / [0, n_i) is the caller's error.  Nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_narre_attn_jac(const float *z,            /* [N, R, L] review latents                              */
+                       const int64_t *nb,         /* [N, R] neighbour ids, rows of other_table             */
+                       const float *other_table, int64_t other_rows,   /* [other_rows, L]                  */
+                       const float *own_table, const int64_t *owner,   /* [*, L], [N]; both NULL: no add   */
+                       const float *W0, const float *b0, const float *w3, const float *b3,
+                       const float *fc, int F,    /* [L, F] the side's tower fc.weight; needed for E       */
+                       float *attn,               /* [N, R]  softmax weights; nullable                     */
+                       float *pooled_attn,        /* [N, L]  o, without the own row; nullable              */
+                       float *out,                /* [N, L]  p = o + own_table[owner]; nullable            */
+                       float *D,                  /* [N, R, L] nullable                                    */
+                       float *E,                  /* [N, R, F] nullable                                    */
+                       float *dz,                 /* [N, R]  nullable                                      */
+                       int64_t N, int R, int L, void *stream);
+int r4r_narre_pair_grad(const float *p_u, const float *z_u, const float *attn_u, const float *E_u, const float *dz_u,
+                        const float *fc_u, int64_t n_u, int R_u,     /* [n_u, L], [n_u, R_u, L], [n_u, R_u], [n_u, R_u, F], [n_u, R_u], [L, F] */
+                        const float *p_i, const float *z_i, const float *attn_i, const float *E_i, const float *dz_i,
+                        const float *fc_i, int64_t n_i, int R_i,     /* the item side likewise                */
+                        const int64_t *u_idx, const int64_t *i_idx, int64_t n_p,    /* [n_p] rows of the sides   */
+                        const float *q_bias, const float *c_bias,                    /* [n_u], [n_i]; NULL = 0    */
+                        const float *W1, const float *b1, const float *w, int L, int F,   /* [L, L], [L], [L]     */
+                        float *out_score,                                            /* [n_p], nullable           */
+                        float *g_user, float *g_item,                                /* [n_p, L] each, nullable   */
+                        float *glogit_user, float *glogit_item,                      /* [n_p, R_u] / [n_p, R_i]   */
+                        float *rev_user, float *rev_item,                            /* [n_p, R_u] / [n_p, R_i]   */
+                        float *w_user, float *w_item,                   /* [n_p, R_u, F] / [n_p, R_i, F], nullable */
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -663,7 +663,8 @@ class Catalogue:
         return (self.reader.store.users, m.user_conv, None) if side == 'user' else (self.reader.store.items, m.item_conv, None)
 
     def _phrase_weights(self, tower, weights, n, per):
-        """``explain_words``' ``weights`` as what the kernel takes: None, [F] or one row per document [n per, F]."""
+        """``explain_words``' ``weights`` as what the kernel takes: None, [F] or one row per document [n per, F].  NARRE
+        (``per`` = R > 1) also takes one row per REVIEW, [n, R, F]."""
         F = int(tower.convs[0].bias.numel())
         if weights is None:
             return None
@@ -671,11 +672,14 @@ class Catalogue:
             if weights != 'latent':
                 raise ValueError("catalogue: weights must be None, 'latent' or a tensor [F] / [n, F], got %r" % (weights,))
             return tower.fc.weight.detach().norm(dim=0).to(torch.float32).contiguous()
-        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or \
-                tuple(weights.shape) not in ((F,), (n, F)):
-            raise ValueError("catalogue: weights must be None, 'latent' or a float32 tensor [%d] / [%d, %d], got %s"
-                             % (F, n, F, tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__))
+        shapes = ((F,), (n, F)) + (((n, per, F),) if per > 1 else ())
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) not in shapes:
+            raise ValueError("catalogue: weights must be None, 'latent' or a float32 tensor [%d] / [%d, %d]%s, got %s"
+                             % (F, n, F, ' / [%d, %d, %d]' % (n, per, F) if per > 1 else '',
+                                tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights).__name__))
         weights = weights.detach().to(self.dev).contiguous()
+        if weights.dim() == 3:
+            return weights.reshape(n * per, F)                 # a row per review already
         if weights.dim() == 2 and per > 1:
             weights = weights.repeat_interleave(per, dim=0).contiguous()      # an owner's row for each of its reviews
         return weights
@@ -856,7 +860,8 @@ class Catalogue:
         through ``_latents`` (``towers`` 'host' and 'device': the same bits), then ONE r4r_pair_grad call (include/r4r.h,
         "Pair gradients") over the model's current weights.  The engine's pending updates are flushed first, as
         ``refresh()`` does; the training state is left untouched.  Unequal lengths raise ValueError, an id outside its
-        side's pool KeyError; a configuration without a tower is refused with the reason."""
+        side's pool KeyError; a configuration without a tower is refused with the reason.  NARRE is refused here too: its
+        answer is per review and lives under ``NarreCatalogue.pair_reviews`` / ``explain_pair_reviews``."""
         why = self._pair_limits()
         if why is not None:
             raise RuntimeError('reviews4rec_amd.recommend: ' + why)
@@ -890,6 +895,8 @@ class Catalogue:
 
 
 PairPhrases = namedtuple('PairPhrases', 'user item scores')      # Catalogue.explain_pair: two ``Phrases`` and [n] scores
+PairReviews = namedtuple('PairReviews', 'w_user w_item rev_user rev_item glogit_user glogit_item attention_user '
+                         'attention_item live_user live_item scores')          # NarreCatalogue.pair_reviews
 PHRASE_FILTERS = 100                # every TextCNN tower's filter count (common_pytorch_models.py:11)
 _PHRASE_TYPES = ('deepconn', 'deepconn++', 'transnet', 'transnet++', 'NARRE')
 Phrases = namedtuple('Phrases', 'positions scores filters tokens reviews offsets windows slots weights',
@@ -1167,18 +1174,28 @@ class NarreCatalogue(Catalogue):
         return ((True, self.reader.store.users, m.user_conv, self.n_items + 1) if user else
                 (False, self.reader.store.items, m.item_conv, self.n_users + 1))
 
-    def _attend(self, side, z, nb, ids, explain_k=None):
+    def _attend(self, side, z, nb, ids, explain_k=None, jac=False):
         """The eval-mode attention over review latents ``z`` [n, R, L] weighed by the neighbours ``nb`` [n, 10], plus
         the id embedding of the owners ``ids`` (a host int64 array).  Where r4r_narre_attn_fwd takes the shape (R and L
         up to 32) it is that call, as before; beyond, r4r_narre_explain's ``out`` with the owners' rows added in the
         kernel.  ``explain_k``: no pooled vector but ``explain``'s pieces of these owners, from r4r_narre_explain at
-        every L -> (attention [n, R], top_slot int32 [n, k], top_w [n, k], live int32 [n], nb)."""
+        every L -> (attention [n, R], top_slot int32 [n, k], top_w [n, k], live int32 [n], nb).  ``jac``: the owner pass
+        of ``pair_reviews``, r4r_narre_attn_jac at every L -> a dict with p, z, attn, E, dz (``ops.narre_pair_grad``'s
+        side) and live int64 [n]."""
         m, user = self.model, side == 'user'
         scorer = m.attention_scorer_user if user else m.attention_scorer_item
         own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
         weights = (scorer[0].weight.detach(), scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach())
         ids = np.asarray(ids, dtype=np.int64)
         with torch.no_grad():
+            if jac:
+                _, pool, tower, _ = self._narre_side(side)
+                got = ops.narre_attn_jac(z, nb, other.weight.detach(), *weights, fc=tower.fc.weight.detach(),
+                                         own_table=own.weight.detach(), owner=torch.from_numpy(ids).to(self.dev),
+                                         want=('attn', 'out', 'E', 'dz'))
+                live = np.minimum(pool.first[ids + 1] - pool.first[ids], z.shape[1]).astype(np.int64)
+                return dict(p=got['out'], z=z, attn=got['attn'], E=got['E'], dz=got['dz'],
+                            live=torch.from_numpy(live).to(self.dev))
             if explain_k is not None:
                 first = self._narre_side(side)[1].first
                 live = torch.from_numpy(np.minimum(first[ids + 1] - first[ids], z.shape[1]).astype(np.int32)).to(self.dev)
@@ -1261,6 +1278,123 @@ class NarreCatalogue(Catalogue):
         return ("model_type 'NARRE' has no pair explanation: its review latents reach the score through the softmax "
                 "of the review attention (NARRE.py:53-64), and a gradient through it is not built")
 
+    # ------------------------------------------------------------------ pair explanations per REVIEW
+    pair_batch = 8192      # pairs per r4r_narre_pair_grad call of ``pair_reviews``; set after construction
+
+    def _pair_reviews(self, u, i):
+        """``pair_reviews`` of checked host id tensors."""
+        self._flush()
+        m = self.model
+        R = int(self.hp['narre_num_reviews'])
+        n = int(u.numel())
+        F = int(m.user_conv.fc.weight.shape[1])
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
+        i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=self.dev)
+        out = PairReviews(f32(n, R, F), f32(n, R, F), f32(n, R), f32(n, R), f32(n, R), f32(n, R), f32(n, R), f32(n, R),
+                          i64(n), i64(n), f32(n))
+        if n == 0:
+            return out
+        uu, u_inv = torch.unique(u, return_inverse=True)
+        ui, i_inv = torch.unique(i, return_inverse=True)
+        with torch.no_grad():
+            sides = []
+            for side, ids in (('user', uu), ('item', ui)):
+                parts = [part for _, part in self._attended_chunks(side, ids.numpy(), jac=True)]
+                s = {key: torch.cat([part[key] for part in parts]).contiguous() for key in parts[0]}
+                s['fc'] = self._narre_side(side)[2].fc.weight.detach()
+                sides.append(s)
+            su, si = sides
+            f64 = lambda t: t.detach().to(torch.float64)
+            qb = (f64(m.user_bias).reshape(-1)[uu.to(self.dev)] + f64(m.global_bias).reshape(())
+                  + f64(m.final[3].bias).reshape(())).to(torch.float32).contiguous()
+            cb = m.item_bias.detach().reshape(-1)[ui.to(self.dev)].to(torch.float32).contiguous()
+            W1, b1, w = m.final[1].weight.detach(), m.final[1].bias.detach(), m.final[3].weight.detach().reshape(-1)
+            u_inv, i_inv = u_inv.to(self.dev), i_inv.to(self.dev)
+            step = max(1, int(self.pair_batch))
+            for s0 in range(0, n, step):
+                sl = slice(s0, s0 + step)
+                got = ops.narre_pair_grad(su, si, u_inv[sl].contiguous(), i_inv[sl].contiguous(), W1, b1, w, q_bias=qb,
+                                          c_bias=cb, want=('score', 'glogit_user', 'glogit_item', 'rev_user', 'rev_item',
+                                                           'w_user', 'w_item'))
+                out.w_user[sl], out.w_item[sl] = got['w_user'], got['w_item']
+                out.rev_user[sl], out.rev_item[sl] = got['rev_user'], got['rev_item']
+                out.glogit_user[sl], out.glogit_item[sl] = got['glogit_user'], got['glogit_item']
+                out.scores[sl] = got['score']
+            out.attention_user.copy_(su['attn'][u_inv])
+            out.attention_item.copy_(si['attn'][i_inv])
+            out.live_user.copy_(su['live'][u_inv])
+            out.live_item.copy_(si['live'][i_inv])
+        return out
+
+    def pair_reviews(self, users, items):
+        """Why THIS item for THIS user, per REVIEW: for the pairs (users[p], items[p]) (lists, arrays or tensors on any
+        device, equally long; owners of the review pools) -> ``PairReviews`` of device tensors, n = len(users):
+
+            w_user, w_item                  float32 [n, R, F]  d score / d pooled[r, f] of the side's tower for slot r,
+                                            through the attention's softmax: what ``explain_words(..., weights=)`` takes
+            rev_user, rev_item              float32 [n, R]     gradient . input of slot r's latent: how much review r
+                                            carries THIS pair's score (a_r g . z_r + delta_r D_r . z_r)
+            glogit_user, glogit_item        float32 [n, R]     d score / d logit_r of the attention; rows sum to 0
+            attention_user, attention_item  float32 [n, R]     ``explain``'s ``attention`` of the pair's owners, bit for bit
+            live_user, live_item            int64 [n]          ``explain``'s ``live``
+            scores                          float32 [n]        the model's eval-mode prediction, from the raw head parameters
+
+        The DISTINCT users and items go once through the towers (both ``towers`` modes: the same bits) and the owner
+        pass r4r_narre_attn_jac; the pairs go through r4r_narre_pair_grad, ``pair_batch`` at a time (the results do not
+        depend on it) -- include/r4r.h, "NARRE pair gradients".  The score's scalars (user bias, global bias,
+        final.3.bias) are summed in float64 and rounded once.  Unequal lengths raise ValueError, an id outside its side's
+        pool KeyError, before anything is enqueued.  The engine's pending updates are flushed first, as ``refresh()``
+        does; the training state is left untouched."""
+        return self._pair_reviews(*self._pair_request(users, items))
+
+    def explain_pair_reviews(self, users, items, k=5, reviews=None, direction='up'):
+        """The reviews and the words behind one user-item score -> ``PairPhrases(user, item, scores)``: ``user`` is
+        ``explain_words(users, k, 'user', weights=+-w_user)`` and ``item`` is ``explain_words(items, k, 'item',
+        weights=+-w_item)`` of ``pair_reviews(users, items)``, bit for bit (they are made by those calls): [n, R, k] per
+        side.  ``direction``: 'up' lists what RAISES the prediction most (+w, +rev), 'down' what lowers it most.
+        ``reviews=k_r``: the lists are cut to the ``k_r`` LIVE slots with the largest +-rev (ties by ascending slot):
+        [n, k_r, k], with ``slots`` [n, k_r] holding those slots and ``weights`` [n, k_r] their ``rev`` values; a place
+        beyond the owner's live slots holds ``explain_words``' fill (slot -1, weight 0).  Refused before anything is
+        enqueued, in this order: a ``direction`` other than 'up' / 'down', ``k`` outside 1 .. F, ``reviews`` outside
+        1 .. R, unequal lengths (ValueError), an id outside its side's pool (KeyError)."""
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        R = int(self.hp['narre_num_reviews'])
+        F = int(self._phrase_side('item')[1].convs[0].bias.numel())
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= F:
+            raise ValueError('catalogue: explain_pair_reviews k = %r outside 1 .. %d' % (k, F))
+        if reviews is not None and (isinstance(reviews, bool) or not isinstance(reviews, (int, np.integer))
+                                    or not 1 <= reviews <= R):
+            raise ValueError('catalogue: explain_pair_reviews reviews = %r outside 1 .. %d' % (reviews, R))
+        u, i = self._pair_request(users, items)
+        pr = self._pair_reviews(u, i)
+        sign = 1.0 if direction == 'up' else -1.0
+        sides = []
+        for ids, side, w, rev, live in ((u, 'user', pr.w_user, pr.rev_user, pr.live_user),
+                                        (i, 'item', pr.w_item, pr.rev_item, pr.live_item)):
+            ph = self.explain_words(ids, k=int(k), side=side, weights=w if direction == 'up' else -w)
+            if reviews is not None:
+                ph = self._cut_to_reviews(ph, sign * rev, rev, live, int(reviews))
+            sides.append(ph)
+        return PairPhrases(sides[0], sides[1], pr.scores)
+
+    def _cut_to_reviews(self, ph, key, rev, live, k_r):
+        """``ph`` ([n, R, ...]) cut to the ``k_r`` live slots with the largest ``key`` [n, R], ties by ascending slot."""
+        n, R = key.shape
+        slot_of = torch.arange(R, device=self.dev)[None, :]
+        key = torch.where(slot_of < live[:, None], key, torch.full_like(key, float('-inf')))
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k_r]
+        none = torch.arange(k_r, device=self.dev)[None, :] >= live[:, None]
+        slots = order.masked_fill(none, -1)
+        take = order
+
+        def pick(t, fill):
+            tail = (1,) * (t.dim() - 2)
+            rows = t.gather(1, take.view(take.shape + tail).expand(take.shape + t.shape[2:]))
+            return rows.masked_fill(none.view(none.shape + tail), fill).contiguous()
+        return Phrases(pick(ph.positions, -1), pick(ph.scores, 0), pick(ph.filters, 0), pick(ph.tokens, -1),
+                       pick(ph.reviews, -1), pick(ph.offsets, -1), pick(ph.windows, 0), slots, pick(rev, 0))
+
     def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
         """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
         (NARRE.py:95-96), so there is one list of windows per (owner, slot) -> ``Phrases`` with [n, R, k] (tokens
@@ -1272,7 +1406,8 @@ class NarreCatalogue(Catalogue):
                               word lies inside it, else -1
             offsets    int64  that word's offset inside the review, max(p - 2, 0); -1 with reviews == -1
 
-        ``weights``: as ``Catalogue.explain_words``; a tensor [n, F] weighs every review of owner n alike."""
+        ``weights``: as ``Catalogue.explain_words``; a tensor [n, F] weighs every review of owner n alike, a tensor
+        [n, R, F] holds one row per review (``pair_reviews``' ``w_user`` / ``w_item``)."""
         R = int(self.hp['narre_num_reviews'])
         if reviews is not None and (isinstance(reviews, bool) or not isinstance(reviews, (int, np.integer))
                                     or not 1 <= reviews <= R):
