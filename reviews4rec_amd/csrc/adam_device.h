@@ -24,7 +24,10 @@ struct AdamScalars {
 // Two forms of the same update.
 //   adam_elem       -- IEEE-exact sqrtf() and `/` (hipcc's expansions: 27 of the update's 35 vector instructions).
 //                      The DEFAULT: the flat dense-parameter buffers (adam.hip, the fused reduce launches) are
-//                      latency- or HBM-bound and pay nothing for it, and their update is torch.optim.Adam's to the bit.
+//                      latency- or HBM-bound and pay nothing for it.  Within the per-rounding float64 bound of
+//                      tests/adam_ref.py (half an ulp per operation below, one ulp per float32 scalar); NOT torch's
+//                      bits: torch divides by sqrt(bc2) where this multiplies by a rounded 1 / sqrt(bc2), and rounds
+//                      mul_ and add_ apart where this forms m and v with one fma each.
 //   adam_elem_fast  -- the hardware's v_sqrt_f32 / v_rcp_f32 (1 ulp each; m * rcp(denom) for m / denom; a denormal
 //                      second moment reads as zero: sqrt(v) < 1e-19 against eps = 1e-8 either way).  Only for the
 //                      ID-table sweeps (mf_engine.hip, rows_device.h / step_device.h, idnet_engine.hip): temporally
