@@ -1732,6 +1732,67 @@ int r4r_narre_pair_grad(const float *p_u, const float *z_u, const float *attn_u,
                         float *w_user, float *w_item,                   /* [n_p, R_u, F] / [n_p, R_i, F], nullable */
                         void *stream);
 
+/* ------------------------------------------------------------------------
+ * NARRE what-if scores: a pair's eval-mode rating with chosen reviews of either owner REMOVED (csrc/narre_whatif.hip).
+ * A review enters NARRE's score only through its own latent z_r and its own attention logit (NARRE.attention,
+ * NARRE.py:53-64; the scorer of NARRE.py:24-36), so "what would the model predict without review r" needs no tower:
+ * the loader's own removal (`skip`, data.py:144-172 for the reviews, data.py:275-279 for the neighbour ids: slot r holds
+ * the r-th REMAINING review, the next review beyond R slides in, padding fills the tail) is a re-selection of slots, a new
+ * softmax and a new pooled vector.  An owner pass returns every slot's logit once; a variant pass scores
+ * n_p pairs x V variants.
+ *
+ * r4r_narre_logits -- the owner pass over S slots per owner: r4r_narre_explain's attention inputs, one wave per owner, one
+ *   launch.  logit[n, s] = w3 . relu(W0 [z[n, s] ; other_table[nb[n, s]]] + b0) + b3, the PRE-softmax value, by
+ *   r4r_narre_explain's instruction sequence: lane l chains column c ascending of W0[l, c] cat[c] from 0.0f, + b0[l],
+ *   relu; the sum over l of w3_l h_l (the product rounded) is the wave sum of the Pair gradients section (xor 1, xor 2,
+ *   rotate 4, rotate 8 within each 16 lanes, then (r_0 + r_16) + (r_32 + r_48)), then + b3.  A slot's logit depends on
+ *   that slot's inputs only: equal z rows and equal ids give equal bits, whatever N, S, the slot index and who shares the
+ *   call.  An nb id outside [0, other_rows) reads as a row of zeros.  Limits: 1 <= S <= 64, 1 <= L <= 64, N >= 0,
+ *   other_rows >= 0.  N == 0 returns R4R_OK and enqueues nothing.  The padding slot of a side is the call with N = 1,
+ *   S = 1 on z_pad (the tower on an all-padding review) and the pad id (total + 1 of the other side, data.py:275-276).
+ *
+ * r4r_narre_whatif -- the variant pass; one wave per (pair, 16 variants), one launch.  Per side: z [n, S, L] and
+ *   logit [n, S] (the owner pass's), own [n, L] (the owners' id-embedding rows, NARRE.py:115-116; NULL = no add),
+ *   z_pad [L], logit_pad, and R, the slots the model attends, 1 <= R <= S <= 64; the sides may differ in R and S.
+ *   drop_u, drop_i [n_p, V] int64 bit masks, bit s = slot s removed (NULL = nothing removed).
+ *   One (pair, variant, side):
+ *     list   the first R slots of 0 .. S - 1 whose bit is clear, in ascending slot order; with fewer than R left the tail
+ *            is copies of the pad slot (logit_pad, z_pad).  Bits at positions >= S are ignored.  With S = R + (drops)
+ *            this is the loader's `skip` rule; with S = R it is occlusion by padding.
+ *     a'     lane k holds the k-th selected logit: m = wave max, e_k = expf(logit_k - m), den = wave sum of e (the order
+ *            above, 0.0f in the lanes past R), a'_k = e_k / den
+ *     o'_l   chain over k ascending of fmaf(a'_k, z'_k[l], .) from 0.0f;   p'_l = o'_l + own[l] (no add with a NULL own)
+ *   The head (NARRE.py:38-46, 115-124; dropout is the identity in eval mode): x_l = p'_u[l] p'_i[l];
+ *     t_j = chain over l ascending of fmaf(W1[j, l], x_l, .) from 0.0f (v_mfma_f32_16x16x4_f32, bitwise that chain; the
+ *     variants are its columns);  z_j = fmaxf(t_j + b1_j, 0);  h_g = chain of fmaf(w_j, z_j, .) over the j with
+ *     ((j >> 2) & 3) == g, ascending;  head = (h_0 + h_1) + (h_2 + h_3);  out_score[p, v] = (head + q_bias[u]) + c_bias[i]
+ *     (q_bias [n_u] / c_bias [n_i] hold every scalar of the score; NULL counts as 0).
+ *   A variant's bits depend only on its own pair's inputs, the ordered selected list and the pad count: not on V, the
+ *   variant's column, n_p, the grid, the other variants or how the mask spells the same list (a bit on a slot that would
+ *   not have been selected changes nothing).
+ *   Limits: 1 <= L <= 64, V >= 1, n_u, n_i >= 0, 0 <= n_p, n_p V < 2^31.  Refused before the launch and the first
+ *   dereference, in the entry point's own name: a limit; with n_p > 0 a null z, logit, z_pad of either side, u_idx,
+ *   i_idx, W1, b1, w or out_score, and n_u or n_i == 0.  n_p == 0 returns R4R_OK and enqueues nothing.  An index outside
+ *   [0, n_u) / [0, n_i) is the caller's error.  Both calls: one launch; nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_narre_logits(const float *z,              /* [N, S, L] review latents                              */
+                     const int64_t *nb,           /* [N, S] neighbour ids, rows of other_table             */
+                     const float *other_table, int64_t other_rows,   /* [other_rows, L]                    */
+                     const float *W0, const float *b0, const float *w3, const float *b3,
+                     float *logit,                /* [N, S]  the pre-softmax logits                        */
+                     int64_t N, int S, int L, void *stream);
+int r4r_narre_whatif(const float *z_u, const float *logit_u, const float *own_u, const float *z_pad_u, float logit_pad_u,
+                     int64_t n_u, int S_u, int R_u,          /* [n_u, S_u, L], [n_u, S_u], [n_u, L] or NULL, [L]      */
+                     const float *z_i, const float *logit_i, const float *own_i, const float *z_pad_i, float logit_pad_i,
+                     int64_t n_i, int S_i, int R_i,          /* the item side likewise                                */
+                     const int64_t *u_idx, const int64_t *i_idx,              /* [n_p] rows of the sides              */
+                     const int64_t *drop_u, const int64_t *drop_i,            /* [n_p, V] bit masks; NULL = 0         */
+                     int64_t n_p, int V,
+                     const float *q_bias, const float *c_bias,                /* [n_u], [n_i]; NULL = 0               */
+                     const float *W1, const float *b1, const float *w, int L, /* [L, L], [L], [L]                     */
+                     float *out_score,                                        /* [n_p, V]                             */
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

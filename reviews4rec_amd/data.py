@@ -153,6 +153,26 @@ def _np_neighbours(nb, rb, re, skip, pad):
     return np.where(ok, padded[np.where(ok, at, len(nb))], pad).astype(np.int64)
 
 
+def _np_review_slots(tok, rev_off, nb, rb, re, lo, hi, W, pad):
+    """The reviews lo .. hi - 1 of every owner in pool order, nothing removed -> (docs [N, hi - lo, W], neigh
+    [N, hi - lo]): ``_np_reviews`` / ``_np_neighbours`` with skip = -1 over ANY range of slots -- the neighbour lists'
+    fixed width of 10 does not reach the reviews that slide in when earlier ones are removed (NarreCatalogue.what_if).
+    A slot beyond the owner's last review holds zeros and ``pad``."""
+    r = np.arange(lo, hi, dtype=np.int64)[None, :]
+    rev = rb[:, None] + r
+    okr = rev < re[:, None]
+    padded_nb = np.concatenate([nb, np.zeros(1, nb.dtype)])
+    neigh = np.where(okr, padded_nb[np.where(okr, rev, len(nb))], pad).astype(np.int64)
+    if len(rev_off) < 2:
+        return np.zeros((len(rb), hi - lo, W), dtype=np.int64), neigh
+    rev = np.where(okr, rev, 0)
+    rs, rl = rev_off[rev], rev_off[rev + 1] - rev_off[rev]
+    w = np.arange(W, dtype=np.int64)[None, None, :]
+    ok = okr[:, :, None] & (w < rl[:, :, None])
+    padded = np.concatenate([tok, np.zeros(1, tok.dtype)])
+    return np.where(ok, padded[np.where(ok, rs[:, :, None] + w, len(tok))], 0).astype(np.int64), neigh
+
+
 class SpanDescriptor:
     """Host-side view of one loader for r4r_*_span: `words` (ctypes uint64 [R4R_LOADER_WORDS], layout in
     include/r4r.h), `built` (the ring's state, a c_int64 the C side advances), `full_batches`, `batch_size`, and the

@@ -735,6 +735,90 @@ def narre_pair_grad(user, item, u_idx, i_idx, W1, b1, w, q_bias=None, c_bias=Non
     return out
 
 
+NARRE_WHATIF_MAX = 64               # r4r_narre_logits / r4r_narre_whatif: S, R and L up to 64
+
+
+def narre_logits(z, nb, other_table, W0, b0, w3, b3):
+    """r4r_narre_logits (include/r4r.h, "NARRE what-if scores"), the owner pass: ``narre_explain``'s attention inputs
+    over S slots, ``z`` [N, S, L] and ``nb`` [N, S] (int64 rows of ``other_table`` [rows, L]; an id outside reads as
+    zeros) -> the PRE-softmax logits, float32 [N, S].  No autograd."""
+    z, other_table = _f32(z, 'z'), _f32(other_table, 'other_table')
+    W0, b0, w3, b3 = _f32(W0, 'W0'), _f32(b0, 'b0'), _f32(w3, 'w3'), _f32(b3, 'b3')
+    nb = _i64(nb, 'nb')
+    if z.dim() != 3 or tuple(nb.shape) != tuple(z.shape[:2]):
+        raise RuntimeError('reviews4rec_amd.ops: narre_logits takes z [N, S, L] and nb [N, S], got %s and %s'
+                           % (tuple(z.shape), tuple(nb.shape)))
+    N, S, L = (int(d) for d in z.shape)
+    if other_table.dim() != 2 or other_table.shape[1] != L or tuple(W0.shape) != (L, 2 * L) or b0.numel() != L \
+            or w3.numel() != L or b3.numel() != 1:
+        raise RuntimeError('reviews4rec_amd.ops: narre_logits: other_table [*, L], W0 [L, 2L], b0 [L], w3 [L], b3 [1] '
+                           'with L = %d expected' % L)
+    logit = torch.empty((N, S), dtype=torch.float32, device=z.device)
+    call('r4r_narre_logits', ptr(z), ptr(nb), ptr(other_table), int(other_table.shape[0]), ptr(W0), ptr(b0), ptr(w3),
+         ptr(b3), ptr(logit), N, S, L)
+    return logit
+
+
+def narre_whatif(user, item, u_idx, i_idx, drop_u, drop_i, W1, b1, w, q_bias=None, c_bias=None):
+    """r4r_narre_whatif (include/r4r.h, "NARRE what-if scores"), the variant pass.  ``user`` / ``item``: one dict per
+    side with ``z`` [n, S, L], ``logit`` [n, S] (``narre_logits``), ``z_pad`` [L], ``logit_pad`` (a float), ``R`` (the
+    slots the model attends, 1 .. S) and optionally ``own`` [n, L]; the sides may differ in R and S.  ``drop_u`` /
+    ``drop_i``: int64 [n_p, V] bit masks, bit s = slot s removed; None = nothing removed (one of them fixes V; both None:
+    V = 1).  ``W1`` [L, L], ``b1`` [L], ``w`` [L]: final.1 and final.3.weight; ``q_bias`` [n_u] / ``c_bias`` [n_i]: the
+    score's scalars, None = 0.  No autograd -> scores, float32 [n_p, V]."""
+    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
+    if u_idx.numel() != i_idx.numel():
+        raise RuntimeError('reviews4rec_amd.ops: narre_whatif takes equally long u_idx / i_idx, got %d and %d'
+                           % (u_idx.numel(), i_idx.numel()))
+    n_p = int(u_idx.numel())
+    W1, b1, w = _f32(W1, 'W1'), _f32(b1, 'b1').reshape(-1), _f32(w, 'w').reshape(-1)
+    L = int(b1.numel())
+    if tuple(W1.shape) != (L, L) or w.numel() != L:
+        raise RuntimeError('reviews4rec_amd.ops: narre_whatif: W1 [L, L], b1 [L], w [L] expected, got %s, %d and %d'
+                           % (tuple(W1.shape), L, w.numel()))
+    V, drops = None, []
+    for name, d in (('drop_u', drop_u), ('drop_i', drop_i)):
+        if d is not None:
+            d = _i64(d, name)
+            if d.dim() != 2 or d.shape[0] != n_p or d.shape[1] < 1 or (V is not None and d.shape[1] != V):
+                raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s must be [n_p, V] = [%d, %s], got %s'
+                                   % (name, n_p, 'V' if V is None else V, tuple(d.shape)))
+            V = int(d.shape[1])
+        drops.append(d)
+    V = 1 if V is None else V
+    sides = []
+    for name, side in (('user', user), ('item', item)):
+        s = {k: None if side.get(k) is None else _f32(side[k], '%s %s' % (name, k)) for k in ('z', 'logit', 'own', 'z_pad')}
+        if s['z'] is None or s['z'].dim() != 3 or s['z'].shape[2] != L or s['logit'] is None or s['z_pad'] is None:
+            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side needs z [n, S, L], logit [n, S] and z_pad [L] '
+                               'with L = %d' % (name, L))
+        n, S = int(s['z'].shape[0]), int(s['z'].shape[1])
+        if tuple(s['logit'].shape) != (n, S) or s['z_pad'].numel() != L \
+                or (s['own'] is not None and tuple(s['own'].shape) != (n, L)):
+            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side: z %s, logit %s, z_pad %s, own %s do not match'
+                               % (name, tuple(s['z'].shape), tuple(s['logit'].shape), tuple(s['z_pad'].shape),
+                                  None if s['own'] is None else tuple(s['own'].shape)))
+        R = side.get('R')
+        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= S:
+            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side: R = %r outside 1 .. S = %d' % (name, R, S))
+        sides.append((s, float(side['logit_pad']), n, S, R))
+    (su, lpu, n_u, S_u, R_u), (si, lpi, n_i, S_i, R_i) = sides
+    biases = []
+    for name, t, n in (('q_bias', q_bias, n_u), ('c_bias', c_bias, n_i)):
+        t = None if t is None else _f32(t, name).reshape(-1)
+        if t is not None and t.numel() != n:
+            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s must be [%d], got %s' % (name, n, tuple(t.shape)))
+        biases.append(t)
+    if n_p and (n_u == 0 or n_i == 0):
+        raise RuntimeError('reviews4rec_amd.ops: narre_whatif: %d pairs over %d / %d owners' % (n_p, n_u, n_i))
+    out = torch.empty((n_p, V), dtype=torch.float32, device=su['z'].device)
+    side_args = lambda s, lp, n, S, R: (ptr(s['z']), ptr(s['logit']), ptr(s['own']), ptr(s['z_pad']), lp, n, S, R)
+    call('r4r_narre_whatif', *side_args(su, lpu, n_u, S_u, R_u), *side_args(si, lpi, n_i, S_i, R_i), ptr(u_idx),
+         ptr(i_idx), ptr(drops[0]), ptr(drops[1]), n_p, V, ptr(biases[0]), ptr(biases[1]), ptr(W1), ptr(b1), ptr(w), L,
+         ptr(out))
+    return out
+
+
 class TransformLoss(Function):
     """mean_n ||a_n - b_n||^2 (TransNet's source/target representation loss)."""
 

@@ -413,11 +413,13 @@ class Catalogue:
                         int(self.hp['input_length']))
         return torch.from_numpy(docs).to(self.dev)
 
-    def _span_latents(self, tower, pool, ids, narre_pad=None):
+    def _span_latents(self, tower, pool, ids, narre_pad=None, shift=0):
         """The device path of ``_tower(tower, _documents(pool, chunk))`` over every ``tower_batch`` chunk of ``ids`` (a
         host int64 array): ONE r4r_tower_span_fwd call -> latent [n, L].  ``narre_pad`` (NARRE: the pad id of the
         neighbour lists): the reviews one by one -> (latent [n R, L], neigh [n, 10]).  The id check stays on the host
-        and raises before anything is enqueued; the pass has its own workspace and touches no engine buffer."""
+        and raises before anything is enqueued; the pass has its own workspace and touches no engine buffer.
+        ``shift`` > 0 (``what_if``'s slide-in slots): every owner's reviews from its ``shift``-th on, through a table of
+        review ranges in which owner o is row 2 o -- [min(first[o] + shift, first[o + 1]), first[o + 1])."""
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         if len(ids) and (ids.min() < 0 or ids.max() >= pool.owners):
             raise KeyError('id outside the review pools: {}'.format(int(ids.max())))
@@ -444,9 +446,14 @@ class Catalogue:
         F = int(conv_b.numel())
         tok, rev_off, first, nb = pool.device(self.dev)
         dev_ids = torch.from_numpy(ids).to(self.dev)
+        owners = int(pool.owners)
+        if shift:
+            ends = first[1:]
+            first = torch.stack([torch.minimum(first[:-1] + int(shift), ends), ends], 1).reshape(-1)
+            first, dev_ids, owners = torch.cat([first, first[-1:]]).contiguous(), dev_ids * 2, 2 * owners
         group = max(1, self.tower_batch)
         ws = ops._workspace(_lib.lib().r4r_tower_span_ws_bytes(min(group, n), T, R, W, E, F, L, V), self.dev)
-        _lib.call('r4r_tower_span_fwd', ptr(tok), ptr(rev_off), ptr(first), ptr(nb), int(pool.owners), ptr(dev_ids), n, group,
+        _lib.call('r4r_tower_span_fwd', ptr(tok), ptr(rev_off), ptr(first), ptr(nb), owners, ptr(dev_ids), n, group,
                   T, R, W, int(narre_pad or 0), ptr(table), V, ptr(conv_w), ptr(conv_b), ptr(fc_w), ptr(fc_b), E, F, L,
                   ptr(latent), ptr(neigh), ptr(ws), ws.numel(), None)
         return (latent, neigh) if narre else latent
@@ -897,6 +904,10 @@ class Catalogue:
 PairPhrases = namedtuple('PairPhrases', 'user item scores')      # Catalogue.explain_pair: two ``Phrases`` and [n] scores
 PairReviews = namedtuple('PairReviews', 'w_user w_item rev_user rev_item glogit_user glogit_item attention_user '
                          'attention_item live_user live_item scores')          # NarreCatalogue.pair_reviews
+WhatIf = namedtuple('WhatIf', 'scores base')                                    # NarreCatalogue.what_if
+LeaveOneOut = namedtuple('LeaveOneOut', 'base without_user without_item delta_user delta_item live_user live_item')
+DeletionCurve = namedtuple('DeletionCurve', 'scores aopc order live')           # NarreCatalogue.deletion_curve
+WHATIF_MAX_SLOTS = 64               # r4r_narre_whatif: S <= 64, one bit of an int64 mask per slot
 PHRASE_FILTERS = 100                # every TextCNN tower's filter count (common_pytorch_models.py:11)
 _PHRASE_TYPES = ('deepconn', 'deepconn++', 'transnet', 'transnet++', 'NARRE')
 Phrases = namedtuple('Phrases', 'positions scores filters tokens reviews offsets windows slots weights',
@@ -1139,7 +1150,10 @@ class NarreCatalogue(Catalogue):
 
     The attention runs through r4r_narre_attn_fwd where that takes the shape (R and L up to 32) and through
     r4r_narre_explain (csrc/narre_explain.hip: R and L up to 64) beyond.  ``explain`` returns what the attention says:
-    each owner's most useful reviews (``main``'s ``explain_k`` hook writes them for every eligible item)."""
+    each owner's most useful reviews (``main``'s ``explain_k`` hook writes them for every eligible item).
+    ``pair_reviews`` says how much each review carries ONE pair's score, to first order; ``what_if`` /
+    ``leave_one_out`` / ``deletion_curve`` say what the score would be with reviews removed, exactly and in the
+    loader's own sense of removed (csrc/narre_whatif.hip)."""
 
     _form = 'hmlp'
     _limits = staticmethod(narre_catalogue_limits)
@@ -1394,6 +1408,254 @@ class NarreCatalogue(Catalogue):
             return rows.masked_fill(none.view(none.shape + tail), fill).contiguous()
         return Phrases(pick(ph.positions, -1), pick(ph.scores, 0), pick(ph.filters, 0), pick(ph.tokens, -1),
                        pick(ph.reviews, -1), pick(ph.offsets, -1), pick(ph.windows, 0), slots, pick(rev, 0))
+
+    # ------------------------------------------------------------------ what-if scores: a pair's rating with reviews removed
+    def _whatif_drops(self, drop, ids, side, what):
+        """One side's ``drop`` argument of ``what_if`` -> (int64 host masks [n, V] or None, the most drops of any
+        variant); everything is checked here, before anything is enqueued."""
+        n = int(ids.numel())
+        if drop is None:
+            return None, 0
+        if torch.is_tensor(drop) or isinstance(drop, np.ndarray):
+            m = torch.as_tensor(drop)
+            if m.dtype != torch.int64 or m.dim() != 2 or m.shape[0] != n or m.shape[1] < 1:
+                raise ValueError('catalogue: %s as masks must be int64 [%d, V] with V >= 1, got %s %s'
+                                 % (what, n, m.dtype, tuple(m.shape)))
+            m = m.detach().cpu().contiguous()
+            bits = np.unpackbits(m.numpy().view(np.uint8).reshape(n, -1, 8), axis=-1).sum(-1) if n else np.zeros((0, 1))
+            return m, int(bits.max()) if bits.size else 0
+        if not isinstance(drop, (list, tuple)) or len(drop) != n:
+            raise ValueError('catalogue: %s must be None, int64 masks [n, V] or one list of review indices per pair (%d pairs)'
+                             % (what, n))
+        pool = self._narre_side(side)[1]
+        count = pool.first[ids.numpy() + 1] - pool.first[ids.numpy()]
+        is_index = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        rows, most = [], 0
+        for p, entry in enumerate(drop):
+            if not isinstance(entry, (list, tuple, np.ndarray)):
+                raise ValueError('catalogue: %s[%d] must be a list of review indices (or a list of such lists)' % (what, p))
+            entry = list(entry)
+            variants = [entry] if all(is_index(v) for v in entry) else [list(v) if isinstance(v, (list, tuple, np.ndarray))
+                                                                        else [v] for v in entry]
+            row = []
+            for variant in variants:
+                mask = 0
+                for v in variant:
+                    if not is_index(v) or not 0 <= int(v) < int(count[p]) or int(v) >= WHATIF_MAX_SLOTS:
+                        raise ValueError('catalogue: %s[%d] names review %r outside the owner\'s list of %d (the first %d '
+                                         'can be removed)' % (what, p, v, int(count[p]), WHATIF_MAX_SLOTS))
+                    mask |= 1 << int(v)
+                most = max(most, bin(mask).count('1'))
+                row.append(mask - (1 << 64) if mask >= (1 << 63) else mask)
+            rows.append(row)
+        if n and any(len(row) != len(rows[0]) for row in rows):
+            raise ValueError('catalogue: %s holds %s variants per pair; every pair needs as many'
+                             % (what, sorted({len(row) for row in rows})))
+        V = len(rows[0]) if n else 1
+        if V < 1:
+            raise ValueError('catalogue: %s holds no variant' % what)
+        return torch.tensor(rows, dtype=torch.int64).reshape(n, V), most
+
+    def _whatif_side(self, side, ids, S):
+        """``ops.narre_whatif``'s side for the owners ``ids`` (a host int64 array) over S >= R slots: the latents and
+        neighbour ids of the first R reviews as ``_attended`` builds them, those of the reviews R .. S - 1 R at a time
+        the same way -- ``data._np_review_slots`` and the tower per chunk ('host'), one shifted r4r_tower_span_fwd pass
+        ('device'): the same bits -- the logits of all S slots from
+        r4r_narre_logits, and the padding slot: the tower on an all-padding review with the pad id's logit."""
+        from .data import _np_neighbours, _np_review_slots, _np_reviews
+        m, hp = self.model, self.hp
+        user, pool, conv, pad = self._narre_side(side)
+        R, Wd = int(hp['narre_num_reviews']), int(hp['narre_num_words'])
+        scorer = m.attention_scorer_user if user else m.attention_scorer_item
+        own, other = (m.user_embedding, m.item_embedding) if user else (m.item_embedding, m.user_embedding)
+        weights = (scorer[0].weight.detach(), scorer[0].bias.detach(), scorer[3].weight.detach(), scorer[3].bias.detach())
+        ids = np.asarray(ids, dtype=np.int64)
+        n = len(ids)
+        docs_of = lambda d: torch.from_numpy(np.ascontiguousarray(d).reshape(-1, Wd)).to(self.dev)
+        with torch.no_grad():
+            if self.towers == 'device':
+                z, nb = self._span_latents(conv, pool, ids, narre_pad=pad)
+                z = z.view(n, R, -1)
+            else:
+                zs, nbs = [], []
+                for _, chunk in self._batches(ids):
+                    rb, re = pool.first[chunk], pool.first[chunk + 1]
+                    none = np.full(len(chunk), -1, np.int64)
+                    zs.append(self._tower(conv, docs_of(_np_reviews(pool.tok, pool.rev_off, rb, re, none, R, Wd))).view(len(chunk), R, -1))
+                    nbs.append(torch.from_numpy(_np_neighbours(pool.nb, rb, re, none, pad)).to(self.dev))
+                z, nb = torch.cat(zs), torch.cat(nbs)
+            for lo in range(R, S, R):                          # the slots that can slide in, R at a time: the same towers
+                if self.towers == 'device':
+                    zb, nbb = self._span_latents(conv, pool, ids, narre_pad=pad, shift=lo)
+                    zb = zb.view(n, R, -1)
+                else:
+                    zs, nbs = [], []
+                    for _, chunk in self._batches(ids):
+                        docs, neigh = _np_review_slots(pool.tok, pool.rev_off, pool.nb, pool.first[chunk],
+                                                       pool.first[chunk + 1], lo, lo + R, Wd, pad)
+                        zs.append(self._tower(conv, docs_of(docs)).view(len(chunk), R, -1))
+                        nbs.append(torch.from_numpy(neigh).to(self.dev))
+                    zb, nbb = torch.cat(zs), torch.cat(nbs)
+                z, nb = torch.cat([z, zb], 1), torch.cat([nb, nbb], 1)
+            z, nb = z[:, :S].contiguous(), nb[:, :S].contiguous()
+            z_pad = self._tower(conv, torch.zeros((1, Wd), dtype=torch.int64, device=self.dev)).reshape(-1)
+            table = other.weight.detach()
+            logit = ops.narre_logits(z, nb, table, *weights)
+            pad_id = torch.full((1, 1), int(pad), dtype=torch.int64, device=self.dev)
+            logit_pad = float(ops.narre_logits(z_pad.view(1, 1, -1), pad_id, table, *weights).reshape(()))
+            live = np.minimum(pool.first[ids + 1] - pool.first[ids], R).astype(np.int64)
+            return dict(z=z, logit=logit, own=own.weight.detach()[torch.from_numpy(ids).to(self.dev)].contiguous(),
+                        z_pad=z_pad, logit_pad=logit_pad, R=R, live=torch.from_numpy(live).to(self.dev))
+
+    def _what_if(self, u, i, mask_u, mask_i, most_u, most_i, slide):
+        """``what_if`` of checked host tensors -> (scores [n, V], base [n], live_user [n], live_item [n]); the pairs'
+        own prediction rides along as one more variant (nothing removed)."""
+        self._flush()
+        m = self.model
+        R = int(self.hp['narre_num_reviews'])
+        n = int(u.numel())
+        V = next((int(t.shape[1]) for t in (mask_u, mask_i) if t is not None), 1)
+        if n == 0:
+            e = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=self.dev)
+            return e(0, V), e(0), e(0, dt=torch.int64), e(0, dt=torch.int64)
+        drops = []
+        for t in (mask_u, mask_i):
+            d = torch.zeros((n, V + 1), dtype=torch.int64)
+            if t is not None:
+                d[:, 1:] = t
+            drops.append(d.to(self.dev))
+        uu, u_inv = torch.unique(u, return_inverse=True)
+        ui, i_inv = torch.unique(i, return_inverse=True)
+        slots = lambda most: min(WHATIF_MAX_SLOTS, R + most) if slide else R
+        with torch.no_grad():
+            su = self._whatif_side('user', uu.numpy(), slots(most_u))
+            si = self._whatif_side('item', ui.numpy(), slots(most_i))
+            f64 = lambda t: t.detach().to(torch.float64)
+            qb = (f64(m.user_bias).reshape(-1)[uu.to(self.dev)] + f64(m.global_bias).reshape(())
+                  + f64(m.final[3].bias).reshape(())).to(torch.float32).contiguous()
+            cb = m.item_bias.detach().reshape(-1)[ui.to(self.dev)].to(torch.float32).contiguous()
+            W1, b1, w = m.final[1].weight.detach(), m.final[1].bias.detach(), m.final[3].weight.detach().reshape(-1)
+            u_inv, i_inv = u_inv.to(self.dev), i_inv.to(self.dev)
+            out = torch.empty((n, V + 1), dtype=torch.float32, device=self.dev)
+            step = max(1, int(self.pair_batch))
+            for s0 in range(0, n, step):
+                sl = slice(s0, s0 + step)
+                out[sl] = ops.narre_whatif(su, si, u_inv[sl].contiguous(), i_inv[sl].contiguous(), drops[0][sl].contiguous(),
+                                           drops[1][sl].contiguous(), W1, b1, w, q_bias=qb, c_bias=cb)
+            return out[:, 1:].contiguous(), out[:, 0].contiguous(), su['live'][u_inv], si['live'][i_inv]
+
+    def what_if(self, users, items, drop_user=None, drop_item=None, slide=True):
+        """What would the model predict for (users[p], items[p]) if chosen reviews were not there?  -> ``WhatIf(scores
+        [n, V], base [n])`` of device tensors: ``scores[p, v]`` is the eval-mode prediction with variant v's reviews
+        removed from the user's and / or the item's list, ``base[p]`` the prediction with nothing removed.
+
+        ``drop_user`` / ``drop_item``: None (nothing removed on that side); or, per pair, a list of review indices in
+        the owner's pool order -- the loader's ``skip`` (data.py:144-172) -- as one variant, or a list of such lists as
+        V variants (every pair as many); or an int64 mask tensor [n, V], bit s = the owner's review s removed.  Both
+        sides given: the same V.  ``slide=True`` is the loader's removal: slot r holds the r-th REMAINING review, the
+        owner's reviews beyond R slide in (each side reaches S = min(64, R + the most drops of any variant) reviews of
+        its owners), padding fills the tail -- exactly what a training rating sees of its own pair.  ``slide=False`` is
+        occlusion: S = R, the removed reviews' places go to padding at the tail.
+
+        No tower runs per variant: a review enters NARRE's score through its latent and its attention logit alone
+        (NARRE.py:53-64).  The DISTINCT users and items go once through the towers (both ``towers`` modes: the same
+        bits) and the owner pass r4r_narre_logits; the pairs go through r4r_narre_whatif, ``pair_batch`` at a time (the
+        results do not depend on it) -- include/r4r.h, "NARRE what-if scores".  The score's scalars are summed in
+        float64 and rounded once, as ``pair_reviews`` does.  Before anything is enqueued: unequal lengths, a malformed
+        drop, unequal V and a review index outside the owner's list (or beyond the first 64) raise ValueError, an id
+        outside its side's pool KeyError.  The engine's pending updates are flushed first; the training state is left
+        untouched."""
+        u, i = self._pair_request(users, items)
+        mask_u, most_u = self._whatif_drops(drop_user, u, 'user', 'drop_user')
+        mask_i, most_i = self._whatif_drops(drop_item, i, 'item', 'drop_item')
+        if mask_u is not None and mask_i is not None and mask_u.shape[1] != mask_i.shape[1]:
+            raise ValueError('catalogue: drop_user holds %d variants per pair, drop_item %d'
+                             % (mask_u.shape[1], mask_i.shape[1]))
+        scores, base, _, _ = self._what_if(u, i, mask_u, mask_i, most_u, most_i, bool(slide))
+        return WhatIf(scores, base)
+
+    def leave_one_out(self, users, items, slide=True):
+        """Each attended review of each pair removed in turn -> ``LeaveOneOut`` of device tensors, n = len(users):
+
+            base                          float32 [n]     the prediction with nothing removed
+            without_user, without_item    float32 [n, R]  the prediction without the owner's review in slot r
+            delta_user, delta_item        float32 [n, R]  base - without: what review r adds to THIS pair's score
+            live_user, live_item          int64 [n]       ``explain``'s ``live``: min(number of reviews, R)
+
+        A slot at or beyond ``live`` holds no review: ``without`` is ``base`` there and ``delta`` exactly 0.  ``slide``:
+        as ``what_if`` (True: the owner's review R + 1 moves up, the loader's ``skip``).  One ``what_if`` pass of 2 R
+        variants per pair; its checks and refusals."""
+        u, i = self._pair_request(users, items)
+        R, n = int(self.hp['narre_num_reviews']), int(u.numel())
+        one = (torch.ones(R, dtype=torch.int64) << torch.arange(R, dtype=torch.int64))[None, :].expand(n, R)
+        none = torch.zeros((n, R), dtype=torch.int64)
+        scores, base, live_u, live_i = self._what_if(u, i, torch.cat([one, none], 1), torch.cat([none, one], 1), 1, 1,
+                                                     bool(slide))
+        slot = torch.arange(R, device=self.dev)[None, :]
+        held = base[:, None].expand(n, R)
+        without_u = torch.where(slot < live_u[:, None], scores[:, :R], held).contiguous()
+        without_i = torch.where(slot < live_i[:, None], scores[:, R:], held).contiguous()
+        return LeaveOneOut(base, without_u, without_i, held - without_u, held - without_i, live_u, live_i)
+
+    def deletion_curve(self, users, items, by='rev', side='user', direction='up', slide=True):
+        """The live reviews of one side removed CUMULATIVELY, the largest key first -> ``DeletionCurve`` of device tensors:
+
+            scores  float32 [n, R + 1]  column 0 the prediction with nothing removed (``what_if``'s ``base``), column k
+                                        the prediction with the first k reviews of ``order`` removed; beyond the
+                                        owner's live reviews the last live column repeats
+            aopc    float32 [n]         the mean over k = 1 .. live of scores[:, 0] - scores[:, k] (0 with no review):
+                                        the area over the perturbation curve -- large when the key names the reviews
+                                        that carry the score
+            order   int64 [n, R]        the slots in removal order; -1 beyond ``live``
+            live    int64 [n]           min(number of reviews, R)
+
+        ``by``: 'rev' -- ``pair_reviews``' gradient x input of the side; 'attention' -- ``explain``'s weights; or a
+        float tensor [n, R] of your own.  ``direction`` 'up' removes the largest key first, 'down' the smallest; ties go
+        to the ascending slot.  ``side``: 'user' or 'item'; the other side keeps every review.  ``slide``: as
+        ``what_if``.  Refused before anything is enqueued: a bad ``by`` / ``side`` / ``direction`` (ValueError), unequal
+        lengths (ValueError), an id outside its side's pool (KeyError)."""
+        if side not in ('item', 'user'):
+            raise ValueError("catalogue: side must be 'item' or 'user', got %r" % (side,))
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        R = int(self.hp['narre_num_reviews'])
+        named = isinstance(by, str)
+        if named and by not in ('rev', 'attention'):
+            raise ValueError("catalogue: by must be 'rev', 'attention' or a tensor [n, %d], got %r" % (R, by))
+        u, i = self._pair_request(users, items)
+        n = int(u.numel())
+        if not named:
+            if not (torch.is_tensor(by) or isinstance(by, np.ndarray)) or tuple(by.shape) != (n, R) \
+                    or not torch.as_tensor(by).dtype.is_floating_point:
+                raise ValueError("catalogue: by must be 'rev', 'attention' or a float tensor [%d, %d], got %r"
+                                 % (n, R, getattr(by, 'shape', by)))
+            key = torch.as_tensor(by).detach().to(self.dev, torch.float32)
+        ids = u if side == 'user' else i
+        pool = self._narre_side(side)[1]
+        count = pool.first[ids.numpy() + 1] - pool.first[ids.numpy()]
+        live = torch.from_numpy(np.minimum(count, R).astype(np.int64)).to(self.dev)
+        if named and n and by == 'rev':
+            key = getattr(self._pair_reviews(u, i), 'rev_' + side)
+        elif named and n:                                      # the DISTINCT owners' attention, handed to their pairs
+            distinct, inverse = torch.unique(ids, return_inverse=True)
+            key = self.explain(distinct, k=1, side=side).attention[inverse.to(self.dev)]
+        elif named:
+            key = torch.empty((0, R), dtype=torch.float32, device=self.dev)
+        if direction == 'down':
+            key = -key
+        slot = torch.arange(R, device=self.dev)[None, :]
+        valid = slot < live[:, None]
+        key = torch.where(valid, key, torch.full_like(key, float('-inf')))
+        order = torch.sort(key, dim=1, descending=True, stable=True).indices
+        bit = torch.where(valid, torch.ones_like(order) << order, torch.zeros_like(order))
+        masks = torch.cumsum(bit, dim=1).cpu()                  # distinct bits: the sum is the union
+        mu, mi = (masks, None) if side == 'user' else (None, masks)
+        most = (R, 0) if side == 'user' else (0, R)
+        scores, base, _, _ = self._what_if(u, i, mu, mi, most[0], most[1], bool(slide))
+        gain = (base[:, None].double() - scores.double()) * valid
+        aopc = (gain.sum(1) / live.clamp(min=1)).to(torch.float32)
+        return DeletionCurve(torch.cat([base[:, None], scores], 1).contiguous(), aopc,
+                             torch.where(valid, order, torch.full_like(order, -1)), live)
 
     def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
         """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
