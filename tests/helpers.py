@@ -201,8 +201,12 @@ def _adam_tap(seen, perturb=None):
         O.adam_step = real
 
 
+SE_RTOL, SE_ATOL = 1e-4, 1e-5       # per-rating SE: the golden SE comparisons' tolerances (test_gpu_engine.py)
+
+
 class StepState:
-    """What one reference step left: gradients, Adam moments and weights by parameter name."""
+    """What one reference step left: the sum of the squared errors and each rating's (in the reference's dtype),
+    gradients, Adam moments and weights by parameter name."""
 
     def __init__(self, step, sse, se, grads, m, v, params, zero_so_far):
         self.step, self.sse, self.se, self.grads, self.m, self.v, self.params = step, sse, se, grads, m, v, params
@@ -240,8 +244,10 @@ class _StepReference:
                 se, _, _ = oracle.transnet_train_step(self.params, data, y, self.hp, self.states, masks=masks)
                 sse = float(se.sum())
             else:
+                with torch.no_grad():                        # (train_step returns the sum alone)
+                    out = oracle.model_forward(self.params, data, self.hp, train=True, masks=masks)
+                    se = oracle.mse_loss(out, y, return_mean=False).reshape(-1).clone()
                 sse, _ = oracle.train_step(self.params, data, y, self.hp, self.states, masks=masks)
-                se = None
         self.steps += 1
         states = list(self.states.values()) if self.transnet else [self.states]
         m, v = {}, {}
@@ -392,6 +398,27 @@ def assert_step_state(engine, model, ref, data=None, weights=None, atol=None, wh
         bad += weights_failures(sd, ref.params, weights, skip)
     bad = [b for b in bad if b]
     assert not bad, '%s after step %d:\n  ' % (what or type(engine).__name__, ref.step) + '\n  '.join(bad)
+
+
+def assert_per_rating_se(se, ref, what=''):
+    """Each rating's squared error of a training step against the StepState `ref`, at SE_RTOL / SE_ATOL."""
+    torch.testing.assert_close(se.detach().cpu().double().reshape(-1), ref.se.double().reshape(-1), rtol=SE_RTOL,
+                               atol=SE_ATOL, msg=lambda m: '%s per-rating SE of step %d: %s' % (what, ref.step, m))
+
+
+def multipliers(engine, data):
+    """The multipliers the last training step of a native engine drew, flattened: the [n, ND] block is one contiguous
+    counter range.  Each engine class has its own call."""
+    from reviews4rec_amd import engine as E
+    n = data[5].numel()
+    if isinstance(engine, E.DeepCoNNEngine):
+        m = engine.dropout_multipliers(n, data[3].reshape(n, -1).shape[1])
+    elif isinstance(engine, (E.MFEngine, E.IdNetEngine)):
+        m = engine.dropout_multipliers(n)
+    else:
+        m = engine.dropout_multipliers(data)
+    torch.cuda.synchronize()
+    return m.reshape(-1)
 
 
 class StepStateProbe:

@@ -1,20 +1,29 @@
 """The cases of the step-state tests: per native engine the smallest shapes that reach each path of the duplicate-row
 summation (hits spread over lanes, chunk boundaries, pairs of entry waves, the 2,048-rating scan, the 4,096 / 16,384
 entry caps).  tests/test_step_state_checker.py runs the float32 oracle through the checker on these inputs (CPU),
-tests/test_gpu_step_state.py the engines.  Two steps per case, a different batch each; dropout 0 unless stated."""
+tests/test_gpu_step_state.py the engines.  Two steps per case, a different batch each; dropout 0 unless stated.
+
+Every text case has twins with dropout on (`-p0.5` / `-p0.3`): the named case's shapes, seeds and batches, so each head
+instantiation the dropout-0 cases reach is reached with masks too.  Their masks are the ones the device will draw
+(stream_multipliers), so the CPU checker sees the GPU test's inputs."""
+import numpy as np
 import torch
 
 import oracle
+import philox_ref
 from helpers import WEIGHTS_CLOSE, synthetic_review_batch, weights_outliers
 
 LR, WD = 0.002, 1e-6
+ENGINE_SEED = (0x5EED5EED * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF    # the engines' default seed, rank 0; position 0
 
 
 class Case:
-    def __init__(self, id, engine, hp, make_batches, vocab=None, seed=0, weights=None, draws=0, sites=None, table=None):
+    def __init__(self, id, engine, hp, make_batches, vocab=None, seed=0, weights=None, draws=0, sites=None, table=None,
+                 stream=False):
         self.id, self.engine, self.hp, self.vocab, self.seed = id, engine, hp, vocab, seed
         self.weights = weights                  # the engine tests' own weight criterion at this shape
         self.draws, self.sites = draws, sites   # dropout: multipliers per rating, and how they map to the oracle's sites
+        self.stream = stream                    # the CPU stand-in masks are the device's Philox stream
         self.table = table                      # (an ID table or bias vector, the slots of `data` that name its rows)
         self._make, self._batches = make_batches, None
 
@@ -92,6 +101,60 @@ def idnet_cases():
     return out
 
 
+# ------------------------------------------------------------------------------------ the text families' dropout
+def text_layout(hp):
+    """The dropout draws of one rating of a native text step, in stream order (ND of include/r4r.h, site-major):
+    [(oracle site, draws per rating, shape of the site's tensor for B ratings)].  A site of None is drawn and unused:
+    plain `transnet` draws the ten ID-vector multipliers of `transnet++` and has no ID vectors."""
+    mt, L, R = hp['model_type'], int(hp['latent_size']), int(hp.get('narre_num_reviews') or 0)
+    row = lambda B: (B, L)                                                                         # noqa: E731
+    if mt in ('deepconn', 'deepconn++'):
+        out = [('user_conv.dropout', L, row), ('item_conv.dropout', L, row)]
+        return out + ([('final.2', L, row)] if mt == 'deepconn++' else [])                          # 2L, 3L
+    if mt == 'NARRE':
+        return [('user_conv.dropout', R * L, lambda B: (B * R, L)), ('item_conv.dropout', R * L, lambda B: (B * R, L)),
+                ('attention_scorer_user.2', R * L, lambda B: (B, R, L)),
+                ('attention_scorer_item.2', R * L, lambda B: (B, R, L)),
+                ('dropout.user', L, row), ('dropout.item', L, row), ('final.0', L, row)]            # 4RL + 3L
+    assert mt in ('transnet', 'transnet++'), mt
+    ids = mt == 'transnet++'
+    return [('source.user_conv.dropout', L, row), ('source.item_conv.dropout', L, row), ('target.conv.dropout', L, row),
+            ('source.dropout', L, row), ('target.dropout', L, row),
+            ('dropout.user' if ids else None, 5, lambda B: (B, 5)),
+            ('dropout.item' if ids else None, 5, lambda B: (B, 5))]                                 # 5L + 10
+
+
+def text_draws(hp):
+    return sum(n for _, n, _ in text_layout(hp))
+
+
+def text_sites(hp):
+    """[B, ND] multipliers -> {oracle site: its multipliers}."""
+    def sites(mult):
+        out, at = {}, 0
+        for site, n, shape in text_layout(hp):
+            if site is not None:
+                out[site] = mult[:, at:at + n].reshape(shape(mult.shape[0]))
+            at += n
+        assert at == mult.shape[1], (at, tuple(mult.shape))
+        return out
+    return sites
+
+
+def with_dropout(cases, twins):
+    """`cases` followed by their dropout-on twins: twins = [(id of a case in `cases`, p)]."""
+    by_id = {c.id: c for c in cases}
+    out = list(cases)
+    for id, p in twins:
+        c = by_id[id]
+        hp = dict(c.hp, dropout=p)
+        twin = Case('%s-p%s' % (id, p), c.engine, hp, c._make, vocab=c.vocab, seed=c.seed, weights=c.weights,
+                    draws=text_draws(hp), sites=text_sites(hp), table=c.table, stream=True)
+        twin.batches = c.batches                             # the same batches, made once
+        out.append(twin)
+    return out
+
+
 def pooled(docs, pool, gen):
     """Every document of `docs` ([..., T]) replaced by one of its first `pool` documents.  The large-batch text cases
     are about the ID rows; with thousands of distinct documents some max-pool always sits within rounding of a tie, where
@@ -140,7 +203,8 @@ def narre_cases():
         out.append(Case('narre-' + id, 'NarreEngine', hp, narre_batches(B, R, W, V, U, I, 40 + B + L, few), vocab=V, seed=12,
                         weights=weights_outliers(2e-3, wmax),
                         table=('user_embedding.weight', (1, 5))))
-    return out
+    return with_dropout(out, [('narre-fused-B96', 0.5), ('narre-L24-R20', 0.5), ('narre-L33-R33', 0.3),
+                              ('narre-L48-R10', 0.5), ('narre-B373', 0.3)])
 
 
 def doc_batches(B, T, V, U, I, seed, users=None, items=None):
@@ -174,7 +238,8 @@ def deepconnpp_cases():
                         doc_batches(B, T, V, U, I, 140 + L + B, users, items), vocab=V, seed=83,
                         weights=weights_outliers(2e-3, 5e-4 if L <= 32 else 2.5e-3),
                         table=('user_bias', (5,))))
-    return out
+    return with_dropout(out, [('deepconnpp-L16-B12', 0.5), ('deepconnpp-L17-B12', 0.3), ('deepconnpp-L32-B12', 0.3),
+                              ('deepconnpp-L33-B12', 0.5), ('deepconnpp-L64-B12', 0.3), ('deepconnpp-L16-B300', 0.3)])
 
 
 def transnet_cases():
@@ -187,18 +252,43 @@ def transnet_cases():
                         doc_batches(B, T, V, U, I, 160 + L + B, users), vocab=V, seed=4,
                         weights=weights_outliers(2e-3, 5e-4 if L <= 32 else 2.5e-3),
                         table=('user_embedding.weight', (5,)) if mt == 'transnet++' else None))
-    return out
+    return with_dropout(out, [('transnet-L24-B12', 0.3), ('transnet-L48-B12', 0.5), ('transnet-L64-B12', 0.3),
+                              ('transnet++-L24-B12', 0.5), ('transnet++-L48-B12', 0.3), ('transnet++-L64-B12', 0.5),
+                              ('transnet++-L24-B300', 0.3)])
 
 
 def deepconn_cases():
     B, T, E, V, U, I = 12, 60, 32, 300, 40, 30
-    return [Case('deepconn-L%d' % L, 'DeepCoNNEngine', _doc_hp('deepconn', L, B, T, E, U, I),
-                 doc_batches(B, T, V, U, I, 90 + L), vocab=V, seed=61,
-                 weights=weights_outliers(2e-3, 5e-4 if L <= 32 else 2.5e-3)) for L in (16, 17, 64, 65, 128)]
+    out = [Case('deepconn-L%d' % L, 'DeepCoNNEngine', _doc_hp('deepconn', L, B, T, E, U, I),
+                doc_batches(B, T, V, U, I, 90 + L), vocab=V, seed=61,
+                weights=weights_outliers(2e-3, 5e-4 if L <= 32 else 2.5e-3)) for L in (16, 17, 64, 65, 128)]
+    return with_dropout(out, [('deepconn-L16', 0.3), ('deepconn-L17', 0.5), ('deepconn-L64', 0.3), ('deepconn-L65', 0.5),
+                              ('deepconn-L128', 0.3)])
 
 
 def all_cases():
     return mf_cases() + idnet_cases() + narre_cases() + deepconnpp_cases() + transnet_cases() + deepconn_cases()
+
+
+def stream_keep(case, step):
+    """bool [B, ND]: the keep pattern the case's engine draws on `step` (0 or 1).  The engines of the step-state tests
+    have the default seed and start at position 0; draw k of rating b of a step that starts at `at` is position
+    at + b ND + k, and a step of B ratings advances the position by B ND (tests/test_gpu_dropout_stream.py pins that)."""
+    sizes = [y.numel() for _, y in case.batches()]
+    at, B = sum(sizes[:step]) * case.draws, sizes[step]
+    keep = philox_ref.engine_keep(ENGINE_SEED, at, B * case.draws, np.float32(case.hp['dropout']))
+    return torch.from_numpy(keep.reshape(B, case.draws))
+
+
+def stream_multipliers(case, step):
+    """Stand-in for the multipliers the device draws on `step`, where no device is: its own stream."""
+    return stream_keep(case, step).float() * float(philox_ref.scale(case.hp['dropout']))
+
+
+def stand_in_multipliers(case, step):
+    if case.stream:
+        return stream_multipliers(case, step)
+    return random_multipliers(case, case.batches()[step][1].numel(), step)
 
 
 def random_multipliers(case, B, step):

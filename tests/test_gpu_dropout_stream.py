@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import philox_ref as P
+from helpers import multipliers
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -121,20 +122,6 @@ def build(mt, p):
     assert (hp['batch_size'], hp['latent_size'], hp['narre_num_reviews']) == (B, L, R)
     model.train()
     return hp, reader, model, engine
-
-
-def multipliers(engine, data):
-    """The multipliers the last training step drew, flattened: the [n, ND] block is one contiguous counter range."""
-    from reviews4rec_amd import engine as E
-    n = data[5].numel()
-    if isinstance(engine, E.DeepCoNNEngine):
-        m = engine.dropout_multipliers(n, data[3].reshape(n, -1).shape[1])
-    elif isinstance(engine, (E.MFEngine, E.IdNetEngine)):
-        m = engine.dropout_multipliers(n)
-    else:
-        m = engine.dropout_multipliers(data)
-    torch.cuda.synchronize()
-    return m.reshape(-1)
 
 
 def run_sequence(mt, p, start=None):

@@ -8,12 +8,22 @@ each summation path (tests/step_state_cases.py); every element of every moment, 
 after step 2 (helpers.assert_step_state; tests/test_step_state_checker.py tests that checker), and a second run from
 the same state leaves the same bits.
 
+The text families' cases have twins with dropout on (`-p0.5` / `-p0.3`).  The forward of a dropout site multiplies by
+0 or 1 / (1 - p), its backward has to multiply by the same; a backward that multiplies by the 0 / 1 keep pattern
+instead puts the factor 1 - p on the gradient of every parameter upstream of the site, which two Adam steps hide from
+the weights and the SE and exp_avg shows.  Each twin's device masks equal the Philox stand-in the CPU checker ran on
+(tests/test_step_state_checker.py), element for element, and are injected into the float64 reference.
+
+Every rating's SE is compared on its own (rtol 1e-4, atol 1e-5), on every case.
+
 No absolute tolerance is widened: every tensor is held to rtol 1e-4, atol 1e-7 (exp_avg_sq: 1e-10)."""
 import pytest
 import torch
 
-from helpers import StateStandIn, assert_step_state, float64_step_reference, state_distances
-from step_state_cases import (deepconn_cases, deepconnpp_cases, idnet_cases, mf_cases, narre_cases, transnet_cases)
+from helpers import (StateStandIn, assert_per_rating_se, assert_step_state, float64_step_reference, multipliers,
+                     state_distances)
+from step_state_cases import (deepconn_cases, deepconnpp_cases, idnet_cases, mf_cases, narre_cases, stream_keep,
+                              transnet_cases)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -47,10 +57,17 @@ def run(case, check):
     ref = float64_step_reference(P0, case.hp)
     o32 = float64_step_reference(P0, case.hp, dtype=torch.float32)
     bits, before = [], None
-    for data, y in case.batches():
+    for step, (data, y) in enumerate(case.batches()):
         dev = [None if d is None else d.to(DEV) for d in data]
         se = eng.train_step(dev, y.to(DEV)).cpu().clone()
-        masks = case.sites(eng.dropout_multipliers(y.numel()).cpu()) if case.draws else None
+        masks = None
+        if case.draws:
+            mult = multipliers(eng, dev).cpu().reshape(y.numel(), case.draws)
+            if case.stream:                                  # the CPU pre-check saw these very masks
+                off = torch.nonzero((mult != 0) != stream_keep(case, step))
+                assert off.numel() == 0, ('%s step %d: %d draws differ from the Philox stand-in, first at %s'
+                                          % (case.id, step + 1, off.shape[0], off[0].tolist()))
+            masks = case.sites(mult)
         m, v = eng.moments()
         sd = {k: t.detach().cpu().clone() for k, t in model.state_dict().items()}
         bits.append((se, sd, {k: t.cpu().clone() for k, t in m.items()}, {k: t.cpu().clone() for k, t in v.items()}))
@@ -61,6 +78,7 @@ def run(case, check):
                   % (case.engine, case.id, r.step, worst(state_distances(eng, r, dev)),
                      worst(state_distances(StateStandIn(r32), r))))
             torch.testing.assert_close(se.double().sum(), torch.tensor(r.sse, dtype=torch.float64), rtol=1e-4, atol=1e-3)
+            assert_per_rating_se(se, r, what=case.id)
             assert_step_state(eng, model, r, data=dev, weights=case.weights, what=case.id)
         before = sd
     return bits
@@ -94,24 +112,30 @@ def test_idnet_step_state(case):
 def test_narre_step_state(case):
     """r4r_narre_step's fused ID role with rows that hundreds of entries hit, its <= 32 instantiation, the split form
     (L or R beyond 32 -> r4r_narre_rows_apply_large), B = 372 / 373 on either side of the fused 4,096-entry limit,
-    B = 512 (the stand-alone rows-apply launch) and B = 2,048 (22,528 entries -> r4r_narre_rows_apply_large)."""
+    B = 512 (the stand-alone rows-apply launch) and B = 2,048 (22,528 entries -> r4r_narre_rows_apply_large).
+    The twins draw at all seven sites (the towers' outputs, the two scorers' hidden layers, the two ID rows, the
+    product): the fused form, both instantiations, the split form and the first split batch size, at p 0.5 / 0.3."""
     check_case(case)
 
 
 @pytest.mark.parametrize('case', deepconnpp_cases(), ids=repr)
 def test_deepconnpp_step_state(case):
-    """r4r_deepconnpp_step at L 16 / 17 / 32 / 33 / 64, and B = 300 with users drawn from 12 ids, items from 8."""
+    """r4r_deepconnpp_step at L 16 / 17 / 32 / 33 / 64, and B = 300 with users drawn from 12 ids, items from 8.
+    Every case has a twin that draws at its three sites (the towers' outputs and the head's hidden layer)."""
     check_case(case)
 
 
 @pytest.mark.parametrize('case', transnet_cases(), ids=repr)
 def test_transnet_step_state(case):
     """r4r_transnet_step, `transnet` and `transnet++`, L 24 / 48 / 64: the moments of its three optimisers' groups;
-    transnet++ also at B = 300 with users drawn from 12 ids."""
+    transnet++ also at B = 300 with users drawn from 12 ids.  Every case has a twin that draws at its five (transnet)
+    or seven (transnet++: the two ID rows) sites; a scale lost at a source site shows in the `source` group's moments,
+    at a target site in the `target` group's."""
     check_case(case)
 
 
 @pytest.mark.parametrize('case', deepconn_cases(), ids=repr)
 def test_deepconn_step_state(case):
-    """r4r_deepconn_step at L 16 / 17 / 64 / 65 / 128 (the 65 .. 128 head instantiation keeps the old tail)."""
+    """r4r_deepconn_step at L 16 / 17 / 64 / 65 / 128 (the 65 .. 128 head instantiation keeps the old tail).  Every
+    case has a twin that draws at the two towers' outputs."""
     check_case(case)

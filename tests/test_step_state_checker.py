@@ -3,14 +3,18 @@ an engine.  On the inputs of every case of tests/test_gpu_step_state.py the orac
 alone stays inside the tolerance -- and every seeded mistake in the summation of duplicate rows must raise, from the
 Adam moments alone.  The weights-only criteria the edge-shape tests used so far pass the first two mistakes: two Adam
 steps hide a positive factor on a gradient (step 1 is lr g / (|g| + eps), step 2 is homogeneous of degree 0), which is
-why the moments are compared at all."""
+why the moments are compared at all.
+
+The same holds for dropout: the text families' dropout-on cases run on the masks the device will draw (the Philox
+stream, step_state_cases.stream_multipliers), and a dropout site whose backward loses the factor 1 / (1 - p), or hands
+dropped elements a gradient, must raise at every site -- while the weights-only criteria pass the lost factor."""
 import pytest
 import torch
 
 import oracle
-from helpers import (StateStandIn, assert_step_state, float64_step_reference, ill_conditioned, is_row_tensor, oracle_atol,
-                     state_distances, weights_failures, weights_outliers)
-from step_state_cases import all_cases, random_multipliers
+from helpers import (StateStandIn, assert_per_rating_se, assert_step_state, float64_step_reference, ill_conditioned,
+                     is_row_tensor, oracle_atol, state_distances, weights_failures, weights_outliers)
+from step_state_cases import all_cases, stand_in_multipliers
 
 CASES = all_cases()
 BY_ID = {c.id: c for c in CASES}
@@ -19,14 +23,19 @@ BY_ID = {c.id: c for c in CASES}
 def masks_of(case, step):
     if not case.draws:
         return None
-    B = case.batches()[step][1].numel()
-    return case.sites(random_multipliers(case, B, step))
+    return case.sites(stand_in_multipliers(case, step))
 
 
-def run(case, mistake=None):
+_UNSEEDED = {}
+
+
+def run(case, mistake=None, at_site=None):
     """The two steps of a case by the float32 oracle, each next to the float64 step from the same weights: a list of
     (float32 StepState, float64 StepState).  mistake(step, data, y, masks, grads, params) edits the gradients the float32
-    oracle's Adam sees."""
+    oracle's Adam sees; at_site(masks) edits the dropout multipliers the float32 oracle sees (the float64 step keeps
+    the true ones).  The unseeded run of a case is computed once and shared; nothing changes it."""
+    if mistake is None and at_site is None and case.id in _UNSEEDED:
+        return _UNSEEDED[case.id]
     o32 = float64_step_reference(case.params(), case.hp, dtype=torch.float32)
     ref = float64_step_reference(case.params(), case.hp)
     out, before = [], None
@@ -35,9 +44,11 @@ def run(case, mistake=None):
         perturb = None
         if mistake is not None:
             perturb = lambda grads, params, a=(step, data, y, masks): mistake(*a, grads, params)   # noqa: E731
-        s32 = o32.step(data, y, masks, perturb=perturb)
+        s32 = o32.step(data, y, masks if at_site is None else at_site(masks), perturb=perturb)
         out.append((s32, ref.step(data, y, masks, start=before)))
         before = s32.params
+    if mistake is None and at_site is None:
+        _UNSEEDED[case.id] = out
     return out
 
 
@@ -54,6 +65,30 @@ def test_the_float32_oracle_stays_inside_the_tolerance_on_every_case(case):
     if case.table is not None:                               # the case has what the seeded mistakes need
         zero = steps[-1][1].zero_so_far[case.table[0]]
         assert bool((zero.all(dim=-1) if zero.dim() > 1 else zero).any()), 'no row without a gradient'
+
+
+@pytest.mark.parametrize('case', CASES, ids=repr)
+def test_the_float32_oracle_s_per_rating_se_stays_inside_the_tolerance_on_every_case(case):
+    """Each rating's squared error of the float32 oracle against float64, on both steps, at the tolerance
+    tests/test_gpu_step_state.py holds the engines to (rtol 1e-4, atol 1e-5)."""
+    for s32, s64 in run(case):
+        assert s32.se.numel() == s64.se.numel() == case.batches()[s64.step - 1][1].numel()
+        assert_per_rating_se(s32.se, s64, what=case.id)
+
+
+@pytest.mark.parametrize('case', [c for c in CASES if c.stream], ids=repr)
+def test_a_dropout_case_draws_at_every_site_on_both_steps(case):
+    """The stand-in masks of a dropout-on case: every site named by the oracle's forward, each with dropped and kept
+    elements, kept ones at 1 / (1 - p); the two steps draw different masks (step 2 starts where step 1 stopped)."""
+    p = float(case.hp['dropout'])
+    both = [masks_of(case, step) for step in range(2)]
+    for masks in both:
+        assert len(masks) == SITES[case.hp['model_type']]
+        for site, m in masks.items():
+            kept = m[m != 0]
+            assert 0 < kept.numel() < m.numel(), site
+            assert bool((kept == kept[0]).all()) and abs(float(kept[0]) - 1 / (1 - p)) < 1e-6, site
+    assert any(a.shape != b.shape or not torch.equal(a, b) for a, b in zip(both[0].values(), both[1].values()))
 
 
 # ------------------------------------------------------------------------------------------------ seeded mistakes
@@ -133,6 +168,88 @@ def untouched_row_given_a_gradient(case):
             g[int(never[0])] = 1e-3
             grads[name] = g
     return mistake
+
+
+# ------------------------------------------------------------------------------------------------ dropout sites
+SITES = {'deepconn': 2, 'deepconn++': 3, 'NARRE': 7, 'transnet': 5, 'transnet++': 7}
+
+
+class SiteMistake:
+    """In place of a site's multipliers: the forward is x * mult to the bit, the gradient flows through x * through."""
+
+    def __init__(self, mult, through):
+        self.mult, self.through = mult, through
+
+    def to(self, dtype):
+        return SiteMistake(self.mult.to(dtype), self.through.to(dtype))
+
+    def __rmul__(self, x):
+        back = x * self.through
+        return (x * self.mult).detach() + (back - back.detach())
+
+
+def scale_lost_in_backward(site):
+    """The backward of `site` multiplies by the 0 / 1 keep pattern where the forward multiplied by 0 or 1 / (1 - p)."""
+    def at_site(masks):
+        return dict(masks, **{site: SiteMistake(masks[site], (masks[site] != 0).to(masks[site].dtype))})
+    return at_site
+
+
+def dropped_elements_keep_their_gradient(site):
+    """The backward of `site` multiplies every element by 1 / (1 - p), the dropped ones too."""
+    def at_site(masks):
+        return dict(masks, **{site: SiteMistake(masks[site], torch.full_like(masks[site], float(masks[site].max())))})
+    return at_site
+
+
+def caught_at_site(case, at_site):
+    """caught(), for a mistake seeded through the masks."""
+    steps = run(case, at_site=at_site)
+    raised = []
+    for s32, s64 in steps:
+        try:
+            assert_step_state(StateStandIn(s32, with_grads=False), StateStandIn(s32), s64, what=case.id)
+            raised.append(False)
+        except AssertionError:
+            raised.append(True)
+    return raised, steps
+
+
+# one dropout-on case per family, every site of it
+SITE_CASES = ['deepconn-L17-p0.5', 'deepconnpp-L33-B12-p0.5', 'narre-L24-R20-p0.5', 'transnet-L48-B12-p0.5',
+              'transnet++-L64-B12-p0.5']
+EVERY_SITE = [(id, site) for id in SITE_CASES for site in masks_of(BY_ID[id], 0)]
+assert [sum(1 for i, _ in EVERY_SITE if i == id) for id in SITE_CASES] == [2, 3, 7, 5, 7]
+
+
+@pytest.mark.parametrize('mistake', [scale_lost_in_backward, dropped_elements_keep_their_gradient],
+                         ids=lambda f: f.__name__)
+@pytest.mark.parametrize('case,site', EVERY_SITE)
+def test_a_seeded_mistake_at_a_dropout_site_raises(case, site, mistake):
+    """At every dropout site of one case per text family, from the moments alone, on step 1 and on step 2.  The seeded
+    forward is the true one to the bit: the SE does not move."""
+    case = BY_ID[case]
+    raised, steps = caught_at_site(case, mistake(site))
+    assert raised == [True, True]
+    assert torch.equal(steps[0][0].se, run(case)[0][0].se)
+
+
+@pytest.mark.parametrize('case,site', [
+    ('deepconn-L17-p0.5', 'user_conv.dropout'), ('deepconnpp-L33-B12-p0.5', 'final.2'),
+    ('deepconnpp-L33-B12-p0.5', 'user_conv.dropout'), ('transnet-L48-B12-p0.5', 'source.dropout'),
+    ('transnet-L48-B12-p0.5', 'target.dropout'), ('transnet-L48-B12-p0.5', 'target.conv.dropout'),
+    ('transnet++-L64-B12-p0.5', 'dropout.user')])
+def test_the_weights_only_criteria_pass_a_scale_lost_in_the_backward_of_a_dropout_site(case, site):
+    """Why the dropout-on cases exist: with the factor 1 / (1 - p) lost in the backward of one site -- the gradient of
+    every parameter upstream of it halved -- the weights after each of two Adam steps stay inside the case's own
+    weights criterion and every rating's SE inside its tolerance, which is all the dropout-on engine tests compared;
+    the moments raise on both steps."""
+    case = BY_ID[case]
+    raised, steps = caught_at_site(case, scale_lost_in_backward(site))
+    assert raised == [True, True]
+    for s32, s64 in steps:
+        assert weights_failures(s32.params, s64.params, case.weights) == []
+        assert_per_rating_se(s32.se, s64, what=case.id)
 
 
 # one case per engine that sums ID rows (TransNet++, whose oracle step is its own, below)
