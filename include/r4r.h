@@ -1793,6 +1793,60 @@ int r4r_narre_whatif(const float *z_u, const float *logit_u, const float *own_u,
                      float *out_score,                                        /* [n_p, V]                             */
                      void *stream);
 
+/* ------------------------------------------------------------------------
+ * What-if documents: the single-document families' tower over VARIANTS of an owner's document -- chosen reviews taken
+ * away, chosen positions occluded -- from the resident pools (csrc/tower_variants.hip, csrc/docs_masked_device.h).
+ * Replaces  the loader's `skip`: a training rating's documents leave the rating's own review out of both sides
+ *                                                                       data.py:223-235
+ *           pad_and_join / pad_only: cut / zero padded to input_length  data.py:181-210
+ *           the documents of a rating outside the training split        data.py:240-246
+ *           generalised from ONE removed review to a set, for DeepCoNN, DeepCoNN++ and the TransNets, whose towers read
+ *           one document per owner (NARRE's removal re-selects slots and needs no tower: "NARRE what-if scores").
+ * The pool (tok, rev_off, first, owners) and ids [n] are those of "Tower spans"; the document layout only (R = 0).
+ *
+ * r4r_tower_build_variants: ONE launch, one workgroup per row.  Row r, with owner o = ids[r], rb = first[o],
+ *   count = first[o + 1] - rb:
+ *     kept list   the reviews s in [0, count), ascending, with s >= 64 or bit s of drop[r] clear.  Bits at or beyond count
+ *                 are ignored; drop == NULL removes nothing; reviews from the 65th on can never be dropped.
+ *     document    docs[r, :] = the tokens of the kept reviews concatenated, the first T of them, padded with word 0.
+ *                 With exactly one bit set: data._np_docs(..., skip = that bit, T) integer for integer, the document the
+ *                 loader gives a training rating.  With no bit set: r4r_tower_build (R = 0).
+ *     occlusion   every position p = occ_pos[j], j in [occ_off[r], occ_off[r + 1]), with 0 <= p < T holds word 0 instead
+ *                 (no shift: the padding the model already knows).  Positions outside [0, T) are ignored, repeats are
+ *                 harmless.  occ_off == NULL occludes nothing; occ_pos may be NULL only then.  occ_off's entries index
+ *                 occ_pos absolutely and need not start at 0: the slice occ_off + a of a longer table serves rows a ..
+ *                 with the same occ_pos, without a copy (what the span's rounds pass).
+ *     other ids   an id outside [0, owners) gives a zero document; nothing outside the pool is read whatever ids, drop
+ *                 or occ_pos hold.
+ *   Every element of docs [n, T] is written exactly once.  Refused before the launch and the first dereference, in the
+ *   entry point's own name: a null tok, rev_off, first, ids or docs; n outside [0, 2^31); owners < 0; T < 1 or
+ *   T > 65536 (the occlusion flags of one row: one bit per position in 8 KB of LDS); occ_off given with a NULL occ_pos.
+ *   n == 0 returns R4R_OK and enqueues nothing.
+ *
+ * r4r_tower_span_variants: r4r_tower_span_fwd at R = 0 with r4r_tower_build_variants in r4r_tower_build's place:
+ *   round g covers rows [g group, min(n, (g + 1) group)) and enqueues the builder (drop + g group, occ_off + g group),
+ *   r4r_textcnn_fwd over the round's rows and r4r_linear_fwd (no ReLU) into latent + g group L -- the kernels, arguments
+ *   and algorithm choice of the per-call entry points, so a span over `group` gives the bits of one
+ *   r4r_tower_build_variants + r4r_textcnn_fwd + r4r_linear_fwd call per chunk of `group` rows, and with NULL drop and
+ *   occ_off r4r_tower_span_fwd's latents bit for bit.  pooled [n, F] float32 and argmax [n, F] int32 (either nullable):
+ *   the rounds' own r4r_textcnn_fwd outputs, copied out of the workspace before the next round overwrites them (what
+ *   r4r_textcnn_phrases lists a variant's windows from); asking for them changes no bit of latent.
+ *   ws: r4r_tower_span_variants_ws_bytes(group, ...) bytes, r4r_tower_span_fwd's layout.  groups_done (host, out,
+ *   nullable): rounds enqueued before an error.  Refusals: r4r_tower_span_fwd's (null pointers, group < 1, E % 4 != 0,
+ *   F > 112, a short workspace: R4R_ERR_WORKSPACE) and the builder's, before the first launch.  n == 0 returns R4R_OK and
+ *   enqueues nothing.  Nothing allocates, nothing synchronises, no training state is touched.
+ * ---------------------------------------------------------------------- */
+int r4r_tower_build_variants(const int32_t *tok, const int64_t *rev_off, const int64_t *first, int64_t owners,
+                             const int64_t *ids, const int64_t *drop, const int64_t *occ_off, const int32_t *occ_pos,
+                             int64_t n, int T, int64_t *docs, void *stream);
+size_t r4r_tower_span_variants_ws_bytes(int64_t group, int T, int E, int F, int L, int64_t V);
+int r4r_tower_span_variants(const int32_t *tok, const int64_t *rev_off, const int64_t *first, int64_t owners,
+                            const int64_t *ids, const int64_t *drop, const int64_t *occ_off, const int32_t *occ_pos,
+                            int64_t n, int64_t group, int T, const float *table, int64_t V, const float *conv_w,
+                            const float *conv_b, const float *fc_w, const float *fc_b, int E, int F, int L,
+                            float *latent, float *pooled, int32_t *argmax, void *ws, size_t ws_bytes,
+                            int64_t *groups_done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

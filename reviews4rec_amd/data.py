@@ -126,6 +126,46 @@ def _np_docs(tok, rev_off, rb, re, skip, T):
     return np.where(ok, padded[np.where(ok, src, len(tok))], 0).astype(np.int64)
 
 
+MASK_SLOTS = 64                                            # _np_docs_masked: one bit of an int64 mask per review
+
+
+def _np_docs_masked(tok, rev_off, rb, re, drop, occ, T):
+    """[N, T]: ``_np_docs`` with the one ``skip`` generalised to a set (include/r4r.h, "What-if documents"; the host
+    twin of r4r_tower_build_variants).  Row n holds the tokens of reviews [rb, re) minus every review rb + s, s < 64,
+    whose bit s is set in ``drop[n]`` (int64 [N] or None; bits at or beyond re - rb are ignored, reviews from the 65th
+    on are always kept), cut / zero padded to T; then word 0 at every position of ``occ[n]`` (int [N, P] or None)
+    inside [0, T) -- no shift; other values, -1 among them, are ignored."""
+    rb, re = np.asarray(rb, dtype=np.int64), np.asarray(re, dtype=np.int64)
+    N = len(rb)
+    count = np.maximum(re - rb, 0)
+    bits = np.zeros(N, np.uint64) if drop is None else np.asarray(drop, dtype=np.int64).view(np.uint64)
+    s = np.arange(MASK_SLOTS, dtype=np.int64)[None, :]
+    live = s < count[:, None]
+    at = rev_off[np.where(live, rb[:, None] + s, 0)]
+    kept = live & (((bits[:, None] >> s.astype(np.uint64)) & np.uint64(1)) == 0)
+    lens = np.where(kept, rev_off[np.where(live, rb[:, None] + s + 1, 0)] - at, 0)
+    cum = np.cumsum(lens, axis=1)
+    delta = at - (cum - lens)
+    end = rev_off[np.maximum(re, rb)]
+    tail = np.where(count > MASK_SLOTS, rev_off[np.where(count > MASK_SLOTS, rb + MASK_SLOTS, 0)], end)
+    p = np.arange(T, dtype=np.int64)[None, :]
+    lo = np.zeros((N, T), np.int64)
+    for k in range(MASK_SLOTS):                                # the number of sums <= p: the review holding position p
+        lo += cum[:, k:k + 1] <= p
+    head = cum[:, -1:]
+    inside = p < head
+    src = np.where(inside, p + np.take_along_axis(delta, np.minimum(lo, MASK_SLOTS - 1), 1), tail[:, None] + (p - head))
+    ok = inside | (src < end[:, None])
+    padded = np.concatenate([tok, np.zeros(1, tok.dtype)])
+    docs = np.where(ok, padded[np.where(ok, src, len(tok))], 0).astype(np.int64)
+    if occ is not None:
+        occ = np.asarray(occ, dtype=np.int64).reshape(N, -1)
+        hit = (occ >= 0) & (occ < T)
+        rows = np.broadcast_to(np.arange(N)[:, None], occ.shape)
+        docs[rows[hit], occ[hit]] = 0
+    return docs
+
+
 def _np_reviews(tok, rev_off, rb, re, skip, R, W):
     """[N, R, W] (NARRE, data.py:144-172): review slot r = the r-th remaining review, each cut / padded to W."""
     r = np.arange(R, dtype=np.int64)[None, :]

@@ -414,13 +414,14 @@ def main_NeuMF(hyper_params, readers=None, user_count=None, item_count=None, dp=
     like the reference does."""
     from .pytorch_models.NeuMF import GMF, MLP, NeuMF
     from .recommend import check_catalogue_metrics_request, check_explain_request, check_recommend_request
-    from .recommend import check_explain_pairs_request, check_explain_words_request
+    from .recommend import check_explain_pairs_request, check_explain_reviews_request, check_explain_words_request
     from .utils import load_user_item_counts
     check_recommend_request(hyper_params)                     # (NeuMF has no catalogue form: says so before training)
     check_catalogue_metrics_request(hyper_params)
     check_explain_request(hyper_params)
     check_explain_words_request(hyper_params)
     check_explain_pairs_request(hyper_params)
+    check_explain_reviews_request(hyper_params)
     if readers is None:
         user_count, item_count = load_user_item_counts(hyper_params)
         train_reader, test_reader, val_reader, ranking_reader, hyper_params = _load_readers(hyper_params, False)
@@ -466,13 +467,14 @@ def main_pytorch(hyper_params, readers=None, user_count=None, item_count=None, r
     train-set counts, the three loaders, and the negatives reader for HR@1."""
     import reviews4rec_amd
     from .recommend import check_catalogue_metrics_request, check_explain_request, check_recommend_request
-    from .recommend import check_explain_pairs_request, check_explain_words_request
+    from .recommend import check_explain_pairs_request, check_explain_reviews_request, check_explain_words_request
     from .utils import load_user_item_counts
     check_recommend_request(hyper_params)                     # (callers that come here directly, not through main())
     check_catalogue_metrics_request(hyper_params)
     check_explain_request(hyper_params)
     check_explain_words_request(hyper_params)
     check_explain_pairs_request(hyper_params)
+    check_explain_reviews_request(hyper_params)
     Model = reviews4rec_amd.get_model_class(hyper_params['model_type'])
     if review_based_model is None:
         review_based_model = hyper_params['model_type'] not in ['bias_only', 'MF', 'MF_dot', 'NeuMF']
@@ -528,6 +530,11 @@ def main_pytorch(hyper_params, readers=None, user_count=None, item_count=None, r
         from .recommend import write_pair_phrases
         write_pair_phrases(hyper_params['explain_pairs_path'], model, hyper_params, train_reader,
                            hyper_params['explain_pairs_k'], engine=engine)
+    if hyper_params.get('explain_reviews_k') and (dp is None or not dp.on or dp.rank == 0):
+        # the reviews behind every recommended pair (recommend.Catalogue.leave_one_out), from the same model: rank 0 writes
+        from .recommend import write_pair_reviews
+        write_pair_reviews(hyper_params['explain_reviews_path'], model, hyper_params, train_reader,
+                           hyper_params['explain_reviews_k'], engine=engine)
     return metrics, user_count_mse_map, item_count_mse_map
 
 
@@ -540,12 +547,13 @@ def main(hyper_params, gpu_id=None):
         raise ValueError('model_type %r (Surprise / HFT / MPCN) is outside the accelerated path; run it with the '
                          'reference' % (mt,))
     from .recommend import check_catalogue_metrics_request, check_explain_request, check_recommend_request
-    from .recommend import check_explain_pairs_request, check_explain_words_request
+    from .recommend import check_explain_pairs_request, check_explain_reviews_request, check_explain_words_request
     check_recommend_request(hyper_params)                     # refuse before any training, with the reason
     check_catalogue_metrics_request(hyper_params)
     check_explain_request(hyper_params)
     check_explain_words_request(hyper_params)
     check_explain_pairs_request(hyper_params)
+    check_explain_reviews_request(hyper_params)
     method = main_NeuMF if mt == 'NeuMF' else main_pytorch
     metrics, user_count_mse_map, item_count_mse_map = method(hyper_params, gpu_id=gpu_id)
     return metrics

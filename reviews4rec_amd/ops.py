@@ -131,6 +131,82 @@ def textcnn_phrases(pooled, argmax, k, T, weights=None, idx=None):
     return pos, score, filters, tokens, windows
 
 
+VARIANT_SLOTS = 64            # r4r_tower_build_variants: a mask removes reviews 0 .. 63 of an owner
+VARIANT_MAX_T = 65536         # ... and a document has at most this many words
+
+
+def _variant_args(pool, ids, drop, occ_off, occ_pos):
+    """The pool (tok, rev_off, first, nb -- ``data._Pool.device``'s tuple) and the per-row arguments of the two variant
+    entry points, checked: ids int64 [n]; drop int64 [n] or None; occ_off int64 [n + 1] with occ_pos int32, or both
+    None."""
+    tok, rev_off, first = pool[0], _i64(pool[1], 'rev_off'), _i64(pool[2], 'first')
+    if not tok.is_cuda or tok.dtype != torch.int32:
+        raise RuntimeError('reviews4rec_amd.ops: tok must be int32 on a ROCm device, got %s on %s' % (tok.dtype, tok.device))
+    ids = _i64(ids, 'ids').reshape(-1)
+    n = int(ids.numel())
+    if drop is not None:
+        drop = _i64(drop, 'drop').reshape(-1)
+        if drop.numel() != n:
+            raise RuntimeError('reviews4rec_amd.ops: drop must be [n] = [%d], got %d masks' % (n, drop.numel()))
+    if (occ_off is None) != (occ_pos is None):
+        raise RuntimeError('reviews4rec_amd.ops: occ_off and occ_pos come together')
+    if occ_off is not None:
+        occ_off = _i64(occ_off, 'occ_off').reshape(-1)
+        if occ_off.numel() != n + 1:
+            raise RuntimeError('reviews4rec_amd.ops: occ_off must be [n + 1] = [%d], got %d' % (n + 1, occ_off.numel()))
+        if not occ_pos.is_cuda or occ_pos.dtype != torch.int32:
+            raise RuntimeError('reviews4rec_amd.ops: occ_pos must be int32 on a ROCm device, got %s on %s'
+                               % (occ_pos.dtype, occ_pos.device))
+        occ_pos = occ_pos.contiguous().reshape(-1)
+        if occ_pos.numel() == 0:                                # (an empty tensor has no address to pass)
+            occ_pos = torch.zeros(1, dtype=torch.int32, device=occ_pos.device)
+    return tok.contiguous(), rev_off, first, int(first.numel()) - 1, ids, drop, occ_off, occ_pos, n
+
+
+def tower_build_variants(pool, ids, T, drop=None, occ_off=None, occ_pos=None):
+    """r4r_tower_build_variants (include/r4r.h, "What-if documents"): docs int64 [n, T], row r = the document of owner
+    ``ids[r]`` of ``pool`` (the device tuple of ``data._Pool.device``) without the reviews whose bit is set in
+    ``drop[r]`` and with word 0 at the positions ``occ_pos[occ_off[r] : occ_off[r + 1]]``.  One launch."""
+    tok, rev_off, first, owners, ids, drop, occ_off, occ_pos, n = _variant_args(pool, ids, drop, occ_off, occ_pos)
+    docs = torch.empty((n, int(T)), dtype=torch.int64, device=ids.device)
+    call('r4r_tower_build_variants', ptr(tok), ptr(rev_off), ptr(first), owners, ptr(ids), ptr(drop), ptr(occ_off),
+         ptr(occ_pos), n, int(T), ptr(docs))
+    return docs
+
+
+def tower_span_variants(pool, ids, T, table, conv_w, conv_b, fc_w, fc_b, group, drop=None, occ_off=None, occ_pos=None,
+                        want=('latent',)):
+    """r4r_tower_span_variants: the tower over the variant documents of ``tower_build_variants``, ``group`` rows per
+    round, every launch enqueued from C -> latent [n, L], or with ``want`` naming 'pooled' / 'argmax' as well a dict
+    name -> tensor (pooled fp32 [n, F], argmax int32 [n, F]: the rounds' own)."""
+    tok, rev_off, first, owners, ids, drop, occ_off, occ_pos, n = _variant_args(pool, ids, drop, occ_off, occ_pos)
+    want = tuple(want)
+    if 'latent' not in want or set(want) - {'latent', 'pooled', 'argmax'}:
+        raise RuntimeError("reviews4rec_amd.ops: tower_span_variants want names 'latent' and any of 'pooled', 'argmax', "
+                           'got %r' % (want,))
+    table, conv_w, conv_b = _f32(table, 'table'), _f32(conv_w, 'conv_w'), _f32(conv_b, 'conv_b')
+    fc_w, fc_b = _f32(fc_w, 'fc_w'), _f32(fc_b, 'fc_b')
+    if table.shape[1] % 4:                                      # (textcnn_fwd_raw's padding)
+        E0 = table.shape[1]
+        table = _padded_table(table)
+        pw = torch.zeros(tuple(conv_w.shape[:-1]) + (table.shape[1],), dtype=conv_w.dtype, device=conv_w.device)
+        pw[..., :E0].copy_(conv_w)
+        conv_w = pw
+    V, E = (int(d) for d in table.shape)
+    F, L, T, group = int(conv_b.numel()), int(fc_w.shape[0]), int(T), int(group)
+    dev = ids.device
+    out = {'latent': torch.empty((n, L), dtype=torch.float32, device=dev)}
+    if 'pooled' in want:
+        out['pooled'] = torch.empty((n, F), dtype=torch.float32, device=dev)
+    if 'argmax' in want:
+        out['argmax'] = torch.empty((n, F), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.lib().r4r_tower_span_variants_ws_bytes(max(1, min(group, n)), T, E, F, L, V), dev)
+    call('r4r_tower_span_variants', ptr(tok), ptr(rev_off), ptr(first), owners, ptr(ids), ptr(drop), ptr(occ_off),
+         ptr(occ_pos), n, group, T, ptr(table), V, ptr(conv_w), ptr(conv_b), ptr(fc_w), ptr(fc_b), E, F, L,
+         ptr(out['latent']), ptr(out.get('pooled')), ptr(out.get('argmax')), ptr(ws), ws.numel(), None)
+    return out['latent'] if want == ('latent',) else out
+
+
 PAIR_GRAD_KINDS = {'fm': 0, 'mlp': 1, 'pfm': 2}              # R4R_PAIR_GRAD_* of include/r4r.h
 PAIR_GRAD_OUTPUTS = ('score', 'g_user', 'g_item', 'w_user', 'w_item')
 _PAIR_GRAD_PARAMS = {'fm': ('V', 'lw'), 'mlp': ('W0', 'b0', 'w3'), 'pfm': ('W0', 'b0', 'W2', 'b2', 'V', 'lw')}

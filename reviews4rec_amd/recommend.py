@@ -900,6 +900,373 @@ class Catalogue:
         return PairPhrases(self.explain_words(u, k=int(k), side='user', weights=w_user),
                            self.explain_words(i, k=int(k), side='item', weights=w_item), scores)
 
+    # ------------------------------------------------------------------ what-if scores: reviews or words REMOVED
+    pair_batch = 8192      # pairs per r4r_pair_grad call of the what-if passes; set after construction
+    whatif_rows = (0, 0)   # the variant rows (user side, item side) the last what-if pass sent through the towers
+
+    def _whatif_slots(self, pool, own):
+        """Of the first 64 reviews of the owners ``own`` -> (has, seen) bool [len(own), 64]: the slot holds a review; and
+        the review shows in the base document (it is not empty and starts before input_length) -- removing one that
+        does not, alone or with others like it, leaves the document as it is."""
+        T = int(self.hp['input_length'])
+        rb, count = pool.first[own], pool.first[own + 1] - pool.first[own]
+        s = np.arange(WHATIF_MAX_SLOTS, dtype=np.int64)[None, :]
+        has = s < count[:, None]
+        at = pool.rev_off[np.where(has, rb[:, None] + s, 0)]
+        return has, has & (pool.rev_off[np.where(has, rb[:, None] + s + 1, 0)] > at) & (at - pool.rev_off[rb][:, None] < T)
+
+    def _loo_rows(self, pool, ids, S):
+        """``_whatif_rows`` for ``leave_one_out``'s masks -- variant s of a pair removes its owner's review s, s < S --
+        from the DISTINCT owners alone, without a pass over the pairs' variants."""
+        own, inv = np.unique(ids, return_inverse=True)
+        nb = len(own)
+        _, seen = self._whatif_slots(pool, own)
+        starts = nb + np.concatenate([[0], np.cumsum(seen.sum(1))[:-1]]).astype(np.int64)
+        row = np.where(seen, starts[:, None] + np.cumsum(seen, 1) - 1, np.arange(nb, dtype=np.int64)[:, None])
+        o, slot = np.nonzero(seen)                              # (row-major: the order of the rows numbered above)
+        row_ids = np.concatenate([own, own[o]])
+        row_drop = np.concatenate([np.zeros(nb, np.int64), (np.uint64(1) << slot.astype(np.uint64)).view(np.int64)])
+        return row_ids, row_drop, None, np.concatenate([inv[:, None], row[inv][:, :S]], 1), nb
+
+    def _whatif_rows(self, pool, ids, masks, occ):
+        """One side's variants as DISTINCT tower rows.  ``ids``: host int64 [n]; ``masks``: int64 [n, V] or None;
+        ``occ``: int64 [n, V, P] (-1 unused) or None -> (row_ids [M], row_drop [M], row_occ [M, P] or None,
+        index [n, V + 1], n_base): rows 0 .. n_base - 1 are the distinct owners with nothing removed, the rest the
+        distinct (owner, mask, positions); ``index[p, 0]`` is pair p's base row and ``index[p, 1 + v]`` variant v's.
+        A mask's bits at or beyond min(count, 64) are cleared; a mask every dropped review of which is empty or starts
+        at or beyond T leaves the document as it is and becomes 0; positions are sorted, repeats dropped.  A variant
+        with nothing left to remove IS its owner's base row."""
+        own, inv = np.unique(ids, return_inverse=True)
+        n, nb = len(ids), len(own)
+        V = masks.shape[1] if masks is not None else (occ.shape[1] if occ is not None else 0)
+        index = np.empty((n, V + 1), np.int64)
+        index[:, 0] = inv
+        if V == 0 or n == 0:
+            return own, np.zeros(nb, np.int64), None, index, nb
+        s = np.arange(WHATIF_MAX_SLOTS, dtype=np.int64)[None, :]
+        has, seen = self._whatif_slots(pool, own)
+        pack = lambda b: (b.astype(np.uint64) << s.astype(np.uint64)).sum(1, dtype=np.uint64).view(np.int64)
+        m = np.zeros((n, V), np.int64) if masks is None else masks & pack(has)[inv][:, None]
+        m = np.where((m & pack(seen)[inv][:, None]) != 0, m, 0)
+        P = occ.shape[2] if occ is not None else 0
+        key = np.empty((n * V, 2 + P), np.int64)
+        key[:, 0], key[:, 1] = np.repeat(inv, V), m.reshape(-1)
+        if P:
+            o = np.sort(occ.reshape(n * V, P), axis=1)
+            o[:, 1:][o[:, 1:] == o[:, :-1]] = -1                                 # repeats
+            key[:, 2:] = -np.sort(-o, axis=1)                                    # descending: the -1 fill at the tail
+        plain = (key[:, 1:] == np.array([0] + [-1] * P)).all(1)
+        rows, where = (np.unique(key[~plain], axis=0, return_inverse=True) if not plain.all() else
+                       (np.zeros((0, 2 + P), np.int64), np.zeros(0, np.int64)))
+        flat = np.empty(n * V, np.int64)
+        flat[plain], flat[~plain] = key[plain, 0], nb + where.reshape(-1)
+        index[:, 1:] = flat.reshape(n, V)
+        row_ids = np.concatenate([own, own[rows[:, 0]]])
+        row_drop = np.concatenate([np.zeros(nb, np.int64), rows[:, 1]])
+        row_occ = np.concatenate([np.full((nb, P), -1, np.int64), rows[:, 2:]]) if P else None
+        return row_ids, row_drop, row_occ, index, nb
+
+    def _whatif_latents(self, tower, pool, row_ids, row_drop, row_occ):
+        """The tower over variant rows -> latent [M, L], ``tower_batch`` rows per round: numpy documents
+        (``data._np_docs_masked``) and ``_tower`` per chunk ('host'), or ONE r4r_tower_span_variants call ('device') --
+        the same bits."""
+        T = int(self.hp['input_length'])
+        conv, M = tower.convs[0], len(row_ids)
+        if self.towers != 'device' or M == 0:
+            from .data import _np_docs_masked
+            z = torch.empty((M, int(tower.fc.weight.shape[0])), dtype=torch.float32, device=self.dev)
+            for sl, chunk in self._batches(row_ids):
+                docs = _np_docs_masked(pool.tok, pool.rev_off, pool.first[chunk], pool.first[chunk + 1], row_drop[sl],
+                                       None if row_occ is None else row_occ[sl], T)
+                z[sl] = self._tower(tower, torch.from_numpy(docs).to(self.dev))
+            return z
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        occ_off = occ_pos = None
+        if row_occ is not None:
+            used = row_occ >= 0
+            off = np.zeros(M + 1, np.int64)
+            np.cumsum(used.sum(1), out=off[1:])
+            occ_off, occ_pos = dev(off), dev(row_occ[used].astype(np.int32))
+        return ops.tower_span_variants(pool.device(self.dev), dev(row_ids), T, self._words().detach(), conv.weight.detach(),
+                                       conv.bias.detach(), tower.fc.weight.detach(), tower.fc.bias.detach(),
+                                       max(1, self.tower_batch), drop=dev(row_drop), occ_off=occ_off, occ_pos=occ_pos)
+
+    def _whatif_request(self, users, items):
+        """The checks every what-if call starts with -> (u, i) as host int64 arrays."""
+        why = phrase_limits(self.hp)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        u, i = self._pair_request(users, items)
+        return u.numpy(), i.numpy()
+
+    def _what_if(self, u, i, mask_u, mask_i, occ_u, occ_i):
+        """``what_if`` of checked host arrays -> (scores [n, V], base [n], same [n, V]): ``same`` marks the variants
+        that ARE the base on both sides; their scores are the base's bits."""
+        (pool_u, tower_u, _), (pool_i, tower_i, _) = self._phrase_side('user'), self._phrase_side('item')
+        n = len(u)
+        V = next((int(t.shape[1]) for t in (mask_u, mask_i, occ_u, occ_i) if t is not None), 1)
+        if n == 0:
+            e = lambda *s, dt=torch.float32: torch.empty(s, dtype=dt, device=self.dev)
+            return e(0, V), e(0), e(0, V, dt=torch.bool)
+        self._flush()
+        fill = lambda m, o: (np.zeros((n, V), np.int64), None) if m is None and o is None else (m, o)
+        return self._whatif_scores(self._whatif_rows(pool_u, u, *fill(mask_u, occ_u)),
+                                   self._whatif_rows(pool_i, i, *fill(mask_i, occ_i)))
+
+    def _whatif_scores(self, rows_u, rows_i):
+        """The towers over both sides' distinct rows (``_whatif_rows``' tuples), then the pairs' variants through
+        r4r_pair_grad, ``pair_batch`` pairs per call -> (scores [n, V], base [n], same [n, V])."""
+        (pool_u, tower_u, _), (pool_i, tower_i, _) = self._phrase_side('user'), self._phrase_side('item')
+        (ru, du, ou, xu, bu), (ri, di, oi, xi, bi) = rows_u, rows_i
+        n, V = xu.shape[0], xu.shape[1] - 1
+        self.whatif_rows = (len(ru) - bu, len(ri) - bi)          # the variant rows the last pass ran, per side
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        with torch.no_grad():
+            zu = self._whatif_latents(tower_u, pool_u, ru, du, ou)
+            zi = self._whatif_latents(tower_i, pool_i, ri, di, oi)
+            head = self._pair_head(dev(ru), dev(ri))
+            out = torch.empty((n, V + 1), dtype=torch.float32, device=self.dev)
+            same = torch.empty((n, V), dtype=torch.bool, device=self.dev)
+            step = max(1, int(self.pair_batch))
+            for s0 in range(0, n, step):
+                sl = slice(s0, s0 + step)
+                out[sl] = ops.pair_grad(self._pair_kind, zu, zi, dev(xu[sl]).reshape(-1), dev(xi[sl]).reshape(-1),
+                                        want=('score',), **head)['score'].view(-1, V + 1)
+                same[sl] = dev((xu[sl, 1:] < bu) & (xi[sl, 1:] < bi))
+            base = out[:, 0].contiguous()
+            return torch.where(same, base[:, None], out[:, 1:]).contiguous(), base, same
+
+    def what_if(self, users, items, drop_user=None, drop_item=None, occlude_user=None, occlude_item=None):
+        """What would the model predict for (users[p], items[p]) if chosen reviews, or chosen words, were not there?
+        -> ``WhatIf(scores [n, V], base [n])`` of device tensors: ``scores[p, v]`` is the eval-mode prediction with
+        variant v's removals applied to the user's and / or the item's document, ``base[p]`` the prediction with
+        nothing removed.
+
+        ``drop_user`` / ``drop_item``: None; or, per pair, a list of review indices in the owner's pool order -- the
+        loader's ``skip`` (data.py:223-235), generalised to a set: the remaining reviews are concatenated and cut /
+        padded to input_length, so later words slide in across the cut -- as one variant, or a list of such lists as V
+        variants; or an int64 mask tensor [n, V], bit s = the owner's review s removed (bits beyond the owner's list are
+        ignored).  Only an owner's first 64 reviews can be removed.  ``occlude_user`` / ``occlude_item``: None; an int
+        tensor [n, V, P] of document positions, -1 unused; or per pair a list of positions (one variant) or a list of
+        such lists.  An occluded position holds word 0, the padding the model knows, with no shift; positions refer to
+        the variant's OWN document, i.e. after its removals.  All four combine; every one given has the same V.
+
+        A variant is a document: the DISTINCT (owner, mask, positions) go through the side's tower once,
+        ``tower_batch`` rows per round -- numpy documents per chunk ('host') or ONE r4r_tower_span_variants call
+        ('device'; include/r4r.h, "What-if documents"): the same bits -- and the variants' latents stand in for their
+        owners' in ONE r4r_pair_grad pass, ``pair_batch`` pairs at a time, over the class's own head.  Before the
+        engine is flushed or anything is enqueued: a configuration without a tower is refused with the reason; unequal
+        lengths, unequal V, a malformed argument, a review index outside the owner's list or at or beyond 64 and a
+        position outside [0, input_length) raise ValueError, an id outside its side's pool KeyError."""
+        u, i = self._whatif_request(users, items)
+        T = int(self.hp['input_length'])
+        args = []
+        for ids, side, drop, occ in ((u, 'user', drop_user, occlude_user), (i, 'item', drop_item, occlude_item)):
+            pool = self._phrase_side(side)[0]
+            args += [_drop_masks(drop, pool.first[ids + 1] - pool.first[ids], 'drop_' + side),
+                     _occlusions(occ, len(ids), T, 'occlude_' + side)]
+        vs = sorted({int(a.shape[1]) for a in args if a is not None})
+        if len(vs) > 1:
+            raise ValueError('catalogue: what_if arguments hold %s variants per pair; every one needs as many' % vs)
+        scores, base, _ = self._what_if(u, i, args[0], args[2], args[1], args[3])
+        return WhatIf(scores, base)
+
+    def leave_one_out(self, users, items):
+        """Each review of each pair's two documents removed in turn -> ``DocLeaveOneOut`` of device tensors:
+
+            base                          float32 [n]      the prediction with nothing removed
+            without_user, without_item    float32 [n, S]   the prediction without the owner's s-th review (the loader's
+                                                           ``skip`` = s); S = the side's largest ``live``
+            delta_user, delta_item        float32 [n, S]   base - without: what review s adds to THIS pair's score
+            live_user, live_item          int64 [n]        min(number of reviews, 64): the slots that hold a review
+            reach_user, reach_item        int64 [n]        the reviews that start before position input_length of the
+                                                           base document (a later one cannot show in it)
+
+        A slot at or beyond ``live`` holds ``base`` and a delta of exactly 0; so does every slot whose review is empty
+        or starts at or beyond input_length: its document IS the base document, and it is not run.  Variant rows depend
+        on the owner alone: every distinct (owner, review) goes through the tower once.  One ``what_if`` pass; its
+        checks and refusals."""
+        u, i = self._whatif_request(users, items)
+        n, T = len(u), int(self.hp['input_length'])
+        sides = []
+        for ids, side in ((u, 'user'), (i, 'item')):
+            pool = self._phrase_side(side)[0]
+            rb, count = pool.first[ids], pool.first[ids + 1] - pool.first[ids]
+            live = np.minimum(count, WHATIF_MAX_SLOTS)
+            cut = pool.rev_off[rb] + T                          # reviews starting before it: a prefix of the owner's list
+            reach = np.searchsorted(pool.rev_off[:-1], cut, side='left') - rb if len(pool.rev_off) > 1 else np.zeros(n, np.int64)
+            sides.append((live, np.clip(reach, 0, count), int(live.max()) if n else 0))
+        (live_u, reach_u, S_u), (live_i, reach_i, S_i) = sides
+        if n and S_u + S_i:
+            self._flush()
+            ru, du, _, xu, bu = self._loo_rows(self._phrase_side('user')[0], u, S_u)
+            ri, di, _, xi, bi = self._loo_rows(self._phrase_side('item')[0], i, S_i)
+            xu = np.concatenate([xu, np.repeat(xu[:, :1], S_i, 1)], 1)           # variants: the user's slots, then the item's
+            xi = np.concatenate([xi[:, :1], np.repeat(xi[:, :1], S_u, 1), xi[:, 1:]], 1)
+            scores, base, _ = self._whatif_scores((ru, du, None, xu, bu), (ri, di, None, xi, bi))
+        else:
+            scores, base, _ = self._what_if(u, i, None, None, None, None)
+            scores = scores[:, :0]
+        held = lambda S: base[:, None].expand(n, S)
+        wu, wi = scores[:, :S_u].contiguous(), scores[:, S_u:].contiguous()
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)
+        return DocLeaveOneOut(base, wu, wi, held(S_u) - wu, held(S_i) - wi, dev(live_u), dev(live_i), dev(reach_u),
+                              dev(reach_i))
+
+    def deletion_curve(self, users, items, k=5, by='pair', side='user', direction='up'):
+        """The ``k`` heaviest word windows of one side's document occluded CUMULATIVELY -> ``DocDeletionCurve`` of
+        device tensors:
+
+            scores     float32 [n, k + 1]  column 0 the prediction with nothing removed, column j the prediction with
+                                           the first j windows of ``positions`` occluded; beyond ``live`` the last
+                                           live column repeats
+            aopc       float32 [n]         the mean over j = 1 .. live of scores[:, 0] - scores[:, j] (0 without a
+                                           window): the area over the perturbation curve -- large when the windows
+                                           named carry the score
+            positions  int32 [n, k]        the windows' conv positions p in occlusion order, -1 unused: window p covers
+                                           the document positions p - 2 .. p inside [0, input_length)
+            live       int64 [n]           the number of windows the list really has
+
+        ``by``: 'pair' -- ``explain_pair``'s windows of the side (this pair's gradient weights; ``direction`` as
+        there); 'mass' -- ``explain_words`` without weights, the owner's heaviest windows whatever the pair; or an int
+        tensor [n, k] of conv positions of your own in [0, input_length + 2), -1 (unused) only after the used ones.
+        ``side``: 'user' or 'item'; the other side's document stays whole.  Refused before anything is enqueued: a bad
+        ``by`` / ``side`` / ``direction`` / ``k`` (ValueError), unequal lengths (ValueError), an id outside its side's
+        pool (KeyError), a configuration without a tower with the reason."""
+        why = phrase_limits(self.hp)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        if side not in ('item', 'user'):
+            raise ValueError("catalogue: side must be 'item' or 'user', got %r" % (side,))
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        T = int(self.hp['input_length'])
+        F = int(self._phrase_side(side)[1].convs[0].bias.numel())
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= F:
+            raise ValueError('catalogue: deletion_curve k = %r outside 1 .. %d' % (k, F))
+        k = int(k)
+        named = isinstance(by, str)
+        if named and by not in ('pair', 'mass'):
+            raise ValueError("catalogue: by must be 'pair', 'mass' or an int tensor [n, %d] of positions, got %r" % (k, by))
+        u, i = self._whatif_request(users, items)
+        n = len(u)
+        if not named:
+            pos = torch.as_tensor(by) if torch.is_tensor(by) or isinstance(by, (np.ndarray, list, tuple)) else None
+            if pos is None or pos.dtype not in (torch.int32, torch.int64) or tuple(pos.shape) != (n, k):
+                raise ValueError("catalogue: by must be 'pair', 'mass' or an int tensor [%d, %d] of positions, got %r"
+                                 % (n, k, getattr(by, 'shape', by)))
+            pos = pos.detach().cpu().to(torch.int64).numpy()
+            used = pos >= 0
+            if ((pos < -1) | (pos >= T + 2)).any() or (used[:, 1:] & ~used[:, :-1]).any():
+                raise ValueError('catalogue: by as positions lies in [0, %d), with -1 (unused) only after the used ones'
+                                 % (T + 2))
+        elif n == 0:
+            pos = np.zeros((0, k), np.int64)
+        elif by == 'pair':
+            pos = getattr(self.explain_pair(u, i, k=k, direction=direction), side).positions.cpu().numpy().astype(np.int64)
+        else:
+            pos = self.explain_words(u if side == 'user' else i, k=k, side=side).positions.cpu().numpy().astype(np.int64)
+        used = pos >= 0
+        live = used.sum(1)
+        win = pos[:, :, None] - 2 + np.arange(3)[None, None, :]                   # [n, k, 3]: the words of window p
+        win = np.where(used[:, :, None] & (win >= 0) & (win < T), win, -1).reshape(n, 1, 3 * k)
+        upto = np.repeat(np.arange(k), 3)[None, None, :] <= np.arange(k)[None, :, None]
+        occ = np.where(upto, win, -1)                                             # [n, k, 3 k]: variant j = windows 0 .. j
+        ou, oi = (occ, None) if side == 'user' else (None, occ)
+        scores, base, _ = self._what_if(u, i, None, None, ou, oi)
+        live_d = torch.from_numpy(live).to(self.dev)
+        col = torch.arange(k, device=self.dev)[None, :]
+        last = torch.cat([base[:, None], scores], 1).gather(1, live_d[:, None])   # the last live column (the base: none)
+        scores = torch.where(col < live_d[:, None], scores, last.expand(n, k))
+        gain = (base[:, None].double() - scores.double()) * (col < live_d[:, None])
+        aopc = (gain.sum(1) / live_d.clamp(min=1)).to(torch.float32)
+        return DocDeletionCurve(torch.cat([base[:, None], scores], 1).contiguous(), aopc,
+                                torch.from_numpy(pos.astype(np.int32)).to(self.dev), live_d)
+
+
+def _drop_masks(drop, count, what):
+    """A ``drop`` argument of ``Catalogue.what_if`` -> int64 numpy masks [n, V] or None, checked against the owners'
+    review counts ``count`` [n]."""
+    n = len(count)
+    if drop is None:
+        return None
+    if torch.is_tensor(drop) or isinstance(drop, np.ndarray):
+        m = torch.as_tensor(drop)
+        if m.dtype != torch.int64 or m.dim() != 2 or m.shape[0] != n or m.shape[1] < 1:
+            raise ValueError('catalogue: %s as masks must be int64 [%d, V] with V >= 1, got %s %s'
+                             % (what, n, m.dtype, tuple(m.shape)))
+        return m.detach().cpu().contiguous().numpy()
+    if not isinstance(drop, (list, tuple)) or len(drop) != n:
+        raise ValueError('catalogue: %s must be None, int64 masks [n, V] or one list of review indices per pair (%d pairs)'
+                         % (what, n))
+    is_index = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    rows = []
+    for p, entry in enumerate(drop):
+        if not isinstance(entry, (list, tuple, np.ndarray)):
+            raise ValueError('catalogue: %s[%d] must be a list of review indices (or a list of such lists)' % (what, p))
+        entry = list(entry)
+        variants = [entry] if all(is_index(v) for v in entry) else [list(v) if isinstance(v, (list, tuple, np.ndarray))
+                                                                    else [v] for v in entry]
+        row = []
+        for variant in variants:
+            mask = 0
+            for v in variant:
+                if not is_index(v) or not 0 <= int(v) < int(count[p]) or int(v) >= WHATIF_MAX_SLOTS:
+                    raise ValueError('catalogue: %s[%d] names review %r outside the owner\'s list of %d (the first %d '
+                                     'can be removed)' % (what, p, v, int(count[p]), WHATIF_MAX_SLOTS))
+                mask |= 1 << int(v)
+            row.append(mask - (1 << 64) if mask >= (1 << 63) else mask)
+        rows.append(row)
+    if n and any(len(row) != len(rows[0]) for row in rows):
+        raise ValueError('catalogue: %s holds %s variants per pair; every pair needs as many'
+                         % (what, sorted({len(row) for row in rows})))
+    V = len(rows[0]) if n else 1
+    if V < 1:
+        raise ValueError('catalogue: %s holds no variant' % what)
+    return np.array(rows, dtype=np.int64).reshape(n, V)
+
+
+def _occlusions(occ, n, T, what):
+    """An ``occlude`` argument of ``Catalogue.what_if`` -> int64 numpy [n, V, P] (-1 unused) or None; every position
+    is -1 or inside [0, T)."""
+    if occ is None:
+        return None
+    if torch.is_tensor(occ) or isinstance(occ, np.ndarray):
+        a = torch.as_tensor(occ)
+        if a.dtype not in (torch.int32, torch.int64) or a.dim() != 3 or a.shape[0] != n or a.shape[1] < 1:
+            raise ValueError('catalogue: %s as a tensor must be int32 / int64 [%d, V, P] with V >= 1, got %s %s'
+                             % (what, n, a.dtype, tuple(a.shape)))
+        a = a.detach().cpu().to(torch.int64).contiguous().numpy()
+    else:
+        if not isinstance(occ, (list, tuple)) or len(occ) != n:
+            raise ValueError('catalogue: %s must be None, an int tensor [n, V, P] or one list of positions per pair (%d '
+                             'pairs)' % (what, n))
+        is_index = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        rows = []
+        for p, entry in enumerate(occ):
+            if not isinstance(entry, (list, tuple, np.ndarray)):
+                raise ValueError('catalogue: %s[%d] must be a list of positions (or a list of such lists)' % (what, p))
+            entry = list(entry)
+            variants = [entry] if all(is_index(v) for v in entry) else [list(v) if isinstance(v, (list, tuple, np.ndarray))
+                                                                        else [v] for v in entry]
+            if any(not is_index(v) for variant in variants for v in variant):
+                raise ValueError('catalogue: %s[%d] holds something that is not a position' % (what, p))
+            rows.append(variants)
+        if n and any(len(row) != len(rows[0]) for row in rows):
+            raise ValueError('catalogue: %s holds %s variants per pair; every pair needs as many'
+                             % (what, sorted({len(row) for row in rows})))
+        V = len(rows[0]) if n else 1
+        if V < 1:
+            raise ValueError('catalogue: %s holds no variant' % what)
+        P = max([len(variant) for row in rows for variant in row] + [1])
+        a = np.full((n, V, P), -1, np.int64)
+        for p, row in enumerate(rows):
+            for v, variant in enumerate(row):
+                a[p, v, :len(variant)] = variant
+    if ((a < -1) | (a >= T)).any():
+        raise ValueError('catalogue: %s names a position outside [0, input_length = %d) (-1: unused)' % (what, T))
+    return a
+
 
 PairPhrases = namedtuple('PairPhrases', 'user item scores')      # Catalogue.explain_pair: two ``Phrases`` and [n] scores
 PairReviews = namedtuple('PairReviews', 'w_user w_item rev_user rev_item glogit_user glogit_item attention_user '
@@ -907,7 +1274,9 @@ PairReviews = namedtuple('PairReviews', 'w_user w_item rev_user rev_item glogit_
 WhatIf = namedtuple('WhatIf', 'scores base')                                    # NarreCatalogue.what_if
 LeaveOneOut = namedtuple('LeaveOneOut', 'base without_user without_item delta_user delta_item live_user live_item')
 DeletionCurve = namedtuple('DeletionCurve', 'scores aopc order live')           # NarreCatalogue.deletion_curve
-WHATIF_MAX_SLOTS = 64               # r4r_narre_whatif: S <= 64, one bit of an int64 mask per slot
+DocLeaveOneOut = namedtuple('DocLeaveOneOut', LeaveOneOut._fields + ('reach_user', 'reach_item'))   # Catalogue.leave_one_out
+DocDeletionCurve = namedtuple('DocDeletionCurve', 'scores aopc positions live')                    # Catalogue.deletion_curve
+WHATIF_MAX_SLOTS = 64               # r4r_narre_whatif, r4r_tower_build_variants: one bit of an int64 mask per slot
 PHRASE_FILTERS = 100                # every TextCNN tower's filter count (common_pytorch_models.py:11)
 _PHRASE_TYPES = ('deepconn', 'deepconn++', 'transnet', 'transnet++', 'NARRE')
 Phrases = namedtuple('Phrases', 'positions scores filters tokens reviews offsets windows slots weights',
@@ -2246,4 +2615,64 @@ def write_pair_phrases(path, model, hyper_params, train_reader, k, engine=None):
         np.savez(f, users=np.tile(users, 2), items=np.tile(items, 2), side=np.repeat(np.array([0, 1], np.int8), n),
                  pair_scores=np.tile(e.scores.cpu().numpy(), 2), positions=both('positions'), scores=both('scores'),
                  filters=both('filters'), tokens=both('tokens'), reviews=both('reviews'), offsets=both('offsets'))
+    return path
+
+
+def check_explain_reviews_request(hyper_params):
+    """main's hook asked for (hyper_params['explain_reviews_k'])?  Then refuse, BEFORE any training, a model type the
+    hooks' classes cannot explain (``phrase_limits``' reason, else ``hook_limits``': deepconn and deepconn++), a k that
+    is no int in 1 .. 64 (the reviews of an owner that can be removed), a request without a file to write, one without
+    ``recommend_k`` (the pairs explained are the recommended ones) and an unknown ``catalogue_towers``."""
+    if not hyper_params.get('explain_reviews_k'):
+        return
+    why_not = phrase_limits(hyper_params) or hook_limits(hyper_params)
+    if why_not is None and hyper_params['model_type'] not in ('deepconn', 'deepconn++'):
+        why_not = ('model_type %r: the hook removes reviews from the single-document families deepconn and deepconn++ '
+                   '(NARRE: NarreCatalogue.leave_one_out)' % (hyper_params['model_type'],))
+    if why_not is not None:
+        raise RuntimeError("hyper_params['explain_reviews_k']: " + why_not)
+    k = hyper_params['explain_reviews_k']
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= WHATIF_MAX_SLOTS:
+        raise RuntimeError("hyper_params['explain_reviews_k'] must be an int in 1 .. %d, got %r" % (WHATIF_MAX_SLOTS, k))
+    if not hyper_params.get('explain_reviews_path'):
+        raise RuntimeError("hyper_params['explain_reviews_k'] needs hyper_params['explain_reviews_path'] (the .npz to "
+                           "write)")
+    if not hyper_params.get('recommend_k'):
+        raise RuntimeError("hyper_params['explain_reviews_k'] needs hyper_params['recommend_k']: the pairs it explains "
+                           "are every user's recommended items")
+    _check_towers_request(hyper_params)
+
+
+def top_removed_reviews(loo, k):
+    """Per pair and side of a ``DocLeaveOneOut`` the ``k`` reviews whose removal LOWERS the prediction most (the largest
+    delta first, ties to the earlier review; only slots that hold a review) -> (reviews int64 [2, n, k] with -1 unused,
+    deltas float32 [2, n, k] with 0 there) as host arrays, side 0 the user's."""
+    out_r, out_d = [], []
+    for delta, live in ((loo.delta_user, loo.live_user), (loo.delta_item, loo.live_item)):
+        n, S = delta.shape
+        pad = max(0, k - S)
+        d = torch.cat([delta, delta.new_zeros((n, pad))], 1)
+        valid = torch.arange(S + pad, device=delta.device)[None, :] < live[:, None]
+        order = torch.sort(torch.where(valid, d, torch.full_like(d, float('-inf'))), dim=1, descending=True,
+                           stable=True).indices[:, :k]
+        ok = valid.gather(1, order)
+        out_r.append(torch.where(ok, order, torch.full_like(order, -1)).cpu().numpy())
+        out_d.append(torch.where(ok, d.gather(1, order), torch.zeros_like(d[:, :k])).cpu().numpy())
+    return np.stack(out_r), np.stack(out_d)
+
+
+def write_pair_reviews(path, model, hyper_params, train_reader, k, engine=None):
+    """main.main's hook: ``leave_one_out`` of every training user's ``recommend_k`` list -> an .npz whose rows are the n
+    pairs' user sides followed by the n pairs' item sides: users / items (the row's pair), side (0: the user's reviews,
+    1: the item's), pair_scores (the pair's prediction), reviews (the k reviews whose removal lowers the prediction
+    most, as indices into the side's pool order of the owner; -1 unused) and deltas (base - without of each)."""
+    cat = make_catalogue(model, hyper_params, train_reader, engine=engine)
+    users, items = recommended_pairs(cat, hyper_params['recommend_k'])
+    loo = cat.leave_one_out(users, items)
+    reviews, deltas = top_removed_reviews(loo, int(k))
+    n = len(users)
+    with open(path, 'wb') as f:                              # (a file object: numpy appends no suffix to the name)
+        np.savez(f, users=np.tile(users, 2), items=np.tile(items, 2), side=np.repeat(np.array([0, 1], np.int8), n),
+                 pair_scores=np.tile(loo.base.cpu().numpy(), 2), reviews=reviews.reshape(2 * n, -1),
+                 deltas=deltas.reshape(2 * n, -1))
     return path
