@@ -266,8 +266,41 @@ def deepconn_cases():
                               ('deepconn-L128', 0.3)])
 
 
+def deepconn_batch_cases():
+    """r4r_deepconn_step along its batch axis: the split count (min(16, ceil(B / 16)) splits of ceil(B / nsplit)
+    documents), the tail (four launches while B <= 256, per_split <= 16, nsplit E / 4 <= 1,024 and L <= 64; else five),
+    the rounds of a split in the five-launch tail, and head_grad_block's passes of 128 ratings."""
+    V, U, I = 300, 40, 30
+    out = []
+    #        B    T    E   L
+    for B, T, E, L in [
+            (1, 40, 32, 16),         # one document; 15 of head_grad_block's 16 row groups have no rating
+            (16, 40, 32, 16),        # one full split
+            (17, 40, 32, 16),        # two splits of 9 and 8
+            (128, 40, 32, 16),       # eight splits of 16, head_grad_block's one full pass
+            (129, 40, 32, 16),       # nine splits of 15 + 9, a second pass with one live row
+            (241, 40, 32, 16),       # sixteen splits, the last holds one document
+            (255, 40, 32, 16),       # ragged last split
+            (256, 40, 32, 16),       # every LDS row array of wgrad_row_block full: the last folded batch size
+            (257, 40, 32, 16),       # per_split 17: first batch of the five-launch tail by B; rounds of 16 + 1; last split 2
+            (256, 40, 256, 16),      # nsplit E / 4 = 1,024 threads and 256 documents at once: both limits of the fold
+            (256, 40, 260, 16),      # 1,040 threads: five-launch tail at per_split = 16
+            (256, 40, 32, 64),       # widest folded head
+            (256, 40, 32, 65),       # the 65 .. 128 head instantiation keeps the old tail
+            (256, 200, 32, 16),      # documents of two 128-position gather segments under the fold
+            (1000, 40, 32, 16)]:     # per_split 63: rounds 16, 16, 16, 15; last split 55
+        id = 'deepconn-B%d' % B + ''.join('-%s%d' % (k, v) for k, v, d in (('T', T, 40), ('E', E, 32), ('L', L, 16)) if v != d)
+        out.append(Case(id, 'DeepCoNNEngine', _doc_hp('deepconn', L, B, T, E, U, I),
+                        doc_batches(B, T, V, U, I, 500 + B + E), vocab=V, seed=61,
+                        weights=weights_outliers(2e-3, 5e-4 if L <= 32 else 2.5e-3)))
+    return with_dropout(out, [('deepconn-B17', 0.5), ('deepconn-B256', 0.5), ('deepconn-B257', 0.3),
+                              ('deepconn-B256-E256', 0.3),
+                              ('deepconn-B1000', 0.3)])              # (its second step starts at stream position 32,000)
+
+
 def all_cases():
-    return mf_cases() + idnet_cases() + narre_cases() + deepconnpp_cases() + transnet_cases() + deepconn_cases()
+    return (mf_cases() + idnet_cases() + narre_cases() + deepconnpp_cases() + transnet_cases() + deepconn_cases()
+            + deepconn_batch_cases())
 
 
 def stream_keep(case, step):

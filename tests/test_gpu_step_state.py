@@ -14,16 +14,22 @@ instead puts the factor 1 - p on the gradient of every parameter upstream of the
 the weights and the SE and exp_avg shows.  Each twin's device masks equal the Philox stand-in the CPU checker ran on
 (tests/test_step_state_checker.py), element for element, and are injected into the float64 reference.
 
+DeepCoNN's dense gradients are sums over the ratings, dealt to splits, rounds and passes by the batch size: its
+batch-axis cases (deepconn_batch_cases: 1 to 1,000 ratings) hold the step to the same reference on either side of every
+batch size at which that dealing or the tail of the step changes, with the four-launch and the five-launch tail.
+
 Every rating's SE is compared on its own (rtol 1e-4, atol 1e-5), on every case.
 
 No absolute tolerance is widened: every tensor is held to rtol 1e-4, atol 1e-7 (exp_avg_sq: 1e-10)."""
+import os
+
 import pytest
 import torch
 
 from helpers import (StateStandIn, assert_per_rating_se, assert_step_state, float64_step_reference, multipliers,
                      state_distances)
-from step_state_cases import (deepconn_cases, deepconnpp_cases, idnet_cases, mf_cases, narre_cases, stream_keep,
-                              transnet_cases)
+from step_state_cases import (deepconn_batch_cases, deepconn_cases, deepconnpp_cases, idnet_cases, mf_cases, narre_cases,
+                              stream_keep, transnet_cases)
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -84,15 +90,20 @@ def run(case, check):
     return bits
 
 
-def check_case(case):
-    first = run(case, check=True)
-    again = run(case, check=False)
+def same_bits(first, again, between='two runs'):
+    assert len(first) == len(again)
     for step, (a, b) in enumerate(zip(first, again)):
-        assert torch.equal(a[0], b[0]), 'per-example SE of step %d differs between two runs' % (step + 1)
+        assert torch.equal(a[0], b[0]), 'per-example SE of step %d differs between %s' % (step + 1, between)
         for what, x, z in (('weight', a[1], b[1]), ('exp_avg', a[2], b[2]), ('exp_avg_sq', a[3], b[3])):
             assert set(x) == set(z)
             for k in x:
-                assert torch.equal(x[k], z[k]), '%s %s of step %d differs between two runs' % (what, k, step + 1)
+                assert torch.equal(x[k], z[k]), '%s %s of step %d differs between %s' % (what, k, step + 1, between)
+
+
+def check_case(case):
+    first = run(case, check=True)
+    same_bits(first, run(case, check=False))
+    return first
 
 
 @pytest.mark.parametrize('case', mf_cases(), ids=repr)
@@ -139,3 +150,36 @@ def test_deepconn_step_state(case):
     """r4r_deepconn_step at L 16 / 17 / 64 / 65 / 128 (the 65 .. 128 head instantiation keeps the old tail).  Every
     case has a twin that draws at the two towers' outputs."""
     check_case(case)
+
+
+def expect_fold(B, E, L):
+    nsplit = min(16, -(-B // 16))
+    return int(B <= 256 and -(-B // nsplit) <= 16 and nsplit * (E // 4) <= 1024 and L <= 64)
+
+
+@pytest.mark.parametrize('case', deepconn_batch_cases(), ids=repr)
+def test_deepconn_batch_step_state(case):
+    """r4r_deepconn_step along its batch axis, B = 1 .. 1,000: one to sixteen splits, a last split of one document,
+    head_grad_block's passes on either side of 128 ratings, the four-launch tail up to its limits (256 documents,
+    1,024 threads, L = 64) and the five-launch tail just past each of them and at several rounds per split.  Equal
+    numbers cannot tell the tails apart, so the tail the shape resolves to is asked for (r4r_deepconn_tail) and held to
+    the rule worked out here; every shape the four-launch tail takes is run with the five-launch tail too: each is
+    held to float64 on its own, and the two leave the same bits."""
+    from reviews4rec_amd import _lib
+    lib = _lib.lib()
+    hp = case.hp
+    B, E, L = int(hp['batch_size']), int(hp['word_embed_size']), int(hp['latent_size'])
+    folds = lib.r4r_deepconn_tail(B, E, L)
+    if not any(k in os.environ for k in ('R4R_TAIL', 'R4R_WGRAD_DOCS', 'R4R_WGRAD_MAX_SPLITS')):
+        assert folds == expect_fold(B, E, L)
+    print('STEP-STATE %s %s takes the %s-launch tail' % (case.engine, case.id, 'four' if folds else 'five'))
+    first = check_case(case)
+    if not folds:
+        return
+    before = lib.r4r_deepconn_tail_fold(0)
+    try:
+        assert lib.r4r_deepconn_tail(B, E, L) == 0
+        print('STEP-STATE %s %s again, the five-launch tail forced' % (case.engine, case.id))
+        same_bits(first, run(case, check=True), 'the four-launch and the five-launch tail')
+    finally:
+        lib.r4r_deepconn_tail_fold(before)

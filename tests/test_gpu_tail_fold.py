@@ -177,7 +177,15 @@ CASES = [(1, 8, 200, 10, 1, 1, PROJECT),          # one split, one document, two
          (128, 8, 200, 10, 0, 0, PROJECT),         # sixteen threads of row work in 256; gradients only, no next batch
          (17, 512, 200, 10, 0, 1, PROJECT),
          (5, 52, 30, 10, 1, 1, DIRECT),            # the direct conv: no token state, the same tail
-         (5, 52, 200, 80, 1, 1, PROJECT)]          # latent_size 65 .. 128 keeps the old tail
+         (5, 52, 200, 80, 1, 1, PROJECT),          # latent_size 65 .. 128 keeps the old tail
+         (129, 52, 200, 10, 1, 1, PROJECT),        # nine splits of 15 + 9
+         (241, 64, 200, 10, 1, 1, PROJECT),        # sixteen splits, a last split of one document
+         (255, 52, 30, 10, 1, 1, PROJECT),
+         (256, 256, 30, 10, 1, 1, PROJECT),        # 1,024 threads, 256 documents: both limits at once
+         (256, 260, 30, 10, 1, 1, PROJECT),        # over: the query says old tail, the step still matches
+         (257, 32, 30, 10, 1, 1, PROJECT),         # over by B
+         (256, 64, 200, 64, 0, 0, PROJECT),        # the widest folded head; gradients only, no next batch
+         (256, 52, 30, 10, 1, 1, DIRECT)]
 
 
 @pytest.mark.parametrize('shape', CASES, ids=lambda s: 'B%d-E%d-T%d-L%d-adam%d-next%d-conv%d' % s)

@@ -305,6 +305,69 @@ def test_the_weights_only_criteria_pass_the_first_two_mistakes(case, mistake):
         assert weights_failures(s32.params, s64.params, old) == []
 
 
+# ------------------------------------------------------------------------------------------------ dense sums over B
+def one_rating_s_gradient(case, data, y, masks, params, n):
+    """The gradients of rating n's term of the loss, (pred_n - y_n)^2 / B, by the float32 oracle's autograd on that
+    rating alone."""
+    leaves = {k: params[k].detach().clone().requires_grad_(True) for k in oracle.trainable_names(params)}
+    full = dict(params)
+    full.update(leaves)
+    one = [d if d is None else d[n:n + 1] for d in data]
+    if masks is not None:
+        masks = {site: m[n:n + 1] for site, m in masks.items()}
+    out = oracle.model_forward(full, one, case.hp, train=True, masks=masks)
+    (oracle.mse_loss(out, y[n:n + 1].to(out.dtype), return_mean=False).sum() / y.numel()).backward()
+    return {k: t.grad for k, t in leaves.items()}
+
+
+def one_rating_missing_from_a_dense_sum(case, name, n):
+    def mistake(step, data, y, masks, grads, params):
+        grads[name] = grads[name] - one_rating_s_gradient(case, data, y, masks, params, n)[name]
+    return mistake
+
+
+def one_rating_counted_twice(case, name, n):
+    def mistake(step, data, y, masks, grads, params):
+        grads[name] = grads[name] + one_rating_s_gradient(case, data, y, masks, params, n)[name]
+    return mistake
+
+
+def split_boundaries(B):
+    """The last rating of split 0, the first of the last split and rating B - 1 (min(16, ceil(B / 16)) splits of
+    ceil(B / nsplit) documents: csrc/textcnn.hip, textcnn_wgrad_splits)."""
+    nsplit = min(16, -(-B // 16))
+    per = -(-B // nsplit)
+    return sorted({min(per, B) - 1, (nsplit - 1) * per, B - 1})
+
+
+assert split_boundaries(17) == [8, 9, 16] and split_boundaries(241) == [15, 240]
+assert split_boundaries(256) == [15, 240, 255] and split_boundaries(257) == [16, 255, 256]
+assert split_boundaries(1000) == [62, 945, 999]
+
+# two splits; a last split of one document; the last folded batch size; the first unfolded one, and with dropout on;
+# several rounds per split
+DENSE_SEEDED = ['deepconn-B17', 'deepconn-B241', 'deepconn-B256', 'deepconn-B257', 'deepconn-B257-p0.3', 'deepconn-B1000']
+DENSE_TENSORS = ['user_conv.convs.0.weight', 'item_conv.convs.0.bias', 'user_conv.fc.weight', 'fm.V']
+EVERY_BOUNDARY = [(id, n) for id in DENSE_SEEDED for n in split_boundaries(int(BY_ID[id].hp['batch_size']))]
+
+
+@pytest.mark.parametrize('mistake', [one_rating_missing_from_a_dense_sum, one_rating_counted_twice],
+                         ids=lambda f: f.__name__)
+@pytest.mark.parametrize('name', DENSE_TENSORS)
+@pytest.mark.parametrize('case,n', EVERY_BOUNDARY)
+def test_one_rating_lost_or_doubled_in_a_dense_sum_raises(case, n, name, mistake):
+    """DeepCoNN's dense gradients are sums over the B ratings, dealt to splits and rounds by B: with the term of ONE
+    rating at a split boundary left out of (or added twice to) one tensor's gradient, the moments alone raise on both
+    steps -- at B = 1,000 as at B = 17."""
+    case = BY_ID[case]
+    steps = run(case, mistake(case, name, n))
+    clean = run(case)
+    assert not torch.equal(steps[0][0].grads[name], clean[0][0].grads[name])
+    for s32, s64 in steps:
+        with pytest.raises(AssertionError, match='exp_avg(_sq)? ' + name.replace('.', r'\.')):
+            assert_step_state(StateStandIn(s32, with_grads=False), StateStandIn(s32), s64, what=case.id)
+
+
 def test_a_widened_atol_is_eight_oracle_distances_and_holds_for_its_tensor_alone():
     """The rule for a kernel whose summation order needs more than atol 1e-7 on one tensor: 8 x the float32 oracle's own
     largest distance from float64 on it, for that tensor and that quantity only."""
