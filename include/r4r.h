@@ -1794,6 +1794,61 @@ int r4r_narre_whatif(const float *z_u, const float *logit_u, const float *own_u,
                      void *stream);
 
 /* ------------------------------------------------------------------------
+ * NARRE counterfactual search: the fewest reviews whose removal moves a pair's eval-mode rating past a target, by a
+ * greedy search that runs whole on the device (csrc/narre_search.hip).  A review enters NARRE's score only through its
+ * own latent and its own attention logit (NARRE.attention, NARRE.py:53-64; the head of NARRE.py:38-46, 115-124), and a
+ * removal is the loader's own (`skip`, data.py:144-172 for the reviews, data.py:275-279 for the neighbour ids), so every
+ * candidate removal at every step is one variant of "NARRE what-if scores": no tower runs, the owner pass
+ * (r4r_narre_logits) is paid once.
+ *
+ * r4r_narre_search -- one launch, one wave per pair for the pair's whole search.  Per side exactly r4r_narre_whatif's
+ *   block: z [n, S, L], logit [n, S], own [n, L] or NULL, z_pad [L], logit_pad, S, R with 1 <= R <= S <= 64; u_idx, i_idx
+ *   [n_p]; q_bias, c_bias (NULL = 0); W1, b1, w; 1 <= L <= 64.
+ *   start_u, start_i [n_p] int64 (NULL = 0): the slots already removed before the search; bits >= S are ignored.
+ *   cand_u, cand_i   [n_p] int64 (NULL = no candidate on that side): the slots the search may remove; bits >= S and
+ *                    bits that are also in start are ignored.
+ *   target [n_p] float and direction: 0 = push down, done when score < target; 1 = push up, done when score > target.
+ *                    Strict float compares: a NaN target never ends a search early, an equal score does not cross.
+ *   budget B, 1 <= B <= 64: the most removals of one pair.
+ *   The rule, per pair.  The masks start at start; out_scores[p, 0] is the score under them.  If it satisfies the
+ *   comparison the pair is done with 0 removals.  Otherwise, at each step, the candidates are the slots that are set in
+ *   cand, not yet removed and CURRENTLY SELECTED: among the first R clear slots of their side (a review the model does
+ *   not attend cannot change the score, so it is never a step).  Candidate numbers: c = slot on the user side,
+ *   c = 64 + slot on the item side.  Each candidate's score is the score with that one more bit set; the step takes the
+ *   lowest score (direction 0) or the highest (direction 1), ties (float ==) to the lowest c, a NaN score never over a
+ *   number (all NaN: the lowest c).  The best candidate is taken even when it moves the score the wrong way: a search,
+ *   not a descent with early stopping.  The search ends when the comparison holds, after B removals, or when no
+ *   candidate is left.
+ *   out_order   [n_p, B] int32      c per step; -1 beyond the last step
+ *   out_scores  [n_p, B + 1] float  the score after each step; the columns beyond the last step repeat the last score
+ *   out_steps   [n_p] int32         the removals made
+ *   out_crossed [n_p] int32         1 when the last score satisfies the comparison, else 0
+ *   Bits: a score is r4r_narre_whatif's out_score of the same pair under the same two masks, bit for bit -- the list,
+ *   a', o', p', x, the v_mfma_f32_16x16x4_f32 chain, the epilogue and (head + q_bias[u]) + c_bias[i] of that section,
+ *   restated.  A pair's outputs depend on its own inputs only: not on n_p, the grid or which pairs share the call, and
+ *   on budget by truncation only -- a search at budget B is the prefix of the same search at B' > B.
+ *   Limits: 1 <= L <= 64, 1 <= B <= 64, direction 0 or 1, n_u, n_i >= 0, 0 <= n_p, n_p (B + 1) < 2^31.  Refused before
+ *   the launch and the first dereference, in the entry point's own name: a limit; with n_p > 0 a null z, logit, z_pad of
+ *   either side, u_idx, i_idx, target, W1, b1, w or output, and n_u or n_i == 0.  n_p == 0 returns R4R_OK and enqueues
+ *   nothing.  An index outside [0, n_u) / [0, n_i) is the caller's error.  One launch; nothing allocates, nothing
+ *   synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_narre_search(const float *z_u, const float *logit_u, const float *own_u, const float *z_pad_u, float logit_pad_u,
+                     int64_t n_u, int S_u, int R_u,          /* [n_u, S_u, L], [n_u, S_u], [n_u, L] or NULL, [L]      */
+                     const float *z_i, const float *logit_i, const float *own_i, const float *z_pad_i, float logit_pad_i,
+                     int64_t n_i, int S_i, int R_i,          /* the item side likewise                                */
+                     const int64_t *u_idx, const int64_t *i_idx,              /* [n_p] rows of the sides              */
+                     const int64_t *start_u, const int64_t *start_i,          /* [n_p] bit masks; NULL = 0            */
+                     const int64_t *cand_u, const int64_t *cand_i,            /* [n_p] bit masks; NULL = 0            */
+                     const float *target, int direction, int budget,          /* [n_p]; 0 down / 1 up; 1 .. 64        */
+                     int64_t n_p,
+                     const float *q_bias, const float *c_bias,                /* [n_u], [n_i]; NULL = 0               */
+                     const float *W1, const float *b1, const float *w, int L, /* [L, L], [L], [L]                     */
+                     int32_t *out_order, float *out_scores,                   /* [n_p, B], [n_p, B + 1]               */
+                     int32_t *out_steps, int32_t *out_crossed,                /* [n_p] each                           */
+                     void *stream);
+
+/* ------------------------------------------------------------------------
  * What-if documents: the single-document families' tower over VARIANTS of an owner's document -- chosen reviews taken
  * away, chosen positions occluded -- from the resident pools (csrc/tower_variants.hip, csrc/docs_masked_device.h).
  * Replaces  the loader's `skip`: a training rating's documents leave the rating's own review out of both sides

@@ -895,6 +895,78 @@ def narre_whatif(user, item, u_idx, i_idx, drop_u, drop_i, W1, b1, w, q_bias=Non
     return out
 
 
+NARRE_SEARCH_MAX_BUDGET = 64        # r4r_narre_search: removals per pair
+NARRE_SEARCH_ITEM = 64              # a step's number c: the slot on the user side, 64 + the slot on the item side
+
+
+def narre_search(user, item, u_idx, i_idx, W1, b1, w, target, direction, budget, start_u=None, start_i=None,
+                 cand_u=None, cand_i=None, q_bias=None, c_bias=None):
+    """r4r_narre_search (include/r4r.h, "NARRE counterfactual search"): per pair, the greedy removal of reviews until
+    the score passes ``target``, whole on the device.  ``user`` / ``item``: ``narre_whatif``'s side dicts.  ``target``:
+    float32 [n_p]; ``direction``: 0 = down (done when score < target), 1 = up; ``budget``: 1 .. 64 removals.
+    ``start_u`` / ``start_i``: int64 [n_p] masks of the slots already removed (None = none); ``cand_u`` / ``cand_i``:
+    int64 [n_p] masks of the slots the search may remove (None = none on that side).  No autograd ->
+    (order int32 [n_p, B], scores float32 [n_p, B + 1], steps int32 [n_p], crossed int32 [n_p])."""
+    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
+    if u_idx.numel() != i_idx.numel():
+        raise RuntimeError('reviews4rec_amd.ops: narre_search takes equally long u_idx / i_idx, got %d and %d'
+                           % (u_idx.numel(), i_idx.numel()))
+    n_p = int(u_idx.numel())
+    W1, b1, w = _f32(W1, 'W1'), _f32(b1, 'b1').reshape(-1), _f32(w, 'w').reshape(-1)
+    L = int(b1.numel())
+    if tuple(W1.shape) != (L, L) or w.numel() != L:
+        raise RuntimeError('reviews4rec_amd.ops: narre_search: W1 [L, L], b1 [L], w [L] expected, got %s, %d and %d'
+                           % (tuple(W1.shape), L, w.numel()))
+    for name, v, ok in (('direction', direction, (0, 1)), ('budget', budget, range(1, NARRE_SEARCH_MAX_BUDGET + 1))):
+        if isinstance(v, bool) or not isinstance(v, int) or v not in ok:
+            raise RuntimeError('reviews4rec_amd.ops: narre_search %s = %r outside %d .. %d' % (name, v, ok[0], ok[-1]))
+    target = _f32(target, 'target').reshape(-1)
+    if target.numel() != n_p:
+        raise RuntimeError('reviews4rec_amd.ops: narre_search target must be [%d], got %s' % (n_p, tuple(target.shape)))
+    masks = []
+    for name, m in (('start_u', start_u), ('start_i', start_i), ('cand_u', cand_u), ('cand_i', cand_i)):
+        if m is not None:
+            m = _i64(m, name).reshape(-1)
+            if m.numel() != n_p:
+                raise RuntimeError('reviews4rec_amd.ops: narre_search %s must be [%d], got %s' % (name, n_p, tuple(m.shape)))
+        masks.append(m)
+    sides = []
+    for name, side in (('user', user), ('item', item)):
+        s = {k: None if side.get(k) is None else _f32(side[k], '%s %s' % (name, k)) for k in ('z', 'logit', 'own', 'z_pad')}
+        if s['z'] is None or s['z'].dim() != 3 or s['z'].shape[2] != L or s['logit'] is None or s['z_pad'] is None:
+            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side needs z [n, S, L], logit [n, S] and z_pad [L] '
+                               'with L = %d' % (name, L))
+        n, S = int(s['z'].shape[0]), int(s['z'].shape[1])
+        if tuple(s['logit'].shape) != (n, S) or s['z_pad'].numel() != L \
+                or (s['own'] is not None and tuple(s['own'].shape) != (n, L)):
+            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side: z %s, logit %s, z_pad %s, own %s do not match'
+                               % (name, tuple(s['z'].shape), tuple(s['logit'].shape), tuple(s['z_pad'].shape),
+                                  None if s['own'] is None else tuple(s['own'].shape)))
+        R = side.get('R')
+        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= S:
+            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side: R = %r outside 1 .. S = %d' % (name, R, S))
+        sides.append((s, float(side['logit_pad']), n, S, R))
+    (su, lpu, n_u, S_u, R_u), (si, lpi, n_i, S_i, R_i) = sides
+    biases = []
+    for name, t, n in (('q_bias', q_bias, n_u), ('c_bias', c_bias, n_i)):
+        t = None if t is None else _f32(t, name).reshape(-1)
+        if t is not None and t.numel() != n:
+            raise RuntimeError('reviews4rec_amd.ops: narre_search %s must be [%d], got %s' % (name, n, tuple(t.shape)))
+        biases.append(t)
+    if n_p and (n_u == 0 or n_i == 0):
+        raise RuntimeError('reviews4rec_amd.ops: narre_search: %d pairs over %d / %d owners' % (n_p, n_u, n_i))
+    dev = su['z'].device
+    order = torch.empty((n_p, budget), dtype=torch.int32, device=dev)
+    scores = torch.empty((n_p, budget + 1), dtype=torch.float32, device=dev)
+    steps = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    crossed = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    side_args = lambda s, lp, n, S, R: (ptr(s['z']), ptr(s['logit']), ptr(s['own']), ptr(s['z_pad']), lp, n, S, R)
+    call('r4r_narre_search', *side_args(su, lpu, n_u, S_u, R_u), *side_args(si, lpi, n_i, S_i, R_i), ptr(u_idx),
+         ptr(i_idx), *(ptr(m) for m in masks), ptr(target), direction, budget, n_p, ptr(biases[0]), ptr(biases[1]),
+         ptr(W1), ptr(b1), ptr(w), L, ptr(order), ptr(scores), ptr(steps), ptr(crossed))
+    return order, scores, steps, crossed
+
+
 class TransformLoss(Function):
     """mean_n ||a_n - b_n||^2 (TransNet's source/target representation loss)."""
 

@@ -1274,6 +1274,7 @@ PairReviews = namedtuple('PairReviews', 'w_user w_item rev_user rev_item glogit_
 WhatIf = namedtuple('WhatIf', 'scores base')                                    # NarreCatalogue.what_if
 LeaveOneOut = namedtuple('LeaveOneOut', 'base without_user without_item delta_user delta_item live_user live_item')
 DeletionCurve = namedtuple('DeletionCurve', 'scores aopc order live')           # NarreCatalogue.deletion_curve
+Counterfactual = namedtuple('Counterfactual', 'removed_user removed_item order scores steps crossed base target')  # NarreCatalogue.counterfactual
 DocLeaveOneOut = namedtuple('DocLeaveOneOut', LeaveOneOut._fields + ('reach_user', 'reach_item'))   # Catalogue.leave_one_out
 DocDeletionCurve = namedtuple('DocDeletionCurve', 'scores aopc positions live')                    # Catalogue.deletion_curve
 WHATIF_MAX_SLOTS = 64               # r4r_narre_whatif, r4r_tower_build_variants: one bit of an int64 mask per slot
@@ -2025,6 +2026,140 @@ class NarreCatalogue(Catalogue):
         aopc = (gain.sum(1) / live.clamp(min=1)).to(torch.float32)
         return DeletionCurve(torch.cat([base[:, None], scores], 1).contiguous(), aopc,
                              torch.where(valid, order, torch.full_like(order, -1)), live)
+
+    # ------------------------------------------------------------------ counterfactuals: the fewest reviews that flip a score
+    def _leave_topk_targets(self, u, i, k):
+        """``counterfactual``'s ``k``: per pair the score of the k-th best eligible unseen OTHER item of the user, from
+        ``recommend(users, k + 1)`` over the distinct users; -inf where the user has fewer than k other items."""
+        uu, inv = torch.unique(u, return_inverse=True)
+        items, scores = self.recommend(uu, k + 1)
+        items, scores = items[inv.to(self.dev)], scores[inv.to(self.dev)]
+        other = items != i.to(self.dev)[:, None]               # the item itself steps aside; its place goes to the next
+        place = torch.cumsum(other.to(torch.int64), 1)
+        at = ((place == k) & other).to(torch.int64).argmax(1)
+        has = ((place == k) & other).any(1) & (items.gather(1, at[:, None])[:, 0] >= 0)
+        got = scores.gather(1, at[:, None])[:, 0]
+        return torch.where(has, got, torch.full_like(got, float('-inf'))).contiguous()
+
+    def counterfactual(self, users, items, target=None, k=None, direction='down', side='both', budget=None, slide=True):
+        """Which reviews would have to be missing for the model to stop predicting ``target`` for (users[p], items[p]),
+        and how few are enough?  A greedy search, whole on the device: at each step every review the model currently
+        attends on the chosen side(s) is removed in turn (the loader's removal, as ``what_if``), the removal that moves
+        the score furthest in ``direction`` is kept -- even when it moves the score the wrong way -- and the search
+        ends when the score has passed the target, after ``budget`` removals, or when no attended review is left
+        -> ``Counterfactual`` of device tensors, n = len(users), B = ``budget``:
+
+            removed_user, removed_item  int64 [n, B]    the side's removed reviews as indices in the owner's pool order
+                                                        (what ``what_if`` takes), in step sequence; fill -1
+            order    int64 [n, B]        the step's number c: the review's slot for a user review, 64 + the slot for an
+                                         item review; -1 beyond the last step
+            scores   float32 [n, B + 1]  column 0 the prediction with nothing removed, column t the prediction after
+                                         step t; beyond the last step the last score repeats
+            steps    int64 [n]           the removals made
+            crossed  bool [n]            the last score passed the target (strictly)
+            base     float32 [n]         scores[:, 0]: ``what_if``'s ``base``
+            target   float32 [n]         the threshold each pair was held to
+
+        Exactly one of ``target`` and ``k``.  ``target``: a float or one float per pair, a rating threshold; the pair is
+        done when score < target (``direction='down'``) or score > target ('up').  ``k``: "the item leaves this
+        user's top-k": the target is the score of the k-th best eligible unseen OTHER item from ``recommend(users,
+        k + 1)`` (-inf where the user has fewer than k other items: such a pair never crosses).  ``k`` goes with
+        ``side='item'`` and ``direction='down'`` only: a user's review moves EVERY item's score for that user, so with
+        a user side the list is not a fixed threshold.  The threshold is in ``recommend``'s bits while the search
+        compares r4r_narre_whatif's bits (the two differ as ``what_if``'s ``base`` differs from ``score_pairs``), and an
+        exact tie counts as not crossed.
+
+        ``side``: 'user', 'item' or 'both' -- the candidates are the owner's live reviews of that side or sides.
+        ``budget``: 1 .. 64, default the side's R (R_u + R_i for 'both', capped at 64).  ``slide=True``: each searched
+        side reaches S = min(64, R + budget) reviews of its owners, so that every removal has its slide-in
+        (``what_if``'s slot path, both ``towers`` modes); ``slide=False``: S = R, occlusion.  The greedy answer is an
+        upper bound of the fewest removals, not the minimum.
+
+        The DISTINCT owners go once through the towers and r4r_narre_logits; the pairs go ``pair_batch`` at a time
+        through r4r_narre_search (include/r4r.h, "NARRE counterfactual search"; the results do not depend on the
+        batch).  Every score is ``what_if``'s score of the same removals, bit for bit.  Before anything is enqueued: a
+        ``side`` / ``direction`` outside the above, both or neither of ``target`` / ``k``, ``k`` outside 1 .. 127 or
+        with a user side or 'up', ``budget`` outside 1 .. 64, unequal lengths and a ``target`` tensor of another length
+        raise ValueError, an id outside its side's pool KeyError.  The engine's pending updates are flushed first; the
+        training state is left untouched."""
+        if side not in ('user', 'item', 'both'):
+            raise ValueError("catalogue: side must be 'user', 'item' or 'both', got %r" % (side,))
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        if (target is None) == (k is None):
+            raise ValueError('catalogue: counterfactual takes exactly one of target and k, got target = %r and k = %r'
+                             % (target, k))
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K - 1:
+                raise ValueError('catalogue: counterfactual k = %r outside 1 .. %d' % (k, MAX_K - 1))
+            if side != 'item' or direction != 'down':
+                raise ValueError("catalogue: counterfactual k goes with side='item' and direction='down' only, got side "
+                                 "= %r, direction = %r: a user's review moves every item's score for that user, so the "
+                                 "top-k list is not a fixed threshold" % (side, direction))
+        R = int(self.hp['narre_num_reviews'])
+        if budget is None:
+            budget = min(ops.NARRE_SEARCH_MAX_BUDGET, 2 * R if side == 'both' else R)
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) \
+                or not 1 <= budget <= ops.NARRE_SEARCH_MAX_BUDGET:
+            raise ValueError('catalogue: counterfactual budget = %r outside 1 .. %d' % (budget, ops.NARRE_SEARCH_MAX_BUDGET))
+        B = int(budget)
+        u, i = self._pair_request(users, items)
+        n = int(u.numel())
+        if target is not None:
+            if torch.is_tensor(target) or isinstance(target, (np.ndarray, list, tuple)):
+                tgt = torch.as_tensor(target).detach().reshape(-1).to(torch.float32).cpu()
+                if tgt.numel() != n:
+                    raise ValueError('catalogue: counterfactual target holds %d values for %d pairs' % (tgt.numel(), n))
+            elif isinstance(target, bool) or not isinstance(target, (int, float, np.integer, np.floating)):
+                raise ValueError('catalogue: counterfactual target must be a float or one float per pair, got %r' % (target,))
+            else:
+                tgt = torch.full((n,), float(target), dtype=torch.float32)
+        self._flush()
+        m = self.model
+        i64 = lambda *s: torch.full(s, -1, dtype=torch.int64, device=self.dev)
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
+        if n == 0:
+            return Counterfactual(i64(0, B), i64(0, B), i64(0, B), f32(0, B + 1), i64(0), i64(0).to(torch.bool), f32(0), f32(0))
+        tgt = self._leave_topk_targets(u, i, int(k)) if k is not None else tgt.to(self.dev)
+        on_u, on_i = side in ('user', 'both'), side in ('item', 'both')
+        slots = lambda on: min(WHATIF_MAX_SLOTS, R + B) if (slide and on) else R
+        uu, u_inv = torch.unique(u, return_inverse=True)
+        ui, i_inv = torch.unique(i, return_inverse=True)
+
+        def live_mask(which, ids, inv, S):                     # the owner's reviews among the S slots, one bit each:
+            pool = self._narre_side(which)[1]                  # once per DISTINCT owner, handed to the owner's pairs
+            count = np.minimum(pool.first[ids.numpy() + 1] - pool.first[ids.numpy()], S).astype(np.uint64)
+            bits = np.where(count >= 64, np.uint64(0xFFFFFFFFFFFFFFFF), (np.uint64(1) << np.minimum(count, np.uint64(63))) - np.uint64(1))
+            return torch.from_numpy(bits.view(np.int64)).to(self.dev)[inv]
+        with torch.no_grad():
+            su = self._whatif_side('user', uu.numpy(), slots(on_u))
+            si = self._whatif_side('item', ui.numpy(), slots(on_i))
+            cand_u = live_mask('user', uu, u_inv.to(self.dev), slots(on_u)) if on_u else None
+            cand_i = live_mask('item', ui, i_inv.to(self.dev), slots(on_i)) if on_i else None
+            f64 = lambda t: t.detach().to(torch.float64)
+            qb = (f64(m.user_bias).reshape(-1)[uu.to(self.dev)] + f64(m.global_bias).reshape(())
+                  + f64(m.final[3].bias).reshape(())).to(torch.float32).contiguous()
+            cb = m.item_bias.detach().reshape(-1)[ui.to(self.dev)].to(torch.float32).contiguous()
+            W1, b1, w = m.final[1].weight.detach(), m.final[1].bias.detach(), m.final[3].weight.detach().reshape(-1)
+            u_inv, i_inv = u_inv.to(self.dev), i_inv.to(self.dev)
+            order = torch.empty((n, B), dtype=torch.int32, device=self.dev)
+            scores, steps, crossed = f32(n, B + 1), order.new_empty((n,)), order.new_empty((n,))
+            step = max(1, int(self.pair_batch))
+            for s0 in range(0, n, step):
+                sl = slice(s0, s0 + step)
+                part = lambda t: None if t is None else t[sl].contiguous()
+                order[sl], scores[sl], steps[sl], crossed[sl] = ops.narre_search(
+                    su, si, part(u_inv), part(i_inv), W1, b1, w, part(tgt), 0 if direction == 'down' else 1, B,
+                    cand_u=part(cand_u), cand_i=part(cand_i), q_bias=qb, c_bias=cb)
+            order = order.to(torch.int64)
+            removed = []
+            for lo in (0, ops.NARRE_SEARCH_ITEM):              # a side's steps, moved to the front in step sequence
+                mine = (order >= lo) & (order < lo + ops.NARRE_SEARCH_ITEM)
+                vals = torch.where(mine, order - lo, torch.full_like(order, -1))
+                front = torch.sort((~mine).to(torch.int64), dim=1, stable=True).indices
+                removed.append(vals.gather(1, front).contiguous())
+            return Counterfactual(removed[0], removed[1], order, scores, steps.to(torch.int64), crossed != 0,
+                                  scores[:, 0].contiguous(), tgt)
 
     def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
         """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
