@@ -1824,9 +1824,10 @@ int r4r_narre_whatif(const float *z_u, const float *logit_u, const float *own_u,
  *   out_steps   [n_p] int32         the removals made
  *   out_crossed [n_p] int32         1 when the last score satisfies the comparison, else 0
  *   Bits: a score is r4r_narre_whatif's out_score of the same pair under the same two masks, bit for bit -- the list,
- *   a', o', p', x, the v_mfma_f32_16x16x4_f32 chain, the epilogue and (head + q_bias[u]) + c_bias[i] of that section,
- *   restated.  A pair's outputs depend on its own inputs only: not on n_p, the grid or which pairs share the call, and
- *   on budget by truncation only -- a search at budget B is the prefix of the same search at B' > B.
+ *   a', o', p', x, the v_mfma_f32_16x16x4_f32 chain, the epilogue and (head + q_bias[u]) + c_bias[i] of that section
+ *   (the pooling is one function both kernels call, csrc/narre_variant_device.h).  A pair's outputs depend on its own
+ *   inputs only: not on n_p, the grid or which pairs share the call, and on budget by truncation only -- a search at
+ *   budget B is the prefix of the same search at B' > B.
  *   Limits: 1 <= L <= 64, 1 <= B <= 64, direction 0 or 1, n_u, n_i >= 0, 0 <= n_p, n_p (B + 1) < 2^31.  Refused before
  *   the launch and the first dereference, in the entry point's own name: a limit; with n_p > 0 a null z, logit, z_pad of
  *   either side, u_idx, i_idx, target, W1, b1, w or output, and n_u or n_i == 0.  n_p == 0 returns R4R_OK and enqueues

@@ -8,19 +8,20 @@
 // kept off the lists.
 //
 // One WAVE per owner; a workgroup is EX_WAVES independent waves that share one LDS image of W0 (staged once, then each
-// wave walks its own owners: the only workgroup barrier is the one after the staging).  Per owner:
-//   1. EX_SLOTS = 5 slots at a time, the wave stages [z_r ; other_table[nb_r]] in its own LDS rows (an id outside the
-//      table stages zeros); lane l then owns hidden unit l of all five: W0's row l out of LDS (16-byte reads, row stride
-//      2 LMAX + 4 floats: conflict free) against the five staged rows read as broadcasts, 20 FMAs per 6 LDS reads.
-//      The five accumulators run the same FMA chain in ascending column order, so a slot's logit does not depend on
-//      where in a group it sits; the sum over the hidden units is common.h's fixed-order wave_sum.
-//   2. lane r holds slot r's logit: wave_max, expf, wave_sum, one division -> a_r.
-//   3. lane l sums a_r z_r over the slots in ascending order (a_r read across lanes), plus the owner's own row.
+// wave walks its own owners: the only workgroup barrier is the one after the staging).  Steps 1 to 3 are the functions of
+// csrc/narre_attn_device.h; the what-if logits (narre_whatif.hip) call step 1 too, and the attention Jacobian
+// (narre_pair.hip) keeps the same sequence inline: their logits, attn and out have this kernel's bits.  Per owner:
+//   1. EX_SLOTS = 5 slots at a time, the logits (attn_group_logits): 20 FMAs per 6 LDS reads, a slot's logit independent
+//      of where in a group it sits.
+//   2. lane r holds slot r's logit: the softmax (attn_softmax) -> a_r.
+//   3. lane l sums a_r z_r over the slots in ascending order (attn_pooled), plus the owner's own row.
 //   4. lane r counts the LIVE slots ahead of it (weight descending, ties by ascending slot) and, below K, stores itself
 //      at that place: R <= 64 is one wave's worth of slots, so there is no sort and no insertion chain.
 // Everything an owner's outputs depend on is that owner's inputs and the weights: not N, not the grid, not K, not which
 // outputs are asked for.  The problem is R L 2L MACs per owner (82k at 10 x 64): launch and latency bound, no MFMA.
+// The argument struct is taken by value, as before the owner pass moved into the header: this kernel spills no scalar.
 #include "common.h"
+#include "narre_attn_device.h"
 
 namespace r4r {
 
@@ -52,84 +53,28 @@ struct ExplainArgs {
     int R, L;
 };
 
-__device__ __forceinline__ float lane_value(float v, int lane) {           // `lane` is wave-uniform
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
 // LMAX: the class of L (L <= LMAX) -- it fixes the LDS strides, nothing of the arithmetic.
 template <int LMAX>
 __global__ __launch_bounds__(EX_WAVES *WAVE) void narre_explain_kernel(const ExplainArgs a) {
-    constexpr int CS = 2 * LMAX;       // floats per staged slot: [z_r ; other_r], zero padded
-    constexpr int WS = 2 * LMAX + 4;   // floats per staged row of W0
-    __shared__ __attribute__((aligned(16))) float w0s[LMAX * WS];
-    __shared__ __attribute__((aligned(16))) float cats[EX_WAVES][EX_SLOTS * CS];
+    __shared__ __attribute__((aligned(16))) float w0s[LMAX * ATTN_WS<LMAX>];
+    __shared__ __attribute__((aligned(16))) float cats[EX_WAVES][EX_SLOTS * ATTN_CS<LMAX>];
     const int R = a.R, L = a.L;
-    const int C4 = (2 * L + 3) & ~3;   // the columns walked: 2L rounded up to the 16-byte reads, the pad holds zeros
-    for (int i = threadIdx.x; i < L * WS; i += EX_WAVES * WAVE) {
-        const int l = i / WS, c = i - l * WS;
-        w0s[i] = c < 2 * L ? a.W0[(size_t)l * 2 * L + c] : 0.f;
-    }
+    attn_stage_w0<LMAX>(w0s, a.W0, L, EX_WAVES * WAVE);
     __syncthreads();
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     float *cat = cats[wave];
-    const int lrow = lane < L ? lane : L - 1;                  // lanes past L walk a row that exists and count for nothing
-    const float *wrow = w0s + lrow * WS;
-    const float bias = a.b0[lrow];
-    const float w3l = lane < L ? a.w3[lane] : 0.f;
-    const float b3 = a.b3[0];
+    const AttnLane ln = attn_lane<LMAX>(w0s, a.b0, a.w3, a.b3, L, lane);
     for (int64_t n = (int64_t)blockIdx.x * EX_WAVES + wave; n < a.N; n += (int64_t)gridDim.x * EX_WAVES) {
         const float *zn = a.z + n * R * L;
         const int64_t *nbn = a.nb + n * R;
         float sc = -INFINITY;                                  // lane r: the logit of slot r
-        for (int r0 = 0; r0 < R; r0 += EX_SLOTS) {
-            wave_lds_fence();                                  // the reads of the group before are done
-            for (int i = lane; i < EX_SLOTS * CS; i += WAVE) {
-                const int s = i / CS, c = i - s * CS, r = r0 + s;
-                float v = 0.f;
-                if (r < R) {
-                    if (c < L) {
-                        v = zn[r * L + c];
-                    } else if (c < 2 * L) {
-                        const int64_t id = nbn[r];
-                        if (id >= 0 && id < a.other_rows) v = a.other_table[id * L + (c - L)];
-                    }
-                }
-                cat[i] = v;
-            }
-            wave_lds_fence();
-            float acc[EX_SLOTS];
-#pragma unroll
-            for (int s = 0; s < EX_SLOTS; ++s) acc[s] = 0.f;
-            for (int c = 0; c < C4; c += 4) {
-                const float4 w = *reinterpret_cast<const float4 *>(wrow + c);
-#pragma unroll
-                for (int s = 0; s < EX_SLOTS; ++s) {
-                    const float4 x = *reinterpret_cast<const float4 *>(cat + s * CS + c);
-                    acc[s] = fmaf(w.x, x.x, acc[s]);
-                    acc[s] = fmaf(w.y, x.y, acc[s]);
-                    acc[s] = fmaf(w.z, x.z, acc[s]);
-                    acc[s] = fmaf(w.w, x.w, acc[s]);
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < EX_SLOTS; ++s) {
-                float h = acc[s] + bias;
-                h = h > 0.f ? h : 0.f;
-                const float t = wave_sum(w3l * h) + b3;
-                if (lane == r0 + s) sc = t;
-            }
-        }
-        if (lane >= R) sc = -INFINITY;
-        const float m = wave_max(sc);
-        const float e = lane < R ? expf(sc - m) : 0.f;
-        const float den = wave_sum(e);
-        const float w = e / den;                               // lane r: a_r; 0 in the lanes past R
+        for (int r0 = 0; r0 < R; r0 += EX_SLOTS)
+            attn_group_logits<LMAX, EX_SLOTS>(cat, zn, nbn, a.other_table, a.other_rows, r0, R, L, ln, lane, sc);
+        const float w = attn_softmax(sc, R, lane);         // lane r: a_r; 0 in the lanes past R
         if (a.attn && lane < R) a.attn[n * R + lane] = w;
         if (a.out) {
-            float o = 0.f;
-            const int l = lane < L ? lane : 0;
-            for (int r = 0; r < R; ++r) o = fmaf(lane_value(w, r), zn[r * L + l], o);
+            float o = attn_pooled(w, zn, R, L, lane);
             if (lane < L) {
                 if (a.own_table) o += a.own_table[a.owner[n] * L + lane];
                 a.out[n * L + lane] = o;

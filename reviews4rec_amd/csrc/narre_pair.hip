@@ -8,8 +8,9 @@
 // p = o + own row;  x = p_u o p_i,  t = W1 x + b1,  score = w . relu(t) + scalars.
 //
 // Owner pass: narre_explain.hip's kernel shape -- one WAVE per owner, JAC_WAVES waves share one LDS image of W0 -- and
-// its instruction sequence for the logits, the softmax and the pooled vector, restated here so that attn and out have
-// r4r_narre_explain's bits.  The ReLU masks of a slot (one bit per hidden unit) are a ballot kept in lane r's registers.
+// the instruction sequence of csrc/narre_attn_device.h for the logits, the softmax and the pooled vector, so that attn and
+// out have r4r_narre_explain's bits.  It stands inline here, with the ReLU ballot in its epilogue: as calls of the shared
+// functions this kernel measured 3 % slower at L = 64.  The ReLU masks of a slot (one bit per hidden unit) are a ballot kept in lane r's registers.
 // Then per slot r: lane j chains D_r[j] = sum_m [pre_rm > 0] w3_m W0[m, j] over m ascending out of the LDS image (row m,
 // consecutive j: conflict free), dz_r is the fixed-order wave sum of D_r[j] z_r[j], and E_r = D_r fc is cols_matvec with
 // D_r as an LDS broadcast (the wave's staging rows are free by then).
@@ -67,10 +68,6 @@ struct NarrePairLds {                  // one wave's slice
     float dl[NP_MAXR];                 // delta_r
     float b[NP_MAXF];                  // g fc
 };
-
-__device__ __forceinline__ float np_lane(float v, int lane) {              // `lane` is wave-uniform
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
 
 __device__ __forceinline__ uint32_t np_lane_u32(uint32_t v, int lane) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
@@ -198,7 +195,7 @@ __global__ __launch_bounds__(JAC_WAVES *WAVE) void narre_attn_jac_kernel(const J
         if (a.out || a.pooled_attn) {
             float o = 0.f;
             const int l = lane < L ? lane : 0;
-            for (int r = 0; r < R; ++r) o = fmaf(np_lane(w, r), zn[r * L + l], o);
+            for (int r = 0; r < R; ++r) o = fmaf(lane_value(w, r), zn[r * L + l], o);
             if (lane < L) {
                 if (a.pooled_attn) a.pooled_attn[n * L + lane] = o;
                 if (a.out) {
@@ -214,7 +211,7 @@ __global__ __launch_bounds__(JAC_WAVES *WAVE) void narre_attn_jac_kernel(const J
                 float d = 0.f;                                 // lane j: D_r[j], m ascending, a masked unit as 0.0f
                 for (int mm = 0; mm < L; ++mm) {
                     const uint32_t bit = (mm < 32 ? lo >> mm : hi >> (mm - 32)) & 1u;
-                    const float c = bit ? np_lane(w3l, mm) : 0.f;
+                    const float c = bit ? lane_value(w3l, mm) : 0.f;
                     d = fmaf(c, w0s[mm * WS + lrow], d);
                 }
                 const float zr = lane < L ? zn[r * L + lane] : 0.f;

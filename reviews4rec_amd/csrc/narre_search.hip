@@ -11,13 +11,11 @@
 // removed bit; the lowest (direction 0) or highest (direction 1) score is taken, ties to the lowest c (c = slot on the
 // user side, 64 + slot on the item side), a NaN never over a number.
 //
-// Bits: a candidate's score is r4r_narre_whatif's score of the same pair under the same two masks, bit for bit.  The
-// instruction sequence of csrc/narre_whatif.hip's variant pass is restated here: the popcount rank and scatter of the
-// selected list, wave_max, expf, wave_sum, one division, o' chained over k ascending with fmaf, + own, x = p_u o p_i into
-// a 16 x 66 tile, v_mfma_f32_16x16x4_f32 with W1 as A in topk_hmlp.hip's fragment layout (t ascending), the ReLU / w /
-// bias epilogue with its two __shfl_xor adds, (h + qb) + cb.  A column of the MFMA depends on that column's B values only,
-// so a candidate's bits depend on its own pair's inputs and its two masks: not on its column, the other candidates, n_p,
-// the grid or the budget.
+// Bits: a candidate's score is r4r_narre_whatif's score of the same pair under the same two masks, bit for bit: both
+// kernels call csrc/narre_variant_device.h's variant_pooled for the selected list, its softmax and the pooled vector, add
+// own, write x = p_u o p_i into a row of the 16 x 66 tile, load W1's fragments in the same layout and end in (h + qb) + cb
+// over the same MFMA head.  A column of the MFMA depends on that column's B values only, so a candidate's bits depend on
+// its own pair's inputs and its two masks: not on its column, the other candidates, n_p, the grid or the budget.
 //
 // Shape: one WAVE runs a pair's whole search, grid-strided; the waves of a workgroup are independent, each with its own
 // slice of dynamic LDS (narre_whatif_kernel's slice), the pair staged ONCE for all steps.  W1's fragments, b1 and w are
@@ -25,20 +23,13 @@
 // every candidate of the other side; candidates fill the 16 columns of the tile, ceil(candidates / 16) MFMA groups; the
 // group's scores are walked in ascending c by wave-uniform reads, the groups in ascending order, so a tie keeps the
 // lowest c.  The argument struct is read through kernel_args<>() (common.h); every write is a plain vector store.
-#include <math.h>
-
 #include "common.h"
+#include "narre_variant_device.h"
 
 namespace r4r {
 
-typedef float ns_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int NS_MAXS = 64, NS_MAXL = 64, NS_MAXB = 64;
-constexpr int NS_GROUP = 16;           // candidates per MFMA group: the columns of one tile
-constexpr int NS_XS = 66;              // floats per row of the x tile: bank (mod 32) = 2 column + k quarter
-constexpr int NS_MAX_WAVES = 4;        // waves per workgroup, fewer where their LDS slices would pass 64 KiB
+constexpr int NS_MAXB = 64;
 constexpr int NS_MAX_BLOCKS = 8192;    // beyond, a workgroup's waves loop over pairs
-constexpr int NS_LDS_BYTES = 64 * 1024;
 
 struct SearchSide {                    // one side of a pair
     const float *z, *logit, *own, *z_pad;
@@ -61,45 +52,12 @@ struct SearchArgs {
     int32_t *out_steps, *out_crossed;
 };
 
-__device__ __forceinline__ float ns_lane(float v, int lane) {              // `lane` is wave-uniform
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
 __device__ __forceinline__ uint64_t ns_uniform(uint64_t m) {               // a mask every lane holds, as a scalar
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |
            (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
 }
 
 __device__ __forceinline__ uint64_t ns_slots(int S) { return S >= 64 ? ~0ull : ((1ull << S) - 1ull); }
-
-// One side under `mask`: the selected list, its softmax and the pooled vector o' (lane l; 0 past L) -- narre_whatif.hip's
-// whatif_pooled, statement for statement.  zs: the side's staged rows [S + 1, L] (row S = z_pad), lgs: its staged logits
-// [S + 1], sel: 64 ints of the wave.
-__device__ __forceinline__ float search_pooled(const float *zs, const float *lgs, int *sel, uint64_t mask, int S, int R,
-                                               int L, int lane) {
-    const uint64_t all = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
-    const uint64_t keep = ~mask & all;                         // bits at positions >= S are ignored
-    const int left = __builtin_popcountll(keep);
-    const int nsel = left < R ? left : R;
-    const int rank = __builtin_popcountll(keep & ((1ull << lane) - 1ull));
-    wave_lds_fence();                                          // the reads of the list before are done
-    if (((keep >> lane) & 1ull) && rank < R) sel[rank] = lane;
-    if (lane >= nsel && lane < R) sel[lane] = S;               // the pad slot
-    wave_lds_fence();
-    const int sk = lane < R ? sel[lane] : S;                   // lane k: the k-th selected slot
-    const float lg = lane < R ? lgs[sk] : -INFINITY;
-    const float m = wave_max(lg);
-    const float e = lane < R ? expf(lg - m) : 0.f;
-    const float den = wave_sum(e);
-    const float w = e / den;                                   // lane k: a'_k; 0 in the lanes past R
-    float o = 0.f;
-    const int l = lane < L ? lane : 0;
-    for (int k = 0; k < R; ++k) {
-        const int s = __builtin_amdgcn_readlane(sk, k);
-        o = fmaf(ns_lane(w, k), zs[s * L + l], o);
-    }
-    return lane < L ? o : 0.f;
-}
 
 // The slots of a side the model attends under `mask`: the first R clear slots of 0 .. S - 1, as a wave-uniform mask.
 __device__ __forceinline__ uint64_t search_selected(uint64_t mask, int S, int R, int lane) {
@@ -108,33 +66,9 @@ __device__ __forceinline__ uint64_t search_selected(uint64_t mask, int S, int R,
     return __builtin_amdgcn_ballot_w64(((keep >> lane) & 1ull) && rank < R);
 }
 
-// The head over the 16 columns of the x tile -> lanes 0 .. 15: the head of column `lane` (before the biases).
-template <int LT>
-__device__ __forceinline__ float search_head(const float *xs, const float (&wf)[LT][4 * LT], const float (&bj)[LT][4],
-                                             const float (&wj)[LT][4], int row, int kq) {
-    constexpr int KT = 4 * LT, HT = LT;
-    ns_f32x4 acc[HT];
-#pragma unroll
-    for (int ht = 0; ht < HT; ++ht) acc[ht] = (ns_f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {                             // every accumulator sees t ascending
-        const float xb = xs[row * NS_XS + 4 * t + kq];
-#pragma unroll
-        for (int ht = 0; ht < HT; ++ht) acc[ht] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[ht][t], xb, acc[ht], 0, 0, 0);
-    }
-    float h = 0.f;                                             // h_g of this lane's group g = kq
-#pragma unroll
-    for (int ht = 0; ht < HT; ++ht)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h = __builtin_fmaf(wj[ht][r], __builtin_fmaxf(acc[ht][r] + bj[ht][r], 0.f), h);
-    h = h + __shfl_xor(h, 16);                                 // h_0 + h_1 | h_2 + h_3
-    h = h + __shfl_xor(h, 32);                                 // (h_0 + h_1) + (h_2 + h_3)
-    return h;
-}
-
 // LT: the class of L (L <= 16 LT): 4 LT MFMAs over the input width, LT 16-row tiles of hidden units.
 template <int LT>
-__global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const SearchArgs) {
+__global__ __launch_bounds__(NV_MAX_WAVES *WAVE) void narre_search_kernel(const SearchArgs) {
     const SearchArgs &a = kernel_args<SearchArgs>();           // each field an s_load next to its use (common.h)
     constexpr int KT = 4 * LT, HT = LT;
     extern __shared__ __attribute__((aligned(16))) float ns_lds[];
@@ -146,10 +80,10 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
     const int Su = a.user.S, Si = a.item.S, Ru = a.user.R, Ri = a.item.R;
     // the wave's slice: x tile | sel | user logits | item logits | user rows | item rows
     float *xs = ns_lds + (size_t)wave * a.slice;
-    int *sel = reinterpret_cast<int *>(xs + NS_GROUP * NS_XS);
-    float *lgu = xs + NS_GROUP * NS_XS + WAVE;
-    float *lgi = lgu + (NS_MAXS + 4);
-    float *zu = lgi + (NS_MAXS + 4);
+    int *sel = reinterpret_cast<int *>(xs + NV_GROUP * NV_XS);
+    float *lgu = xs + NV_GROUP * NV_XS + WAVE;
+    float *lgi = lgu + (NV_MAXS + 4);
+    float *zu = lgi + (NV_MAXS + 4);
     float *zi = zu + (Su + 1) * L;
     const int row = lane & 15, kq = lane >> 4;
     // A fragments of W1 and the epilogue's b1 / w in the accumulator layout (topk_hmlp.hip's HmlpWave::init); zero
@@ -219,16 +153,16 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
         wave_lds_fence();
         // the two sides' p' under the masks so far: a side keeps its vector while its mask stands (the same function of
         // the same inputs, so the same bits)
-        float pu_now = search_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
-        float pi_now = search_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
+        float pu_now = variant_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
+        float pi_now = variant_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
         if (has_own_u) pu_now = pu_now + own_u;
         if (has_own_i) pi_now = pi_now + own_i;
         // column 0 of out_scores: the score under the start masks, as column 0 of a tile
         wave_lds_fence();
-        for (int v = 0; v < NS_GROUP; ++v) xs[v * NS_XS + lane] = v == 0 ? pu_now * pi_now : 0.f;
+        for (int v = 0; v < NV_GROUP; ++v) xs[v * NV_XS + lane] = v == 0 ? pu_now * pi_now : 0.f;
         wave_lds_fence();
-        float score = (search_head<LT>(xs, wf, bj, wj, row, kq) + qb) + cb;
-        score = ns_lane(score, 0);
+        float score = (variant_head<LT>(xs, wf, bj, wj, row, kq) + qb) + cb;
+        score = lane_value(score, 0);
         float *scores = a.out_scores + p * (B + 1);
         int32_t *order = a.out_order + p * B;
         if (lane == 0) scores[0] = score;
@@ -244,7 +178,7 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
             while (left_u | left_i) {                          // one MFMA group: the next 16 candidates, c ascending
                 int nv = 0, my_c = -1;
                 wave_lds_fence();                              // the tile reads of the group before are done
-                for (int v = 0; v < NS_GROUP; ++v) {
+                for (int v = 0; v < NV_GROUP; ++v) {
                     float x = 0.f;
                     if (left_u | left_i) {
                         int c;
@@ -252,26 +186,26 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
                             const int s = __builtin_ctzll(left_u);
                             left_u &= left_u - 1ull;
                             c = s;
-                            float pu = search_pooled(zu, lgu, sel, mask_u | (1ull << s), Su, Ru, L, lane);
+                            float pu = variant_pooled(zu, lgu, sel, mask_u | (1ull << s), Su, Ru, L, lane);
                             if (has_own_u) pu = pu + own_u;
                             x = pu * pi_now;                   // 0 in the lanes past L
                         } else {
                             const int s = __builtin_ctzll(left_i);
                             left_i &= left_i - 1ull;
                             c = 64 + s;
-                            float pi = search_pooled(zi, lgi, sel, mask_i | (1ull << s), Si, Ri, L, lane);
+                            float pi = variant_pooled(zi, lgi, sel, mask_i | (1ull << s), Si, Ri, L, lane);
                             if (has_own_i) pi = pi + own_i;
                             x = pu_now * pi;
                         }
                         if (lane == v) my_c = c;
                         nv = v + 1;
                     }
-                    xs[v * NS_XS + lane] = x;                  // every lane: the tile's columns L .. 63 hold zeros
+                    xs[v * NV_XS + lane] = x;                  // every lane: the tile's columns L .. 63 hold zeros
                 }
                 wave_lds_fence();
-                const float got = (search_head<LT>(xs, wf, bj, wj, row, kq) + qb) + cb;     // lanes 0 .. 15: column = lane
+                const float got = (variant_head<LT>(xs, wf, bj, wj, row, kq) + qb) + cb;     // lanes 0 .. 15: column = lane
                 for (int v = 0; v < nv; ++v) {                 // ascending c: a later candidate must be strictly better
-                    const float s = ns_lane(got, v);
+                    const float s = lane_value(got, v);
                     const bool better = !have || (best != best && s == s) || (up ? s > best : s < best);
                     if (better) {
                         have = true;
@@ -283,11 +217,11 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
             // the best candidate is taken, whichever way it moves the score
             if (best_c < 64) {
                 mask_u |= 1ull << best_c;
-                pu_now = search_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
+                pu_now = variant_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
                 if (has_own_u) pu_now = pu_now + own_u;
             } else {
                 mask_i |= 1ull << (best_c - 64);
-                pi_now = search_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
+                pi_now = variant_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
                 if (has_own_i) pi_now = pi_now + own_i;
             }
             score = best;
@@ -309,11 +243,6 @@ __global__ __launch_bounds__(NS_MAX_WAVES *WAVE) void narre_search_kernel(const 
     }
 }
 
-inline size_t search_slice_floats(int S_u, int S_i, int L) {
-    const size_t n = (size_t)NS_GROUP * NS_XS + WAVE + 2 * (NS_MAXS + 4) + (size_t)(S_u + 1 + S_i + 1) * L;
-    return (n + 3) & ~(size_t)3;
-}
-
 }  // namespace r4r
 
 using namespace r4r;
@@ -326,30 +255,20 @@ extern "C" int r4r_narre_search(const float *z_u, const float *logit_u, const fl
                                 int budget, int64_t n_p, const float *q_bias, const float *c_bias, const float *W1,
                                 const float *b1, const float *w, int L, int32_t *out_order, float *out_scores,
                                 int32_t *out_steps, int32_t *out_crossed, void *stream) {
-    R4R_REQUIRE(S_u >= 1 && S_u <= NS_MAXS, "r4r_narre_search: S_u=%d slots outside 1..%d", S_u, NS_MAXS);
-    R4R_REQUIRE(S_i >= 1 && S_i <= NS_MAXS, "r4r_narre_search: S_i=%d slots outside 1..%d", S_i, NS_MAXS);
-    R4R_REQUIRE(R_u >= 1 && R_u <= S_u, "r4r_narre_search: R_u=%d attended slots outside 1..S_u=%d", R_u, S_u);
-    R4R_REQUIRE(R_i >= 1 && R_i <= S_i, "r4r_narre_search: R_i=%d attended slots outside 1..S_i=%d", R_i, S_i);
-    R4R_REQUIRE(L >= 1 && L <= NS_MAXL, "r4r_narre_search: L=%d latent units outside 1..%d", L, NS_MAXL);
     R4R_REQUIRE(budget >= 1 && budget <= NS_MAXB, "r4r_narre_search: budget=%d removals outside 1..%d", budget, NS_MAXB);
     R4R_REQUIRE(direction == 0 || direction == 1, "r4r_narre_search: direction=%d is neither 0 (down) nor 1 (up)",
                 direction);
-    R4R_REQUIRE(n_u >= 0 && n_i >= 0, "r4r_narre_search: n_u=%lld / n_i=%lld negative", (long long)n_u, (long long)n_i);
     R4R_REQUIRE(n_p >= 0 && n_p < (1ll << 31) && n_p * (budget + 1) < (1ll << 31), "r4r_narre_search: n_p=%lld pairs x "
                 "(budget=%d + 1) scores outside 0..2^31-1", (long long)n_p, budget);
+    if (int rc = variant_require("r4r_narre_search", z_u, logit_u, z_pad_u, n_u, S_u, R_u, z_i, logit_i, z_pad_i, n_i, S_i,
+                                 R_i, u_idx, i_idx, n_p, W1, b1, w, L))
+        return rc;
     if (n_p == 0) return R4R_OK;
-    R4R_REQUIRE(z_u && logit_u && z_pad_u, "r4r_narre_search: null pointer among z_u, logit_u, z_pad_u");
-    R4R_REQUIRE(z_i && logit_i && z_pad_i, "r4r_narre_search: null pointer among z_i, logit_i, z_pad_i");
-    R4R_REQUIRE(u_idx && i_idx, "r4r_narre_search: null pointer among u_idx, i_idx");
     R4R_REQUIRE(target, "r4r_narre_search: null target");
-    R4R_REQUIRE(W1 && b1 && w, "r4r_narre_search: null pointer among W1, b1, w");
     R4R_REQUIRE(out_order && out_scores && out_steps && out_crossed,
                 "r4r_narre_search: null pointer among out_order, out_scores, out_steps, out_crossed");
-    R4R_REQUIRE(n_u >= 1 && n_i >= 1, "r4r_narre_search: n_p=%lld pairs over n_u=%lld / n_i=%lld rows", (long long)n_p,
-                (long long)n_u, (long long)n_i);
-    const size_t slice = search_slice_floats(S_u, S_i, L);
-    int waves = NS_MAX_WAVES;
-    while (waves > 1 && waves * slice * sizeof(float) > (size_t)NS_LDS_BYTES) waves >>= 1;
+    const size_t slice = variant_slice_floats(S_u, S_i, L);
+    const int waves = variant_waves(slice);
     SearchArgs a{{z_u, logit_u, own_u, z_pad_u, start_u, cand_u, logit_pad_u, S_u, R_u},
                  {z_i, logit_i, own_i, z_pad_i, start_i, cand_i, logit_pad_i, S_i, R_i},
                  u_idx, i_idx, target, n_p, direction, budget, q_bias, c_bias, W1, b1, w, L, (int)slice,
@@ -358,13 +277,8 @@ extern "C" int r4r_narre_search(const float *z_u, const float *logit_u, const fl
     const dim3 grid((unsigned)(want < NS_MAX_BLOCKS ? want : NS_MAX_BLOCKS)), block(waves * WAVE);
     const size_t lds = waves * slice * sizeof(float);
     hipStream_t st = as_stream(stream);
-    if (L <= 16)
-        hipLaunchKernelGGL(narre_search_kernel<1>, grid, block, lds, st, a);
-    else if (L <= 32)
-        hipLaunchKernelGGL(narre_search_kernel<2>, grid, block, lds, st, a);
-    else if (L <= 48)
-        hipLaunchKernelGGL(narre_search_kernel<3>, grid, block, lds, st, a);
-    else
-        hipLaunchKernelGGL(narre_search_kernel<4>, grid, block, lds, st, a);
+    variant_dispatch(L, [&](auto lt) {
+        hipLaunchKernelGGL(narre_search_kernel<decltype(lt)::value>, grid, block, lds, st, a);
+    });
     return check_launch("r4r_narre_search");
 }

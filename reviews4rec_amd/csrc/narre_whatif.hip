@@ -9,39 +9,31 @@
 // NARRE.py:24-36 and the head of NARRE.py:38-46, 115-124 (dropout is the identity in eval mode).
 //
 // Owner pass: narre_explain.hip's kernel shape -- one WAVE per owner, LOGIT_WAVES waves share one LDS image of W0 -- and
-// its instruction sequence for the logits, restated here over S <= 64 slots, so that a slot's logit has the bits that
-// feed r4r_narre_explain's softmax.
-// Variant pass: one WAVE per (pair, group of 16 variants), grid-strided; WHATIF waves per workgroup are independent.
+// its logits over S <= 64 slots: the same functions of csrc/narre_attn_device.h, so a slot's logit has the bits that feed
+// r4r_narre_explain's softmax.
+// Variant pass: one WAVE per (pair, group of 16 variants), grid-strided; the waves of a workgroup are independent.
 //   1. the wave stages the pair's two z blocks [S, L] and logits [S] in its own LDS slice, the pad slot (z_pad,
 //      logit_pad) as row S of each;
-//   2. per variant and side: lane s ranks slot s among the clear bits below it (one popcount) and, below R, scatters
-//      itself to its place of the selected list; the places beyond hold the pad row.  Lane k then holds the k-th selected
-//      logit: wave_max, expf, wave_sum, one division -> a'_k; lane l chains o'_l = fmaf(a'_k, z'_k[l], o'_l) over k
-//      ascending out of the staged rows (row stride L: consecutive lanes, conflict free);
-//   3. x = (o'_u + own_u) o (o'_i + own_i) of the variant goes to row (variant mod 16) of an LDS tile (row stride 66
-//      floats: the B-fragment reads below are conflict free in both 32-lane halves);
+//   2. per variant and side, csrc/narre_variant_device.h's variant_pooled (the counterfactual search calls the same
+//      function): the selected list of the mask, its softmax, the pooled vector o'; a side whose mask repeats keeps it;
+//   3. x = (o'_u + own_u) o (o'_i + own_i) of the variant goes to row (variant mod 16) of an LDS tile (row stride 66);
 //   4. the 16 variants are the columns of v_mfma_f32_16x16x4_f32: A = W1 in topk_hmlp.hip's fragment layout, loaded once
-//      per wave, B = x read from the tile; ReLU, w and the biases in the epilogue, as topk_hmlp.hip's HmlpWave does.
+//      per wave, B = x read from the tile; ReLU, w and the biases in the epilogue -- variant_head's sequence, inline here
+//      as before (as a call it changed this kernel's code at L <= 32).
 // A column of the MFMA depends on that column's B values only, so a variant's bits depend on its own pair's inputs, its
 // ordered selected list and its pad count: not on V, its column, n_p, the grid or the other variants.
 // Both kernels read their argument struct through kernel_args<>() (common.h).
-#include <math.h>
-
 #include "common.h"
+#include "narre_attn_device.h"
+#include "narre_variant_device.h"
 
 namespace r4r {
-
-typedef float wi_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WI_MAXS = 64, WI_MAXL = 64;
 constexpr int LOGIT_WAVES = 8;         // waves (= owners in flight) per workgroup, sharing one image of W0
 constexpr int LOGIT_SLOTS = 5;         // slots per staged group: narre_explain.hip's EX_SLOTS (the bits do not depend on it)
 constexpr int LOGIT_MAX_BLOCKS = 1024; // beyond, a workgroup's waves loop over owners
-constexpr int WI_GROUP = 16;           // variants per wave pass: the columns of one MFMA tile
-constexpr int WI_XS = 66;              // floats per row of the x tile: bank (mod 32) = 2 column + k quarter
-constexpr int WI_MAX_WAVES = 4;        // waves per workgroup, fewer where their LDS slices would pass 64 KiB
 constexpr int WI_MAX_BLOCKS = 8192;    // beyond, a workgroup's waves loop over (pair, group)
-constexpr int WI_LDS_BYTES = 64 * 1024;
 
 struct LogitArgs {
     const float *z;
@@ -72,115 +64,34 @@ struct WhatifArgs {
     float *out_score;
 };
 
-__device__ __forceinline__ float wi_lane(float v, int lane) {              // `lane` is wave-uniform
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
 // LMAX: the class of L (L <= LMAX) -- it fixes the LDS strides, nothing of the arithmetic.
 template <int LMAX>
 __global__ __launch_bounds__(LOGIT_WAVES *WAVE) void narre_logits_kernel(const LogitArgs) {
     const LogitArgs &a = kernel_args<LogitArgs>();             // each field an s_load next to its use (common.h)
-    constexpr int CS = 2 * LMAX;       // floats per staged slot: [z_s ; other_s], zero padded
-    constexpr int WS = 2 * LMAX + 4;   // floats per staged row of W0
-    __shared__ __attribute__((aligned(16))) float w0s[LMAX * WS];
-    __shared__ __attribute__((aligned(16))) float cats[LOGIT_WAVES][LOGIT_SLOTS * CS];
+    __shared__ __attribute__((aligned(16))) float w0s[LMAX * ATTN_WS<LMAX>];
+    __shared__ __attribute__((aligned(16))) float cats[LOGIT_WAVES][LOGIT_SLOTS * ATTN_CS<LMAX>];
     const int S = a.S, L = a.L;
-    const int C4 = (2 * L + 3) & ~3;   // the columns walked: 2L rounded up to the 16-byte reads, the pad holds zeros
-    {
-        const float *W0 = a.W0;
-        for (int i = threadIdx.x; i < L * WS; i += LOGIT_WAVES * WAVE) {
-            const int l = i / WS, c = i - l * WS;
-            w0s[i] = c < 2 * L ? W0[(size_t)l * 2 * L + c] : 0.f;
-        }
-    }
+    attn_stage_w0<LMAX>(w0s, a.W0, L, LOGIT_WAVES * WAVE);
     __syncthreads();
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
     float *cat = cats[wave];
-    const int lrow = lane < L ? lane : L - 1;                  // lanes past L walk a row that exists and count for nothing
-    const float *wrow = w0s + lrow * WS;
-    const float bias = a.b0[lrow];
-    const float w3l = lane < L ? a.w3[lane] : 0.f;
-    const float b3 = a.b3[0];
+    const AttnLane ln = attn_lane<LMAX>(w0s, a.b0, a.w3, a.b3, L, lane);
     const int64_t N = a.N, other_rows = a.other_rows;
     const float *other_table = a.other_table;
     for (int64_t n = (int64_t)blockIdx.x * LOGIT_WAVES + wave; n < N; n += (int64_t)gridDim.x * LOGIT_WAVES) {
         const float *zn = a.z + n * S * L;
         const int64_t *nbn = a.nb + n * S;
         float sc = 0.f;                                        // lane s: the logit of slot s
-        for (int r0 = 0; r0 < S; r0 += LOGIT_SLOTS) {
-            wave_lds_fence();                                  // the reads of the group (or owner) before are done
-            for (int i = lane; i < LOGIT_SLOTS * CS; i += WAVE) {
-                const int s = i / CS, c = i - s * CS, r = r0 + s;
-                float v = 0.f;
-                if (r < S) {
-                    if (c < L) {
-                        v = zn[r * L + c];
-                    } else if (c < 2 * L) {
-                        const int64_t id = nbn[r];
-                        if (id >= 0 && id < other_rows) v = other_table[id * L + (c - L)];
-                    }
-                }
-                cat[i] = v;
-            }
-            wave_lds_fence();
-            float acc[LOGIT_SLOTS];
-#pragma unroll
-            for (int s = 0; s < LOGIT_SLOTS; ++s) acc[s] = 0.f;
-            for (int c = 0; c < C4; c += 4) {
-                const float4 w = *reinterpret_cast<const float4 *>(wrow + c);
-#pragma unroll
-                for (int s = 0; s < LOGIT_SLOTS; ++s) {
-                    const float4 x = *reinterpret_cast<const float4 *>(cat + s * CS + c);
-                    acc[s] = fmaf(w.x, x.x, acc[s]);
-                    acc[s] = fmaf(w.y, x.y, acc[s]);
-                    acc[s] = fmaf(w.z, x.z, acc[s]);
-                    acc[s] = fmaf(w.w, x.w, acc[s]);
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < LOGIT_SLOTS; ++s) {
-                float h = acc[s] + bias;
-                h = h > 0.f ? h : 0.f;
-                const float t = wave_sum(w3l * h) + b3;
-                if (lane == r0 + s) sc = t;
-            }
-        }
+        for (int r0 = 0; r0 < S; r0 += LOGIT_SLOTS)
+            attn_group_logits<LMAX, LOGIT_SLOTS>(cat, zn, nbn, other_table, other_rows, r0, S, L, ln, lane, sc);
         if (lane < S) a.logit[n * S + lane] = sc;
     }
 }
 
-// One side of one variant: the selected list of `mask`, its softmax and the pooled vector o' (lane l; 0 past L).
-// zs: the side's staged rows [S + 1, L] (row S = z_pad), lgs: its staged logits [S + 1], sel: 64 ints of the wave.
-__device__ __forceinline__ float whatif_pooled(const float *zs, const float *lgs, int *sel, uint64_t mask, int S, int R,
-                                               int L, int lane) {
-    const uint64_t all = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
-    const uint64_t keep = ~mask & all;                         // bits at positions >= S are ignored
-    const int left = __builtin_popcountll(keep);
-    const int nsel = left < R ? left : R;
-    const int rank = __builtin_popcountll(keep & ((1ull << lane) - 1ull));
-    wave_lds_fence();                                          // the reads of the list before are done
-    if (((keep >> lane) & 1ull) && rank < R) sel[rank] = lane;
-    if (lane >= nsel && lane < R) sel[lane] = S;               // the pad slot
-    wave_lds_fence();
-    const int sk = lane < R ? sel[lane] : S;                   // lane k: the k-th selected slot
-    const float lg = lane < R ? lgs[sk] : -INFINITY;
-    const float m = wave_max(lg);
-    const float e = lane < R ? expf(lg - m) : 0.f;
-    const float den = wave_sum(e);
-    const float w = e / den;                                   // lane k: a'_k; 0 in the lanes past R
-    float o = 0.f;
-    const int l = lane < L ? lane : 0;
-    for (int k = 0; k < R; ++k) {
-        const int s = __builtin_amdgcn_readlane(sk, k);
-        o = fmaf(wi_lane(w, k), zs[s * L + l], o);
-    }
-    return lane < L ? o : 0.f;
-}
-
 // LT: the class of L (L <= 16 LT): 4 LT MFMAs over the input width, LT 16-row tiles of hidden units.
 template <int LT>
-__global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const WhatifArgs) {
+__global__ __launch_bounds__(NV_MAX_WAVES *WAVE) void narre_whatif_kernel(const WhatifArgs) {
     const WhatifArgs &a = kernel_args<WhatifArgs>();           // each field an s_load next to its use (common.h)
     constexpr int KT = 4 * LT, HT = LT;
     extern __shared__ __attribute__((aligned(16))) float wi_lds[];
@@ -191,10 +102,10 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
     const int Su = a.user.S, Si = a.item.S, Ru = a.user.R, Ri = a.item.R;
     // the wave's slice: x tile | sel | user logits | item logits | user rows | item rows
     float *xs = wi_lds + (size_t)wave * a.slice;
-    int *sel = reinterpret_cast<int *>(xs + WI_GROUP * WI_XS);
-    float *lgu = xs + WI_GROUP * WI_XS + WAVE;
-    float *lgi = lgu + (WI_MAXS + 4);
-    float *zu = lgi + (WI_MAXS + 4);
+    int *sel = reinterpret_cast<int *>(xs + NV_GROUP * NV_XS);
+    float *lgu = xs + NV_GROUP * NV_XS + WAVE;
+    float *lgi = lgu + (NV_MAXS + 4);
+    float *zu = lgi + (NV_MAXS + 4);
     float *zi = zu + (Su + 1) * L;
     const int row = lane & 15, kq = lane >> 4;
     // A fragments of W1 and the epilogue's b1 / w in the accumulator layout (topk_hmlp.hip's HmlpWave::init); zero
@@ -228,12 +139,12 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
             }
         }
     }
-    const int groups = (V + WI_GROUP - 1) / WI_GROUP;
+    const int groups = (V + NV_GROUP - 1) / NV_GROUP;
     const int64_t items = a.n_p * groups;
     for (int64_t it = (int64_t)blockIdx.x * waves + wave; it < items; it += (int64_t)gridDim.x * waves) {
         const int64_t p = it / groups;
-        const int v0 = (int)(it - p * groups) * WI_GROUP;
-        const int nv = V - v0 < WI_GROUP ? V - v0 : WI_GROUP;
+        const int v0 = (int)(it - p * groups) * NV_GROUP;
+        const int nv = V - v0 < NV_GROUP ? V - v0 : NV_GROUP;
         const int64_t u = a.u_idx[p], i = a.i_idx[p];
         wave_lds_fence();                                      // the reads of the item before are done
         {
@@ -262,7 +173,7 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
         const int64_t *du = a.user.drop, *di = a.item.drop;
         uint64_t had_u = 0ull, had_i = 0ull;                   // a side whose mask repeats keeps its pooled vector: the
         float pu_had = 0.f, pi_had = 0.f;                      // same function of the same inputs, so the same bits
-        for (int v = 0; v < WI_GROUP; ++v) {
+        for (int v = 0; v < NV_GROUP; ++v) {
             float x = 0.f;
             if (v < nv) {
                 const int64_t at = p * V + v0 + v;
@@ -271,8 +182,8 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
                                         (uint32_t)__builtin_amdgcn_readfirstlane((int)mu);
                 const uint64_t mask_i = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(mi >> 32)) << 32) |
                                         (uint32_t)__builtin_amdgcn_readfirstlane((int)mi);
-                if (v == 0 || mask_u != had_u) pu_had = whatif_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
-                if (v == 0 || mask_i != had_i) pi_had = whatif_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
+                if (v == 0 || mask_u != had_u) pu_had = variant_pooled(zu, lgu, sel, mask_u, Su, Ru, L, lane);
+                if (v == 0 || mask_i != had_i) pi_had = variant_pooled(zi, lgi, sel, mask_i, Si, Ri, L, lane);
                 had_u = mask_u;
                 had_i = mask_i;
                 float pu = pu_had, pi = pi_had;
@@ -280,15 +191,15 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
                 if (has_own_i) pi = pi + own_i;
                 x = pu * pi;                                   // 0 in the lanes past L
             }
-            xs[v * WI_XS + lane] = x;                          // every lane: the tile's columns L .. 63 hold zeros
+            xs[v * NV_XS + lane] = x;                          // every lane: the tile's columns L .. 63 hold zeros
         }
         wave_lds_fence();
-        wi_f32x4 acc[HT];
+        nv_f32x4 acc[HT];
 #pragma unroll
-        for (int ht = 0; ht < HT; ++ht) acc[ht] = (wi_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int ht = 0; ht < HT; ++ht) acc[ht] = (nv_f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < KT; ++t) {                         // every accumulator sees t ascending
-            const float xb = xs[row * WI_XS + 4 * t + kq];
+            const float xb = xs[row * NV_XS + 4 * t + kq];
 #pragma unroll
             for (int ht = 0; ht < HT; ++ht) acc[ht] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[ht][t], xb, acc[ht], 0, 0, 0);
         }
@@ -304,11 +215,6 @@ __global__ __launch_bounds__(WI_MAX_WAVES *WAVE) void narre_whatif_kernel(const 
             a.out_score[p * V + v0 + row] = (h + qb) + cb;
         }
     }
-}
-
-inline size_t whatif_slice_floats(int S_u, int S_i, int L) {
-    const size_t n = (size_t)WI_GROUP * WI_XS + WAVE + 2 * (WI_MAXS + 4) + (size_t)(S_u + 1 + S_i + 1) * L;
-    return (n + 3) & ~(size_t)3;
 }
 
 }  // namespace r4r
@@ -346,40 +252,25 @@ extern "C" int r4r_narre_whatif(const float *z_u, const float *logit_u, const fl
                                 const int64_t *u_idx, const int64_t *i_idx, const int64_t *drop_u, const int64_t *drop_i,
                                 int64_t n_p, int V, const float *q_bias, const float *c_bias, const float *W1,
                                 const float *b1, const float *w, int L, float *out_score, void *stream) {
-    R4R_REQUIRE(S_u >= 1 && S_u <= WI_MAXS, "r4r_narre_whatif: S_u=%d slots outside 1..%d", S_u, WI_MAXS);
-    R4R_REQUIRE(S_i >= 1 && S_i <= WI_MAXS, "r4r_narre_whatif: S_i=%d slots outside 1..%d", S_i, WI_MAXS);
-    R4R_REQUIRE(R_u >= 1 && R_u <= S_u, "r4r_narre_whatif: R_u=%d attended slots outside 1..S_u=%d", R_u, S_u);
-    R4R_REQUIRE(R_i >= 1 && R_i <= S_i, "r4r_narre_whatif: R_i=%d attended slots outside 1..S_i=%d", R_i, S_i);
-    R4R_REQUIRE(L >= 1 && L <= WI_MAXL, "r4r_narre_whatif: L=%d latent units outside 1..%d", L, WI_MAXL);
     R4R_REQUIRE(V >= 1, "r4r_narre_whatif: V=%d variants per pair, at least 1", V);
-    R4R_REQUIRE(n_u >= 0 && n_i >= 0, "r4r_narre_whatif: n_u=%lld / n_i=%lld negative", (long long)n_u, (long long)n_i);
     R4R_REQUIRE(n_p >= 0 && n_p < (1ll << 31) && n_p * V < (1ll << 31), "r4r_narre_whatif: n_p=%lld pairs x V=%d "
                 "variants outside 0..2^31-1", (long long)n_p, V);
+    if (int rc = variant_require("r4r_narre_whatif", z_u, logit_u, z_pad_u, n_u, S_u, R_u, z_i, logit_i, z_pad_i, n_i, S_i,
+                                 R_i, u_idx, i_idx, n_p, W1, b1, w, L))
+        return rc;
     if (n_p == 0) return R4R_OK;
-    R4R_REQUIRE(z_u && logit_u && z_pad_u, "r4r_narre_whatif: null pointer among z_u, logit_u, z_pad_u");
-    R4R_REQUIRE(z_i && logit_i && z_pad_i, "r4r_narre_whatif: null pointer among z_i, logit_i, z_pad_i");
-    R4R_REQUIRE(u_idx && i_idx, "r4r_narre_whatif: null pointer among u_idx, i_idx");
-    R4R_REQUIRE(W1 && b1 && w, "r4r_narre_whatif: null pointer among W1, b1, w");
     R4R_REQUIRE(out_score, "r4r_narre_whatif: null out_score");
-    R4R_REQUIRE(n_u >= 1 && n_i >= 1, "r4r_narre_whatif: n_p=%lld pairs over n_u=%lld / n_i=%lld rows", (long long)n_p,
-                (long long)n_u, (long long)n_i);
-    const size_t slice = whatif_slice_floats(S_u, S_i, L);
-    int waves = WI_MAX_WAVES;
-    while (waves > 1 && waves * slice * sizeof(float) > (size_t)WI_LDS_BYTES) waves >>= 1;
+    const size_t slice = variant_slice_floats(S_u, S_i, L);
+    const int waves = variant_waves(slice);
     WhatifArgs a{{z_u, logit_u, own_u, z_pad_u, drop_u, logit_pad_u, S_u, R_u},
                  {z_i, logit_i, own_i, z_pad_i, drop_i, logit_pad_i, S_i, R_i},
                  u_idx, i_idx, n_p, V, q_bias, c_bias, W1, b1, w, L, (int)slice, out_score};
-    const int64_t want = cdiv(n_p * cdiv(V, WI_GROUP), waves);
+    const int64_t want = cdiv(n_p * cdiv(V, NV_GROUP), waves);
     const dim3 grid((unsigned)(want < WI_MAX_BLOCKS ? want : WI_MAX_BLOCKS)), block(waves * WAVE);
     const size_t lds = waves * slice * sizeof(float);
     hipStream_t st = as_stream(stream);
-    if (L <= 16)
-        hipLaunchKernelGGL(narre_whatif_kernel<1>, grid, block, lds, st, a);
-    else if (L <= 32)
-        hipLaunchKernelGGL(narre_whatif_kernel<2>, grid, block, lds, st, a);
-    else if (L <= 48)
-        hipLaunchKernelGGL(narre_whatif_kernel<3>, grid, block, lds, st, a);
-    else
-        hipLaunchKernelGGL(narre_whatif_kernel<4>, grid, block, lds, st, a);
+    variant_dispatch(L, [&](auto lt) {
+        hipLaunchKernelGGL(narre_whatif_kernel<decltype(lt)::value>, grid, block, lds, st, a);
+    });
     return check_launch("r4r_narre_whatif");
 }

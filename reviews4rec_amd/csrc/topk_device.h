@@ -40,10 +40,6 @@ template <class IdT> struct fill_id;
 template <> struct fill_id<int> { static constexpr int value = 0x7fffffff; };
 template <> struct fill_id<int64_t> { static constexpr int64_t value = 0x7fffffffffffffffLL; };
 
-__device__ __forceinline__ float lane_value(float v, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-
 // All 64 lanes of one wave insert (s, i) into the sorted list sc / id of K <= 128 slots (two per lane); unused slots hold
 // (-inf, fill_id): never ahead of a real entry, so the list needs no count and its K-th score -- what a newcomer has to
 // beat, -inf while there is room -- is sc[K - 1].  Returns that score as it is after the call.  One LDS round trip:

@@ -835,6 +835,51 @@ def narre_logits(z, nb, other_table, W0, b0, w3, b3):
     return logit
 
 
+def _narre_variant_args(op, user, item, u_idx, i_idx, W1, b1, w, q_bias, c_bias):
+    """What ``narre_whatif`` and ``narre_search`` (``op``) share: u_idx / i_idx, W1 / b1 / w, the two side dicts and the
+    biases, checked and normalised -> (n_p, device, head, tail, keep).  ``head``: the C arguments from z_u to i_idx,
+    ``tail``: those from q_bias to L; ``keep`` holds the normalised tensors until the call is enqueued."""
+    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
+    if u_idx.numel() != i_idx.numel():
+        raise RuntimeError('reviews4rec_amd.ops: %s takes equally long u_idx / i_idx, got %d and %d'
+                           % (op, u_idx.numel(), i_idx.numel()))
+    n_p = int(u_idx.numel())
+    W1, b1, w = _f32(W1, 'W1'), _f32(b1, 'b1').reshape(-1), _f32(w, 'w').reshape(-1)
+    L = int(b1.numel())
+    if tuple(W1.shape) != (L, L) or w.numel() != L:
+        raise RuntimeError('reviews4rec_amd.ops: %s: W1 [L, L], b1 [L], w [L] expected, got %s, %d and %d'
+                           % (op, tuple(W1.shape), L, w.numel()))
+    keep, head, owners = [u_idx, i_idx, W1, b1, w], [], []
+    for name, side in (('user', user), ('item', item)):
+        s = {k: None if side.get(k) is None else _f32(side[k], '%s %s' % (name, k)) for k in ('z', 'logit', 'own', 'z_pad')}
+        if s['z'] is None or s['z'].dim() != 3 or s['z'].shape[2] != L or s['logit'] is None or s['z_pad'] is None:
+            raise RuntimeError('reviews4rec_amd.ops: %s %s side needs z [n, S, L], logit [n, S] and z_pad [L] '
+                               'with L = %d' % (op, name, L))
+        n, S = int(s['z'].shape[0]), int(s['z'].shape[1])
+        if tuple(s['logit'].shape) != (n, S) or s['z_pad'].numel() != L \
+                or (s['own'] is not None and tuple(s['own'].shape) != (n, L)):
+            raise RuntimeError('reviews4rec_amd.ops: %s %s side: z %s, logit %s, z_pad %s, own %s do not match'
+                               % (op, name, tuple(s['z'].shape), tuple(s['logit'].shape), tuple(s['z_pad'].shape),
+                                  None if s['own'] is None else tuple(s['own'].shape)))
+        R = side.get('R')
+        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= S:
+            raise RuntimeError('reviews4rec_amd.ops: %s %s side: R = %r outside 1 .. S = %d' % (op, name, R, S))
+        keep.append(s)
+        owners.append(n)
+        head += [ptr(s['z']), ptr(s['logit']), ptr(s['own']), ptr(s['z_pad']), float(side['logit_pad']), n, S, R]
+    biases = []
+    for name, t, n in (('q_bias', q_bias, owners[0]), ('c_bias', c_bias, owners[1])):
+        t = None if t is None else _f32(t, name).reshape(-1)
+        if t is not None and t.numel() != n:
+            raise RuntimeError('reviews4rec_amd.ops: %s %s must be [%d], got %s' % (op, name, n, tuple(t.shape)))
+        biases.append(t)
+    if n_p and 0 in owners:
+        raise RuntimeError('reviews4rec_amd.ops: %s: %d pairs over %d / %d owners' % (op, n_p, owners[0], owners[1]))
+    head += [ptr(u_idx), ptr(i_idx)]
+    tail = [ptr(biases[0]), ptr(biases[1]), ptr(W1), ptr(b1), ptr(w), L]
+    return n_p, keep[5]['z'].device, head, tail, keep + biases           # the device: the user side's
+
+
 def narre_whatif(user, item, u_idx, i_idx, drop_u, drop_i, W1, b1, w, q_bias=None, c_bias=None):
     """r4r_narre_whatif (include/r4r.h, "NARRE what-if scores"), the variant pass.  ``user`` / ``item``: one dict per
     side with ``z`` [n, S, L], ``logit`` [n, S] (``narre_logits``), ``z_pad`` [L], ``logit_pad`` (a float), ``R`` (the
@@ -842,16 +887,7 @@ def narre_whatif(user, item, u_idx, i_idx, drop_u, drop_i, W1, b1, w, q_bias=Non
     ``drop_i``: int64 [n_p, V] bit masks, bit s = slot s removed; None = nothing removed (one of them fixes V; both None:
     V = 1).  ``W1`` [L, L], ``b1`` [L], ``w`` [L]: final.1 and final.3.weight; ``q_bias`` [n_u] / ``c_bias`` [n_i]: the
     score's scalars, None = 0.  No autograd -> scores, float32 [n_p, V]."""
-    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
-    if u_idx.numel() != i_idx.numel():
-        raise RuntimeError('reviews4rec_amd.ops: narre_whatif takes equally long u_idx / i_idx, got %d and %d'
-                           % (u_idx.numel(), i_idx.numel()))
-    n_p = int(u_idx.numel())
-    W1, b1, w = _f32(W1, 'W1'), _f32(b1, 'b1').reshape(-1), _f32(w, 'w').reshape(-1)
-    L = int(b1.numel())
-    if tuple(W1.shape) != (L, L) or w.numel() != L:
-        raise RuntimeError('reviews4rec_amd.ops: narre_whatif: W1 [L, L], b1 [L], w [L] expected, got %s, %d and %d'
-                           % (tuple(W1.shape), L, w.numel()))
+    n_p, dev, head, tail, keep = _narre_variant_args('narre_whatif', user, item, u_idx, i_idx, W1, b1, w, q_bias, c_bias)
     V, drops = None, []
     for name, d in (('drop_u', drop_u), ('drop_i', drop_i)):
         if d is not None:
@@ -862,36 +898,8 @@ def narre_whatif(user, item, u_idx, i_idx, drop_u, drop_i, W1, b1, w, q_bias=Non
             V = int(d.shape[1])
         drops.append(d)
     V = 1 if V is None else V
-    sides = []
-    for name, side in (('user', user), ('item', item)):
-        s = {k: None if side.get(k) is None else _f32(side[k], '%s %s' % (name, k)) for k in ('z', 'logit', 'own', 'z_pad')}
-        if s['z'] is None or s['z'].dim() != 3 or s['z'].shape[2] != L or s['logit'] is None or s['z_pad'] is None:
-            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side needs z [n, S, L], logit [n, S] and z_pad [L] '
-                               'with L = %d' % (name, L))
-        n, S = int(s['z'].shape[0]), int(s['z'].shape[1])
-        if tuple(s['logit'].shape) != (n, S) or s['z_pad'].numel() != L \
-                or (s['own'] is not None and tuple(s['own'].shape) != (n, L)):
-            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side: z %s, logit %s, z_pad %s, own %s do not match'
-                               % (name, tuple(s['z'].shape), tuple(s['logit'].shape), tuple(s['z_pad'].shape),
-                                  None if s['own'] is None else tuple(s['own'].shape)))
-        R = side.get('R')
-        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= S:
-            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s side: R = %r outside 1 .. S = %d' % (name, R, S))
-        sides.append((s, float(side['logit_pad']), n, S, R))
-    (su, lpu, n_u, S_u, R_u), (si, lpi, n_i, S_i, R_i) = sides
-    biases = []
-    for name, t, n in (('q_bias', q_bias, n_u), ('c_bias', c_bias, n_i)):
-        t = None if t is None else _f32(t, name).reshape(-1)
-        if t is not None and t.numel() != n:
-            raise RuntimeError('reviews4rec_amd.ops: narre_whatif %s must be [%d], got %s' % (name, n, tuple(t.shape)))
-        biases.append(t)
-    if n_p and (n_u == 0 or n_i == 0):
-        raise RuntimeError('reviews4rec_amd.ops: narre_whatif: %d pairs over %d / %d owners' % (n_p, n_u, n_i))
-    out = torch.empty((n_p, V), dtype=torch.float32, device=su['z'].device)
-    side_args = lambda s, lp, n, S, R: (ptr(s['z']), ptr(s['logit']), ptr(s['own']), ptr(s['z_pad']), lp, n, S, R)
-    call('r4r_narre_whatif', *side_args(su, lpu, n_u, S_u, R_u), *side_args(si, lpi, n_i, S_i, R_i), ptr(u_idx),
-         ptr(i_idx), ptr(drops[0]), ptr(drops[1]), n_p, V, ptr(biases[0]), ptr(biases[1]), ptr(W1), ptr(b1), ptr(w), L,
-         ptr(out))
+    out = torch.empty((n_p, V), dtype=torch.float32, device=dev)
+    call('r4r_narre_whatif', *head, ptr(drops[0]), ptr(drops[1]), n_p, V, *tail, ptr(out))
     return out
 
 
@@ -907,16 +915,7 @@ def narre_search(user, item, u_idx, i_idx, W1, b1, w, target, direction, budget,
     ``start_u`` / ``start_i``: int64 [n_p] masks of the slots already removed (None = none); ``cand_u`` / ``cand_i``:
     int64 [n_p] masks of the slots the search may remove (None = none on that side).  No autograd ->
     (order int32 [n_p, B], scores float32 [n_p, B + 1], steps int32 [n_p], crossed int32 [n_p])."""
-    u_idx, i_idx = _i64(u_idx, 'u_idx').reshape(-1), _i64(i_idx, 'i_idx').reshape(-1)
-    if u_idx.numel() != i_idx.numel():
-        raise RuntimeError('reviews4rec_amd.ops: narre_search takes equally long u_idx / i_idx, got %d and %d'
-                           % (u_idx.numel(), i_idx.numel()))
-    n_p = int(u_idx.numel())
-    W1, b1, w = _f32(W1, 'W1'), _f32(b1, 'b1').reshape(-1), _f32(w, 'w').reshape(-1)
-    L = int(b1.numel())
-    if tuple(W1.shape) != (L, L) or w.numel() != L:
-        raise RuntimeError('reviews4rec_amd.ops: narre_search: W1 [L, L], b1 [L], w [L] expected, got %s, %d and %d'
-                           % (tuple(W1.shape), L, w.numel()))
+    n_p, dev, head, tail, keep = _narre_variant_args('narre_search', user, item, u_idx, i_idx, W1, b1, w, q_bias, c_bias)
     for name, v, ok in (('direction', direction, (0, 1)), ('budget', budget, range(1, NARRE_SEARCH_MAX_BUDGET + 1))):
         if isinstance(v, bool) or not isinstance(v, int) or v not in ok:
             raise RuntimeError('reviews4rec_amd.ops: narre_search %s = %r outside %d .. %d' % (name, v, ok[0], ok[-1]))
@@ -930,40 +929,12 @@ def narre_search(user, item, u_idx, i_idx, W1, b1, w, target, direction, budget,
             if m.numel() != n_p:
                 raise RuntimeError('reviews4rec_amd.ops: narre_search %s must be [%d], got %s' % (name, n_p, tuple(m.shape)))
         masks.append(m)
-    sides = []
-    for name, side in (('user', user), ('item', item)):
-        s = {k: None if side.get(k) is None else _f32(side[k], '%s %s' % (name, k)) for k in ('z', 'logit', 'own', 'z_pad')}
-        if s['z'] is None or s['z'].dim() != 3 or s['z'].shape[2] != L or s['logit'] is None or s['z_pad'] is None:
-            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side needs z [n, S, L], logit [n, S] and z_pad [L] '
-                               'with L = %d' % (name, L))
-        n, S = int(s['z'].shape[0]), int(s['z'].shape[1])
-        if tuple(s['logit'].shape) != (n, S) or s['z_pad'].numel() != L \
-                or (s['own'] is not None and tuple(s['own'].shape) != (n, L)):
-            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side: z %s, logit %s, z_pad %s, own %s do not match'
-                               % (name, tuple(s['z'].shape), tuple(s['logit'].shape), tuple(s['z_pad'].shape),
-                                  None if s['own'] is None else tuple(s['own'].shape)))
-        R = side.get('R')
-        if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= S:
-            raise RuntimeError('reviews4rec_amd.ops: narre_search %s side: R = %r outside 1 .. S = %d' % (name, R, S))
-        sides.append((s, float(side['logit_pad']), n, S, R))
-    (su, lpu, n_u, S_u, R_u), (si, lpi, n_i, S_i, R_i) = sides
-    biases = []
-    for name, t, n in (('q_bias', q_bias, n_u), ('c_bias', c_bias, n_i)):
-        t = None if t is None else _f32(t, name).reshape(-1)
-        if t is not None and t.numel() != n:
-            raise RuntimeError('reviews4rec_amd.ops: narre_search %s must be [%d], got %s' % (name, n, tuple(t.shape)))
-        biases.append(t)
-    if n_p and (n_u == 0 or n_i == 0):
-        raise RuntimeError('reviews4rec_amd.ops: narre_search: %d pairs over %d / %d owners' % (n_p, n_u, n_i))
-    dev = su['z'].device
     order = torch.empty((n_p, budget), dtype=torch.int32, device=dev)
     scores = torch.empty((n_p, budget + 1), dtype=torch.float32, device=dev)
     steps = torch.empty((n_p,), dtype=torch.int32, device=dev)
     crossed = torch.empty((n_p,), dtype=torch.int32, device=dev)
-    side_args = lambda s, lp, n, S, R: (ptr(s['z']), ptr(s['logit']), ptr(s['own']), ptr(s['z_pad']), lp, n, S, R)
-    call('r4r_narre_search', *side_args(su, lpu, n_u, S_u, R_u), *side_args(si, lpi, n_i, S_i, R_i), ptr(u_idx),
-         ptr(i_idx), *(ptr(m) for m in masks), ptr(target), direction, budget, n_p, ptr(biases[0]), ptr(biases[1]),
-         ptr(W1), ptr(b1), ptr(w), L, ptr(order), ptr(scores), ptr(steps), ptr(crossed))
+    call('r4r_narre_search', *head, *(ptr(m) for m in masks), ptr(target), direction, budget, n_p, *tail, ptr(order),
+         ptr(scores), ptr(steps), ptr(crossed))
     return order, scores, steps, crossed
 
 
