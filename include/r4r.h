@@ -1903,6 +1903,85 @@ int r4r_tower_span_variants(const int32_t *tok, const int64_t *rev_off, const in
                             float *latent, float *pooled, int32_t *argmax, void *ws, size_t ws_bytes,
                             int64_t *groups_done, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Document fold: the pooled features of a variant document -- chosen reviews taken away, no occlusion -- without the
+ * document and without the tower's gather, and a greedy fewest-review search on top of it (csrc/tower_fold.hip).
+ * Replaces  Conv2d + relu + max_pool over a whole document           common_pytorch_models.py:29-31
+ *           the document a removal makes: the remaining reviews
+ *           joined, cut to input_length, zero padded                data.py:223-235
+ *           the frozen word lookup in front of the tower            DeepCoNN.py:53-54
+ * With ptab[v, j, f] = sum_k table[v, k] conv_w[f, j, k] a window over the tokens (a, c, d) has the value
+ *     y = ((r0 + r1) + r2) + conv_b[f],   r0 = ptab[a, 0, f], r1 = ptab[c, 1, f], r2 = ptab[d, 2, f],
+ * a tap outside the document being a row of 0.0f, every add fp32 and in this order.  It depends on the three tokens
+ * alone, so the maximum over the windows that lie inside one review (`seg`) is computed once per (owner, review) and a
+ * variant row adds only the windows a removal makes new.  pooled[f] = best > 0 ? best : +0.0f, best over all T + 2
+ * windows of the variant's document; no -0 appears.  The pool (tok, rev_off, first) and ids are those of "What-if
+ * documents"; an id must be an owner of the pool or negative (no reviews), a token a row of ptab: neither can be
+ * checked here, the table's height and the pool's size are not arguments.
+ *
+ * r4r_fold_ptab_stride(F): the floats per word of ptab, PS >= 3 F (0 for F outside 1 .. 112); element (v, j, f) is at
+ *   v PS + j F + f.
+ * r4r_fold_project: ptab [V, PS] from table [V, E] and conv_w [F, 3, E]: one launch, 64 x 64 tiles, per element one
+ *   fmaf chain over k ascending (a float64 sum is within (E + 1) 2^-24 sum_k |x_k w_k| of it).  The pad floats of a
+ *   row, 3 F .. PS, are not written.  V == 0 returns R4R_OK and enqueues nothing.
+ * r4r_fold_segments: seg [n, S, F].  For owner ids[i] and slot s < min(count, S): the maximum of y over the windows
+ *   (r[q - 2], r[q - 1], r[q]), 2 <= q < len, of the owner's s-th review r; -inf where len < 3 and for s >= count.
+ *   One wave per (owner, slot): the review's tokens are read 64 at a time, one per lane; then lanes are filters.
+ * r4r_fold_compose: pooled [M, F].  Row m with row_owner[m] < 0 is all +0.0f.  Otherwise o = row_owner[m] is an index
+ *   into ids and seg, and the row is the pooled features of r4r_tower_build_variants' document of (ids[o], drop[m], no
+ *   occlusion, T) -- drop == NULL removes nothing -- by the fold: `pos` = 0 and the last two document tokens (p2, p1)
+ *   = (outside, outside); for each kept review r of the first 64 in order and then the run of all reviews from the
+ *   65th on as one last run, while pos < T, skipping empty runs, with v = min(len, T - pos):
+ *     the windows (p2, p1, r[0]) and, for v >= 2, (p1, r[0], r[1]);
+ *     seg[o, s] where v == len and s < S, else the windows (r[q - 2], r[q - 1], r[q]), 2 <= q < v;
+ *     (p2, p1) = the last two tokens of the document so far, pos += v;
+ *   then min(T - pos, 3) windows that end on the padding's word 0 and the two that hang over the end.  These are all the
+ *   distinct windows of the document, so the result equals the maximum over every window, bit for bit.  One wave per
+ *   row; a row's bits depend on that row alone: not on M, the order of the rows, or S beyond min(count, 64).
+ *
+ * The search (the rule of "NARRE counterfactual search" with "attended" replaced by "shows"), one pair per row p of
+ * n_p, per searched side a pool, ids, own [n_p] (the pair's index into ids), the current mask [n_p] and S, the slots
+ * searched (0 with NULL pointers: the side is not searched); C = S_u + S_i candidate columns, the user side's first:
+ * r4r_fold_search_begin: out_scores[p, :] = score0[p], out_order[p, :] = -1, steps = 0, crossed = done = the
+ *   comparison (direction 0: score < target, 1: score > target; strict fp32, false for a NaN).
+ * r4r_fold_search_rows: a step's candidate rows.  Slot s of a side is a candidate of pair p when p is not done, bit s
+ *   is set in cand (NULL: none) and clear in mask, s < min(count, S), the review is not empty and starts before
+ *   position T of the CURRENT document (the sum of the kept lengths of the lower slots).  row_owner_u / drop_u [n_p, C]:
+ *   column s < S_u holds (own_u[p], mask_u[p] | bit s) for a candidate, else (-1, mask_u[p]); columns >= S_u hold
+ *   (-1, mask_u[p]).  row_owner_i / drop_i likewise with the item side's slots in columns S_u + s.
+ * r4r_fold_search_pick: the step's winner from cand_score [n_p, C] (one score per candidate row; what a non-candidate
+ *   column holds is not read).  The lowest (direction 0) or highest (1) score, ties (float ==) to the lowest column, a
+ *   NaN never over a number (all NaN: the lowest column).  A pair that is done is left alone; one without a candidate
+ *   becomes done.  Otherwise the winner's bit enters its side's mask, out_order[p, steps] = slot (user side) or
+ *   64 + slot (item side), steps += 1, out_scores[p, steps ..] = its score, the winner's latent row n_p + p C + column
+ *   of its side's table z [n_p + n_p C, L] is copied to row p (the pair's current latent), crossed = the comparison,
+ *   done = crossed or steps == budget.  One wave per pair.
+ * Limits: 1 <= F <= 112, E % 4 == 0, 1 <= T <= 65536, 1 <= S <= 64 (0 too for an unsearched side), 1 <= budget <= 64,
+ * 1 <= L, rows and pairs < 2^31.  Refused before the launch and the first dereference, in the entry point's own name: a
+ * limit and, with work to do, a null pointer.  n == 0 (M, n_p) returns R4R_OK and enqueues nothing.  One launch each;
+ * nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_fold_ptab_stride(int F);
+int r4r_fold_project(const float *table, int64_t V, const float *conv_w, float *ptab, int E, int F, void *stream);
+int r4r_fold_segments(const float *ptab, const float *conv_b, const int32_t *tok, const int64_t *rev_off,
+                      const int64_t *first, const int64_t *ids, int64_t n, int S, int F, float *seg, void *stream);
+int r4r_fold_compose(const float *ptab, const float *conv_b, const float *seg, int S, const int32_t *tok,
+                     const int64_t *rev_off, const int64_t *first, const int64_t *row_owner, const int64_t *ids,
+                     const int64_t *drop, int64_t M, int T, int F, float *pooled, void *stream);
+int r4r_fold_search_begin(const float *score0, const float *target, int direction, int budget, int64_t n_p,
+                          int32_t *out_order, float *out_scores,          /* [n_p, B], [n_p, B + 1]                 */
+                          int32_t *out_steps, int32_t *out_crossed, int32_t *done, void *stream);
+int r4r_fold_search_rows(const int64_t *rev_off_u, const int64_t *first_u, const int64_t *ids_u, const int64_t *own_u,
+                         const int64_t *mask_u, const int64_t *cand_u, int S_u,
+                         const int64_t *rev_off_i, const int64_t *first_i, const int64_t *ids_i, const int64_t *own_i,
+                         const int64_t *mask_i, const int64_t *cand_i, int S_i,
+                         const int32_t *done, int64_t n_p, int T,
+                         int64_t *row_owner_u, int64_t *drop_u, int64_t *row_owner_i, int64_t *drop_i, void *stream);
+int r4r_fold_search_pick(const float *cand_score, const int64_t *row_owner_u, const int64_t *row_owner_i, int S_u,
+                         int S_i, const float *target, int direction, int budget, int64_t n_p, int64_t *mask_u,
+                         int64_t *mask_i, float *z_u, float *z_i, int L, int32_t *out_order, float *out_scores,
+                         int32_t *out_steps, int32_t *out_crossed, int32_t *done, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

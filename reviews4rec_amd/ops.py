@@ -207,6 +207,174 @@ def tower_span_variants(pool, ids, T, table, conv_w, conv_b, fc_w, fc_b, group, 
     return out['latent'] if want == ('latent',) else out
 
 
+FOLD_SEARCH_ITEM = 64         # r4r_fold_search_pick: an item review's step number is 64 + its slot
+FOLD_SEARCH_MAX_BUDGET = 64
+
+
+def _fold_pool(pool):
+    """The pool's device tuple (``data._Pool.device``) as the fold's three arrays, checked."""
+    tok, rev_off, first = pool[0], _i64(pool[1], 'rev_off'), _i64(pool[2], 'first')
+    if not tok.is_cuda or tok.dtype != torch.int32:
+        raise RuntimeError('reviews4rec_amd.ops: tok must be int32 on a ROCm device, got %s on %s' % (tok.dtype, tok.device))
+    return tok.contiguous(), rev_off, first
+
+
+def _fold_ptab(ptab, conv_b):
+    ptab, conv_b = _f32(ptab, 'ptab'), _f32(conv_b, 'conv_b').reshape(-1)
+    F = int(conv_b.numel())
+    if ptab.dim() != 2 or ptab.shape[1] != _lib.lib().r4r_fold_ptab_stride(F):
+        raise RuntimeError('reviews4rec_amd.ops: ptab must be [V, r4r_fold_ptab_stride(%d)], got %s' % (F, tuple(ptab.shape)))
+    return ptab, conv_b, F
+
+
+def fold_project(table, conv_w):
+    """r4r_fold_project (include/r4r.h, "Document fold"): ptab [V, PS] fp32, element (v, j, f) at [v, j F + f] =
+    sum_k table[v, k] conv_w[f, j, k], for the whole vocabulary of one tower.  One launch; no autograd."""
+    table, conv_w = _f32(table, 'table'), _f32(conv_w, 'conv_w')
+    if table.shape[1] % 4:                                      # (textcnn_fwd_raw's padding)
+        E0 = table.shape[1]
+        table = _padded_table(table)
+        pw = torch.zeros(tuple(conv_w.shape[:-1]) + (table.shape[1],), dtype=conv_w.dtype, device=conv_w.device)
+        pw[..., :E0].copy_(conv_w)
+        conv_w = pw
+    V, E = (int(d) for d in table.shape)
+    F = int(conv_w.shape[0])
+    if conv_w.numel() != F * 3 * E:
+        raise RuntimeError('reviews4rec_amd.ops: conv_w must hold [F, 3, E] = [%d, 3, %d], got %s' % (F, E, tuple(conv_w.shape)))
+    PS = _lib.lib().r4r_fold_ptab_stride(F)
+    ptab = torch.zeros((V, max(PS, 1)), dtype=torch.float32, device=table.device)
+    call('r4r_fold_project', ptr(table), V, ptr(conv_w), ptr(ptab), E, F)
+    return ptab
+
+
+def fold_segments(ptab, conv_b, pool, ids, S):
+    """r4r_fold_segments: seg fp32 [n, S, F], per owner ``ids[i]`` of ``pool`` and review slot s < S the maximum over
+    the windows that lie inside the review (-inf: fewer than three words, or no such review).  One launch."""
+    ptab, conv_b, F = _fold_ptab(ptab, conv_b)
+    tok, rev_off, first = _fold_pool(pool)
+    ids = _i64(ids, 'ids').reshape(-1)
+    n, S = int(ids.numel()), int(S)
+    seg = torch.empty((n, max(S, 0), F), dtype=torch.float32, device=ids.device)
+    call('r4r_fold_segments', ptr(ptab), ptr(conv_b), ptr(tok), ptr(rev_off), ptr(first), ptr(ids) if n else None, n, S, F,
+         ptr(seg) if n else None)
+    return seg
+
+
+def fold_compose(ptab, conv_b, seg, pool, row_owner, ids, T, drop=None):
+    """r4r_fold_compose: pooled fp32 [M, F], row m = the tower's pooled features of the document of owner
+    ``ids[row_owner[m]]`` without the reviews of ``drop[m]`` (int64 [M] or None), from ``seg`` [n, S, F] of the same
+    ``ids``; a negative ``row_owner[m]`` gives a row of zeros.  One launch."""
+    ptab, conv_b, F = _fold_ptab(ptab, conv_b)
+    tok, rev_off, first = _fold_pool(pool)
+    ids, row_owner, seg = _i64(ids, 'ids').reshape(-1), _i64(row_owner, 'row_owner').reshape(-1), _f32(seg, 'seg')
+    n, M = int(ids.numel()), int(row_owner.numel())
+    if seg.dim() != 3 or seg.shape[0] != n or seg.shape[2] != F:
+        raise RuntimeError('reviews4rec_amd.ops: seg must be [n, S, F] = [%d, S, %d], got %s' % (n, F, tuple(seg.shape)))
+    if drop is not None:
+        drop = _i64(drop, 'drop').reshape(-1)
+        if drop.numel() != M:
+            raise RuntimeError('reviews4rec_amd.ops: drop must be [M] = [%d], got %d masks' % (M, drop.numel()))
+    pooled = torch.empty((M, F), dtype=torch.float32, device=row_owner.device)
+    if M:                                                       # (an empty tensor has no address to pass)
+        call('r4r_fold_compose', ptr(ptab), ptr(conv_b), ptr(seg), int(seg.shape[1]), ptr(tok), ptr(rev_off), ptr(first),
+             ptr(row_owner), ptr(ids), ptr(drop), M, int(T), F, ptr(pooled))
+    return pooled
+
+
+def fold_latents(side, row_owner, T, drop=None, out=None):
+    """compose + the tower's fc for one side -> latent [M, L] (into ``out`` when given).  ``side``: a dict with ptab,
+    conv_b, seg, pool, ids, fc_w, fc_b."""
+    pooled = fold_compose(side['ptab'], side['conv_b'], side['seg'], side['pool'], row_owner, side['ids'], T, drop=drop)
+    fc_w, fc_b = _f32(side['fc_w'], 'fc_w'), _f32(side['fc_b'], 'fc_b')
+    M, (L, F) = int(pooled.shape[0]), (int(d) for d in fc_w.shape)
+    if out is None:
+        out = torch.empty((M, L), dtype=torch.float32, device=pooled.device)
+    if M:
+        call('r4r_linear_fwd', ptr(pooled), ptr(fc_w), ptr(fc_b), ptr(out), M, F, L, 0)
+    return out
+
+
+def fold_search(kind, head, side_u, side_i, own_u, own_i, target, direction, budget, T, start_u=None, start_i=None,
+                cand_u=None, cand_i=None):
+    """The fewest-review greedy search of include/r4r.h, "Document fold", over the pairs p = (own_u[p], own_i[p]) --
+    indices into the sides' ``ids`` -> (order int32 [n_p, B], scores fp32 [n_p, B + 1], steps int32 [n_p], crossed
+    int32 [n_p]).
+
+    ``side_u`` / ``side_i``: dicts with ptab, conv_b, seg [n, S, F], pool, ids, fc_w, fc_b of the side's tower.
+    ``kind`` / ``head``: ``pair_grad``'s kind and parameters, the per-row ones (q_bias, xu; c_bias, xi) PER PAIR.
+    ``target`` fp32 [n_p]; ``direction`` 0 down / 1 up; ``budget`` 1 .. 64.  ``start_*`` int64 [n_p] (None = 0): the
+    reviews already removed; ``cand_*`` int64 [n_p] (None: the side is not searched): the slots that may be removed,
+    bits at or beyond the side's S ignored.  ``budget`` steps of fixed shape are enqueued -- r4r_fold_search_rows,
+    compose + fc per searched side, one r4r_pair_grad over [the pairs' current rows ; the candidate rows],
+    r4r_fold_search_pick -- and the host reads nothing in between."""
+    if kind not in PAIR_GRAD_KINDS:
+        raise RuntimeError('reviews4rec_amd.ops: fold_search kind must be one of %r, got %r' % (tuple(PAIR_GRAD_KINDS), kind))
+    direction, B, T = int(direction), int(budget), int(T)
+    own_u, own_i = _i64(own_u, 'own_u').reshape(-1), _i64(own_i, 'own_i').reshape(-1)
+    target = _f32(target, 'target').reshape(-1)
+    n_p, dev = int(own_u.numel()), own_u.device
+    if own_i.numel() != n_p or target.numel() != n_p:
+        raise RuntimeError('reviews4rec_amd.ops: fold_search takes equally long own_u, own_i and target, got %d, %d and %d'
+                           % (n_p, own_i.numel(), target.numel()))
+    masks = {}
+    for name, m in (('start_u', start_u), ('start_i', start_i), ('cand_u', cand_u), ('cand_i', cand_i)):
+        if m is not None:
+            m = _i64(m, name).reshape(-1)
+            if m.numel() != n_p:
+                raise RuntimeError('reviews4rec_amd.ops: %s must be [n_p] = [%d], got %d masks' % (name, n_p, m.numel()))
+        masks[name] = m
+    order = torch.empty((n_p, max(B, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((n_p, max(B, 0) + 1), dtype=torch.float32, device=dev)
+    steps = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    crossed = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    done = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    S_u = int(side_u['seg'].shape[1]) if masks['cand_u'] is not None else 0
+    S_i = int(side_i['seg'].shape[1]) if masks['cand_i'] is not None else 0
+    C = S_u + S_i
+    if C == 0:
+        raise RuntimeError('reviews4rec_amd.ops: fold_search needs cand_u or cand_i: no side to search')
+    if n_p == 0:                                                # (the limits are still checked)
+        call('r4r_fold_search_begin', None, None, direction, B, 0, None, None, None, None, None)
+        return order, scores, steps, crossed
+    L = int(side_u['fc_w'].shape[0])
+    rows = n_p + n_p * C
+    pairs = torch.arange(n_p, dtype=torch.int64, device=dev)
+    cols = torch.arange(C, dtype=torch.int64, device=dev)
+    cand_rows = (n_p + pairs[:, None] * C + cols[None, :])
+    every = lambda: pairs[:, None].expand(n_p, C)
+    # the pairs' current rows, then the candidate rows; a side that is not searched keeps the current rows alone
+    idx_u = torch.where(cols[None, :] < S_u, cand_rows, every()).reshape(-1).contiguous()
+    idx_i = torch.where(cols[None, :] >= S_u, cand_rows, every()).reshape(-1).contiguous()
+    z_u = torch.zeros((rows if S_u else n_p, L), dtype=torch.float32, device=dev)
+    z_i = torch.zeros((rows if S_i else n_p, L), dtype=torch.float32, device=dev)
+    spread = lambda t, on: torch.cat([t, t.repeat_interleave(C, 0)]).contiguous() if on else t.contiguous()
+    per_row = {'q_bias': S_u, 'xu': S_u, 'c_bias': S_i, 'xi': S_i}
+    head_c = {k: (spread(v, per_row[k]) if k in per_row and v is not None else v) for k, v in head.items()}
+    mask_u = (masks['start_u'] if masks['start_u'] is not None else torch.zeros(n_p, dtype=torch.int64, device=dev)).clone()
+    mask_i = (masks['start_i'] if masks['start_i'] is not None else torch.zeros(n_p, dtype=torch.int64, device=dev)).clone()
+    fold_latents(side_u, own_u, T, drop=mask_u, out=z_u[:n_p])
+    fold_latents(side_i, own_i, T, drop=mask_i, out=z_i[:n_p])
+    score0 = pair_grad(kind, z_u, z_i, pairs, pairs, want=('score',), **head_c)['score']
+    call('r4r_fold_search_begin', ptr(score0), ptr(target), direction, B, n_p, ptr(order), ptr(scores), ptr(steps),
+         ptr(crossed), ptr(done))
+    i64 = lambda on: torch.empty((n_p, C), dtype=torch.int64, device=dev) if on else None
+    ro_u, dr_u, ro_i, dr_i = i64(S_u), i64(S_u), i64(S_i), i64(S_i)
+    pu, pi = _fold_pool(side_u['pool']), _fold_pool(side_i['pool'])
+    ids_u, ids_i = _i64(side_u['ids'], 'ids').reshape(-1), _i64(side_i['ids'], 'ids').reshape(-1)
+    for _ in range(B):
+        call('r4r_fold_search_rows', ptr(pu[1]), ptr(pu[2]), ptr(ids_u), ptr(own_u), ptr(mask_u), ptr(masks['cand_u']), S_u,
+             ptr(pi[1]), ptr(pi[2]), ptr(ids_i), ptr(own_i), ptr(mask_i), ptr(masks['cand_i']), S_i, ptr(done), n_p, T,
+             ptr(ro_u), ptr(dr_u), ptr(ro_i), ptr(dr_i))
+        if S_u:
+            fold_latents(side_u, ro_u, T, drop=dr_u, out=z_u[n_p:])
+        if S_i:
+            fold_latents(side_i, ro_i, T, drop=dr_i, out=z_i[n_p:])
+        cand_score = pair_grad(kind, z_u, z_i, idx_u, idx_i, want=('score',), **head_c)['score']
+        call('r4r_fold_search_pick', ptr(cand_score), ptr(ro_u), ptr(ro_i), S_u, S_i, ptr(target), direction, B, n_p,
+             ptr(mask_u), ptr(mask_i), ptr(z_u), ptr(z_i), L, ptr(order), ptr(scores), ptr(steps), ptr(crossed), ptr(done))
+    return order, scores, steps, crossed
+
+
 PAIR_GRAD_KINDS = {'fm': 0, 'mlp': 1, 'pfm': 2}              # R4R_PAIR_GRAD_* of include/r4r.h
 PAIR_GRAD_OUTPUTS = ('score', 'g_user', 'g_item', 'w_user', 'w_item')
 _PAIR_GRAD_PARAMS = {'fm': ('V', 'lw'), 'mlp': ('W0', 'b0', 'w3'), 'pfm': ('W0', 'b0', 'W2', 'b2', 'V', 'lw')}

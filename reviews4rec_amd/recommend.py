@@ -1022,8 +1022,11 @@ class Catalogue:
         self.whatif_rows = (len(ru) - bu, len(ri) - bi)          # the variant rows the last pass ran, per side
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
         with torch.no_grad():
-            zu = self._whatif_latents(tower_u, pool_u, ru, du, ou)
-            zi = self._whatif_latents(tower_i, pool_i, ri, di, oi)
+            if self.fold and ou is None and oi is None:     # no occlusion: no document is built, no tower runs
+                zu, zi = self._fold_latents(tower_u, pool_u, ru, du), self._fold_latents(tower_i, pool_i, ri, di)
+            else:
+                zu = self._whatif_latents(tower_u, pool_u, ru, du, ou)
+                zi = self._whatif_latents(tower_i, pool_i, ri, di, oi)
             head = self._pair_head(dev(ru), dev(ri))
             out = torch.empty((n, V + 1), dtype=torch.float32, device=self.dev)
             same = torch.empty((n, V), dtype=torch.bool, device=self.dev)
@@ -1113,6 +1116,131 @@ class Catalogue:
         return DocLeaveOneOut(base, wu, wi, held(S_u) - wu, held(S_i) - wi, dev(live_u), dev(live_i), dev(reach_u),
                               dev(reach_i))
 
+    def _leave_topk_targets(self, u, i, k):
+        """``counterfactual``'s ``k``: per pair the score of the k-th best eligible unseen OTHER item of the user, from
+        ``recommend(users, k + 1)`` over the distinct users; -inf where the user has fewer than k other items."""
+        uu, inv = torch.unique(u, return_inverse=True)
+        items, scores = self.recommend(uu, k + 1)
+        items, scores = items[inv.to(self.dev)], scores[inv.to(self.dev)]
+        other = items != i.to(self.dev)[:, None]               # the item itself steps aside; its place goes to the next
+        place = torch.cumsum(other.to(torch.int64), 1)
+        at = ((place == k) & other).to(torch.int64).argmax(1)
+        has = ((place == k) & other).any(1) & (items.gather(1, at[:, None])[:, 0] >= 0)
+        got = scores.gather(1, at[:, None])[:, 0]
+        return torch.where(has, got, torch.full_like(got, float('-inf'))).contiguous()
+
+    # ------------------------------------------------------------------ the document fold: variants without documents
+    fold = False           # True: what_if / leave_one_out without occlusion go through the fold, not the towers
+
+    def _fold_side(self, tower, pool, own, ptab=None):
+        """What ``ops.fold_latents`` / ``ops.fold_search`` take for one side: the tower's projected table (one
+        r4r_fold_project unless ``ptab`` is handed in) and the interior maxima of the reviews of the DISTINCT owners
+        ``own`` (a host int64 array), S = their largest min(count, 64)."""
+        conv = tower.convs[0]
+        if ptab is None:
+            ptab = ops.fold_project(self._words().detach(), conv.weight.detach())
+        live = np.minimum(pool.first[own + 1] - pool.first[own], WHATIF_MAX_SLOTS)
+        ids = torch.from_numpy(np.ascontiguousarray(own, dtype=np.int64)).to(self.dev)
+        pd = pool.device(self.dev)
+        seg = ops.fold_segments(ptab, conv.bias.detach(), pd, ids, max(1, int(live.max()) if len(own) else 1))
+        return dict(ptab=ptab, conv_b=conv.bias.detach(), seg=seg, pool=pd, ids=ids, fc_w=tower.fc.weight.detach(),
+                    fc_b=tower.fc.bias.detach())
+
+    def _fold_latents(self, tower, pool, row_ids, row_drop):
+        """``_whatif_latents`` without occlusion, by the fold (include/r4r.h, "Document fold"): project, segments over
+        the distinct owners, compose and the tower's fc -> latent [M, L]."""
+        own, inv = np.unique(row_ids, return_inverse=True)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)
+        return ops.fold_latents(self._fold_side(tower, pool, own), dev(inv), int(self.hp['input_length']),
+                                drop=dev(row_drop))
+
+    def review_counterfactual(self, users, items, target=None, k=None, direction='down', side='both', budget=5):
+        """Which reviews would have to be missing from the user's and / or the item's document for the model to stop
+        predicting ``target`` for (users[p], items[p]), and how few are enough?  ``NarreCatalogue.counterfactual``'s
+        greedy search for the families whose towers read one document per owner (deepconn, deepconn++, the TransNets):
+        at each step every review that SHOWS in the current document of the chosen side(s) -- it is not empty and
+        starts before input_length -- is removed in turn (the loader's removal, as ``what_if``: later words slide in),
+        the removal that moves the score furthest in ``direction`` is kept, even when it moves the score the wrong
+        way, and the search ends when the score has passed the target, after ``budget`` removals, or when no such
+        review is left -> ``Counterfactual`` of device tensors, its fields as ``NarreCatalogue.counterfactual``
+        documents them.  Only an owner's first 64 reviews can be removed.
+
+        ``target`` / ``k`` / ``direction`` / ``side``: ``NarreCatalogue.counterfactual``'s, with its checks; ``k`` goes
+        with ``side='item'`` and ``direction='down'`` only.  ``budget``: 1 .. 64.  No document is built and no tower
+        runs: per call one r4r_fold_project per side, per ``pair_batch`` pairs the interior maxima of the distinct
+        owners' reviews (r4r_fold_segments) and ``budget`` steps of fixed shape enqueued without a host read in between
+        (``ops.fold_search``; include/r4r.h, "Document fold").  Every score is ``what_if``'s score of the same removals
+        with ``fold = True``, bit for bit; the results do not depend on the batch.  The greedy answer is an upper bound
+        of the fewest removals, not the minimum.  The engine's pending updates are flushed first; the training state is
+        left untouched."""
+        why = phrase_limits(self.hp)
+        if why is not None:
+            raise RuntimeError('reviews4rec_amd.recommend: ' + why)
+        if side not in ('user', 'item', 'both'):
+            raise ValueError("catalogue: side must be 'user', 'item' or 'both', got %r" % (side,))
+        if direction not in ('up', 'down'):
+            raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
+        if (target is None) == (k is None):
+            raise ValueError('catalogue: counterfactual takes exactly one of target and k, got target = %r and k = %r'
+                             % (target, k))
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= MAX_K - 1:
+                raise ValueError('catalogue: counterfactual k = %r outside 1 .. %d' % (k, MAX_K - 1))
+            if side != 'item' or direction != 'down':
+                raise ValueError("catalogue: counterfactual k goes with side='item' and direction='down' only, got side "
+                                 "= %r, direction = %r: a user's review moves every item's score for that user, so the "
+                                 "top-k list is not a fixed threshold" % (side, direction))
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) \
+                or not 1 <= budget <= ops.FOLD_SEARCH_MAX_BUDGET:
+            raise ValueError('catalogue: counterfactual budget = %r outside 1 .. %d' % (budget, ops.FOLD_SEARCH_MAX_BUDGET))
+        B = int(budget)
+        u, i = self._pair_request(users, items)
+        n = int(u.numel())
+        if target is not None:
+            if torch.is_tensor(target) or isinstance(target, (np.ndarray, list, tuple)):
+                tgt = torch.as_tensor(target).detach().reshape(-1).to(torch.float32).cpu()
+                if tgt.numel() != n:
+                    raise ValueError('catalogue: counterfactual target holds %d values for %d pairs' % (tgt.numel(), n))
+            elif isinstance(target, bool) or not isinstance(target, (int, float, np.integer, np.floating)):
+                raise ValueError('catalogue: counterfactual target must be a float or one float per pair, got %r' % (target,))
+            else:
+                tgt = torch.full((n,), float(target), dtype=torch.float32)
+        self._flush()
+        i64 = lambda *s: torch.full(s, -1, dtype=torch.int64, device=self.dev)
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
+        if n == 0:
+            return Counterfactual(i64(0, B), i64(0, B), i64(0, B), f32(0, B + 1), i64(0), i64(0).to(torch.bool), f32(0), f32(0))
+        tgt = self._leave_topk_targets(u, i, int(k)) if k is not None else tgt.to(self.dev)
+        (pool_u, tower_u, _), (pool_i, tower_i, _) = self._phrase_side('user'), self._phrase_side('item')
+        T = int(self.hp['input_length'])
+
+        def live_bits(pool, ids):                              # the owner's first 64 reviews, one bit each
+            count = np.minimum(pool.first[ids + 1] - pool.first[ids], WHATIF_MAX_SLOTS).astype(np.uint64)
+            bits = np.where(count >= 64, np.uint64(0xFFFFFFFFFFFFFFFF), (np.uint64(1) << np.minimum(count, np.uint64(63))) - np.uint64(1))
+            return torch.from_numpy(bits.view(np.int64)).to(self.dev)
+        with torch.no_grad():
+            words = self._words().detach()
+            ptab_u = ops.fold_project(words, tower_u.convs[0].weight.detach())
+            ptab_i = ops.fold_project(words, tower_i.convs[0].weight.detach())
+            order = torch.empty((n, B), dtype=torch.int32, device=self.dev)
+            scores, steps, crossed = f32(n, B + 1), order.new_empty((n,)), order.new_empty((n,))
+            step = max(1, int(self.pair_batch))
+            for s0 in range(0, n, step):
+                sl = slice(s0, s0 + step)
+                uu, u_inv = np.unique(u[sl].numpy(), return_inverse=True)
+                ui, i_inv = np.unique(i[sl].numpy(), return_inverse=True)
+                dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)
+                order[sl], scores[sl], steps[sl], crossed[sl] = ops.fold_search(
+                    self._pair_kind, self._pair_head(u[sl].to(self.dev), i[sl].to(self.dev)),
+                    self._fold_side(tower_u, pool_u, uu, ptab_u), self._fold_side(tower_i, pool_i, ui, ptab_i),
+                    dev(u_inv), dev(i_inv), tgt[sl].contiguous(), 0 if direction == 'down' else 1, B, T,
+                    cand_u=live_bits(pool_u, u[sl].numpy()) if side in ('user', 'both') else None,
+                    cand_i=live_bits(pool_i, i[sl].numpy()) if side in ('item', 'both') else None)
+            order = order.to(torch.int64)
+            removed = _removed_by_side(order)
+            return Counterfactual(removed[0], removed[1], order, scores, steps.to(torch.int64), crossed != 0,
+                                  scores[:, 0].contiguous(), tgt)
+
     def deletion_curve(self, users, items, k=5, by='pair', side='user', direction='up'):
         """The ``k`` heaviest word windows of one side's document occluded CUMULATIVELY -> ``DocDeletionCurve`` of
         device tensors:
@@ -1182,6 +1310,18 @@ class Catalogue:
         aopc = (gain.sum(1) / live_d.clamp(min=1)).to(torch.float32)
         return DocDeletionCurve(torch.cat([base[:, None], scores], 1).contiguous(), aopc,
                                 torch.from_numpy(pos.astype(np.int32)).to(self.dev), live_d)
+
+
+def _removed_by_side(order):
+    """A search's ``order`` int64 [n, B] (user slots, 64 + item slots, fill -1) -> [removed_user, removed_item], each
+    side's steps moved to the front in step sequence, fill -1."""
+    removed = []
+    for lo in (0, ops.NARRE_SEARCH_ITEM):
+        mine = (order >= lo) & (order < lo + ops.NARRE_SEARCH_ITEM)
+        vals = torch.where(mine, order - lo, torch.full_like(order, -1))
+        front = torch.sort((~mine).to(torch.int64), dim=1, stable=True).indices
+        removed.append(vals.gather(1, front).contiguous())
+    return removed
 
 
 def _drop_masks(drop, count, what):
@@ -2028,18 +2168,11 @@ class NarreCatalogue(Catalogue):
                              torch.where(valid, order, torch.full_like(order, -1)), live)
 
     # ------------------------------------------------------------------ counterfactuals: the fewest reviews that flip a score
-    def _leave_topk_targets(self, u, i, k):
-        """``counterfactual``'s ``k``: per pair the score of the k-th best eligible unseen OTHER item of the user, from
-        ``recommend(users, k + 1)`` over the distinct users; -inf where the user has fewer than k other items."""
-        uu, inv = torch.unique(u, return_inverse=True)
-        items, scores = self.recommend(uu, k + 1)
-        items, scores = items[inv.to(self.dev)], scores[inv.to(self.dev)]
-        other = items != i.to(self.dev)[:, None]               # the item itself steps aside; its place goes to the next
-        place = torch.cumsum(other.to(torch.int64), 1)
-        at = ((place == k) & other).to(torch.int64).argmax(1)
-        has = ((place == k) & other).any(1) & (items.gather(1, at[:, None])[:, 0] >= 0)
-        got = scores.gather(1, at[:, None])[:, 0]
-        return torch.where(has, got, torch.full_like(got, float('-inf'))).contiguous()
+    def review_counterfactual(self, *args, **kw):
+        """Refused: NARRE reads its reviews one by one and a removal re-selects slots; its search is ``counterfactual``."""
+        raise RuntimeError('reviews4rec_amd.recommend: review_counterfactual folds the one document of a deepconn / '
+                           'deepconn++ / transnet tower; NARRE reads its reviews one by one: use '
+                           'NarreCatalogue.counterfactual')
 
     def counterfactual(self, users, items, target=None, k=None, direction='down', side='both', budget=None, slide=True):
         """Which reviews would have to be missing for the model to stop predicting ``target`` for (users[p], items[p]),
@@ -2152,12 +2285,7 @@ class NarreCatalogue(Catalogue):
                     su, si, part(u_inv), part(i_inv), W1, b1, w, part(tgt), 0 if direction == 'down' else 1, B,
                     cand_u=part(cand_u), cand_i=part(cand_i), q_bias=qb, c_bias=cb)
             order = order.to(torch.int64)
-            removed = []
-            for lo in (0, ops.NARRE_SEARCH_ITEM):              # a side's steps, moved to the front in step sequence
-                mine = (order >= lo) & (order < lo + ops.NARRE_SEARCH_ITEM)
-                vals = torch.where(mine, order - lo, torch.full_like(order, -1))
-                front = torch.sort((~mine).to(torch.int64), dim=1, stable=True).indices
-                removed.append(vals.gather(1, front).contiguous())
+            removed = _removed_by_side(order)
             return Counterfactual(removed[0], removed[1], order, scores, steps.to(torch.int64), crossed != 0,
                                   scores[:, 0].contiguous(), tgt)
 
