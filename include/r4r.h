@@ -1850,6 +1850,71 @@ int r4r_narre_search(const float *z_u, const float *logit_u, const float *own_u,
                      void *stream);
 
 /* ------------------------------------------------------------------------
+ * NARRE Shapley values: how much of a pair's eval-mode rating each review carries, as the exact Shapley value of the game
+ * "which of the players' reviews are present" (csrc/narre_shapley.hip).  A review enters NARRE's score only through its
+ * own latent and its own attention logit (NARRE.attention, NARRE.py:53-64; the head of NARRE.py:38-46, 115-124), and an
+ * absent review is the loader's own removal (`skip`, data.py:144-172 for the reviews, data.py:275-279 for the neighbour
+ * ids), so a coalition is one variant of "NARRE what-if scores": no tower runs, the owner pass (r4r_narre_logits) is
+ * paid once.  No mask and no score of a coalition goes through memory unless out_values asks for the scores.
+ *
+ * r4r_narre_shapley -- one wave per (pair, 1,024 coalitions).  Per side exactly r4r_narre_whatif's block: z [n, S, L],
+ *   logit [n, S], own [n, L] or NULL, z_pad [L], logit_pad, S, R with 1 <= R <= S <= 64; u_idx, i_idx [n_p]; q_bias, c_bias
+ *   (NULL = 0); W1, b1, w; 1 <= L <= 64.
+ *   start_u, start_i [n_p] int64 (NULL = 0): the slots removed in EVERY coalition; bits >= S are ignored (as in
+ *                    r4r_narre_search).
+ *   play_u, play_i   [n_p] int64 (NULL = no player on that side): the players; bits >= S and bits that are also in start
+ *                    are ignored.  Player numbers t = 0 .. n - 1 run over the user side's player slots ascending, then
+ *                    the item side's.
+ *   P, 1 <= P <= 16: the most players of a pair; a pair with more set bits plays its lowest-numbered P.  out_n returns
+ *                    the count played.
+ *   Coalition c in [0, 2^n) has bit t set when player t is PRESENT; its masks are start | (the players whose bit in c is
+ *   clear) on each side, and its value v(c) is r4r_narre_whatif's out_score of the pair under those two masks, bit for
+ *   bit -- the list, a', o', p', x, the v_mfma_f32_16x16x4_f32 chain, the epilogue and (head + q_bias[u]) + c_bias[i] of
+ *   that section, through the same calls (csrc/narre_variant_device.h's variant_pooled and variant_head).  v(2^n - 1) is
+ *   the pair's score under start alone.
+ *   phi_t = sum over c of coef_t(c) (v(c) - v(2^n - 1)), coef_t(c) = (k - 1)! (n - k)! / n! for t in c and
+ *   -k! (n - k - 1)! / n! for t not in c, k = |c|  (the coefficients of a player sum to 0, so the centre changes nothing
+ *   but the rounding: the terms are of the size of the effects, not of the ratings).
+ *   The accumulation, to the rounding.  The n distinct weights a_k = 1 / (n C(n - 1, k - 1)), k = 1 .. n, are formed in
+ *   float64 (the product an exact integer, one division) and rounded to fp32 once; coef_t(c) is a_k for t in c and
+ *   -a_(k+1) for t not in c (0 at k = n).  The coalitions are cut into chunks of 1,024 consecutive numbers (one chunk
+ *   when n <= 10).  Within a chunk, lane j of 0 .. 15 takes the coalitions c = j (mod 16) in ascending order and chains
+ *   s = fma((double)coef_t(c), (double)v(c) - (double)v(2^n - 1), s) in float64 from 0.0 (the difference of two floats
+ *   in float64; one rounding per fma); the 16 lane sums are added in float64 by four xor butterflies, s_j + s_(j^1),
+ *   then ^2, ^4, ^8.  The chunk sums are chained in float64 in ascending chunk order from 0.0, and the total is rounded
+ *   to fp32 once.  A pair's outputs depend on that pair's inputs alone: not on n_p, the grid, P (beyond truncation),
+ *   out_values or which pairs share the call.  No float atomics.
+ *   out_phi_u [n_p, S_u], out_phi_i [n_p, S_i]  float: phi by slot, +0.0f at every slot that is not a player; either may
+ *                    be NULL when its play is NULL
+ *   out_base  [n_p] float   v(2^n - 1)       out_empty [n_p] float   v(0)       out_n [n_p] int32   the players played
+ *   out_values [n_p, 2^P] float, nullable: entries 0 .. 2^n - 1 hold v(c); the rest are not written
+ *   scratch   n_p 2^(P - 10) P doubles when P > 10 (the chunk sums; a second small launch adds them), unused and
+ *                    nullable when P <= 10.  Its contents after the call mean nothing.
+ *   A pair with n = 0 costs one variant: phi is all zeros and out_base = out_empty.  In a one-side game the other side's
+ *   pooled vector is computed once per wave, in a two-side game the item side's once per 2^n_u coalitions.
+ *   Limits: 1 <= L <= 64, 1 <= P <= 16, n_u, n_i >= 0, 0 <= n_p < 2^31, with out_values n_p 2^P < 2^31.  Refused before
+ *   the launch and the first dereference, in the entry point's own name: a limit; with n_p > 0 a null z, logit, z_pad of
+ *   either side, u_idx, i_idx, W1, b1, w, out_base, out_empty or out_n, a null out_phi of a side whose play is given, a
+ *   null scratch with P > 10, and n_u or n_i == 0.  n_p == 0 returns R4R_OK and enqueues nothing.  An index outside
+ *   [0, n_u) / [0, n_i) is the caller's error.  One launch (two with P > 10); nothing allocates, nothing synchronises.
+ * ---------------------------------------------------------------------- */
+int r4r_narre_shapley(const float *z_u, const float *logit_u, const float *own_u, const float *z_pad_u, float logit_pad_u,
+                      int64_t n_u, int S_u, int R_u,         /* [n_u, S_u, L], [n_u, S_u], [n_u, L] or NULL, [L]      */
+                      const float *z_i, const float *logit_i, const float *own_i, const float *z_pad_i, float logit_pad_i,
+                      int64_t n_i, int S_i, int R_i,         /* the item side likewise                                */
+                      const int64_t *u_idx, const int64_t *i_idx,             /* [n_p] rows of the sides              */
+                      const int64_t *start_u, const int64_t *start_i,         /* [n_p] bit masks; NULL = 0            */
+                      const int64_t *play_u, const int64_t *play_i,           /* [n_p] bit masks; NULL = 0            */
+                      int P, int64_t n_p,                                     /* 1 .. 16                              */
+                      const float *q_bias, const float *c_bias,               /* [n_u], [n_i]; NULL = 0               */
+                      const float *W1, const float *b1, const float *w, int L,/* [L, L], [L], [L]                     */
+                      float *out_phi_u, float *out_phi_i,                     /* [n_p, S_u], [n_p, S_i]; nullable     */
+                      float *out_base, float *out_empty, int32_t *out_n,      /* [n_p] each                           */
+                      float *out_values,                                      /* [n_p, 2^P], nullable                 */
+                      double *scratch,                                        /* n_p 2^(P - 10) P doubles, P > 10     */
+                      void *stream);
+
+/* ------------------------------------------------------------------------
  * What-if documents: the single-document families' tower over VARIANTS of an owner's document -- chosen reviews taken
  * away, chosen positions occluded -- from the resident pools (csrc/tower_variants.hip, csrc/docs_masked_device.h).
  * Replaces  the loader's `skip`: a training rating's documents leave the rating's own review out of both sides

@@ -50,5 +50,6 @@ from .recommend import PairPhrases, check_explain_pairs_request, write_pair_phra
 from .recommend import PairReviews  # noqa: E402,F401
 from .recommend import DeletionCurve, LeaveOneOut, WhatIf  # noqa: E402,F401
 from .recommend import Counterfactual  # noqa: E402,F401
+from .recommend import Shapley  # noqa: E402,F401
 from .recommend import DocDeletionCurve, DocLeaveOneOut, check_explain_reviews_request, write_pair_reviews  # noqa: E402,F401
 from .eval import eval_catalogue, eval_sampled  # noqa: E402,F401

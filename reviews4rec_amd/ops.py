@@ -1106,6 +1106,55 @@ def narre_search(user, item, u_idx, i_idx, W1, b1, w, target, direction, budget,
     return order, scores, steps, crossed
 
 
+NARRE_SHAPLEY_MAX_PLAYERS = 16      # r4r_narre_shapley: players of one pair (2^16 coalitions)
+NARRE_SHAPLEY_CHUNK_LOG = 10        # a pair's coalitions go 2^10 to a wave; beyond, the chunk sums pass through scratch
+
+
+def narre_shapley(user, item, u_idx, i_idx, W1, b1, w, play_u=None, play_i=None, start_u=None, start_i=None, P=None,
+                  q_bias=None, c_bias=None, values=False):
+    """r4r_narre_shapley (include/r4r.h, "NARRE Shapley values"): per pair, the exact Shapley value of every playing
+    review in the game "which of the players' reviews are present", whole on the device.  ``user`` / ``item``:
+    ``narre_whatif``'s side dicts.  ``play_u`` / ``play_i``: int64 [n_p] masks of the slots that play (None = none on that
+    side); ``start_u`` / ``start_i``: int64 [n_p] masks of the slots removed in every coalition (None = none).  ``P``:
+    1 .. 16, the most players of a pair (a pair with more plays its lowest-numbered P: ``n`` tells); None = the most any
+    pair of the call has, which reads the masks back to the host.  ``values=True`` also returns every coalition's score.
+    No autograd -> (phi_u float32 [n_p, S_u], phi_i float32 [n_p, S_i], base float32 [n_p], empty float32 [n_p],
+    n int32 [n_p], values float32 [n_p, 2^P] or None); only the first 2^n[p] entries of ``values[p]`` are written."""
+    n_p, dev, head, tail, keep = _narre_variant_args('narre_shapley', user, item, u_idx, i_idx, W1, b1, w, q_bias, c_bias)
+    S_u, S_i = int(keep[5]['z'].shape[1]), int(keep[6]['z'].shape[1])
+    masks = []
+    for name, m in (('start_u', start_u), ('start_i', start_i), ('play_u', play_u), ('play_i', play_i)):
+        if m is not None:
+            m = _i64(m, name).reshape(-1)
+            if m.numel() != n_p:
+                raise RuntimeError('reviews4rec_amd.ops: narre_shapley %s must be [%d], got %s' % (name, n_p, tuple(m.shape)))
+        masks.append(m)
+    if P is None:
+        most = 0
+        if n_p:
+            count = torch.zeros(n_p, dtype=torch.int64, device=dev)
+            for play, start, S in ((masks[2], masks[0], S_u), (masks[3], masks[1], S_i)):
+                if play is not None:
+                    live = play if start is None else play & ~start
+                    count += ((live[:, None] >> torch.arange(S, device=dev)[None, :]) & 1).sum(1)
+            most = int(count.max())
+        P = min(max(most, 1), NARRE_SHAPLEY_MAX_PLAYERS)
+    if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= NARRE_SHAPLEY_MAX_PLAYERS:
+        raise RuntimeError('reviews4rec_amd.ops: narre_shapley P = %r outside 1 .. %d' % (P, NARRE_SHAPLEY_MAX_PLAYERS))
+    if values and n_p << P >= 1 << 31:
+        raise RuntimeError('reviews4rec_amd.ops: narre_shapley values of %d pairs x 2^%d coalitions pass 2^31 - 1' % (n_p, P))
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    phi_u, phi_i, base, empty = f32(n_p, S_u), f32(n_p, S_i), f32(n_p), f32(n_p)
+    n = torch.empty((n_p,), dtype=torch.int32, device=dev)
+    vals = f32(n_p, 1 << P) if values else None
+    scratch = None
+    if P > NARRE_SHAPLEY_CHUNK_LOG:
+        scratch = torch.empty((n_p, 1 << (P - NARRE_SHAPLEY_CHUNK_LOG), P), dtype=torch.float64, device=dev)
+    call('r4r_narre_shapley', *head, *(ptr(m) for m in masks), P, n_p, *tail, ptr(phi_u), ptr(phi_i), ptr(base),
+         ptr(empty), ptr(n), ptr(vals), ptr(scratch))
+    return phi_u, phi_i, base, empty, n, vals
+
+
 class TransformLoss(Function):
     """mean_n ||a_n - b_n||^2 (TransNet's source/target representation loss)."""
 

@@ -1154,6 +1154,14 @@ class Catalogue:
         return ops.fold_latents(self._fold_side(tower, pool, own), dev(inv), int(self.hp['input_length']),
                                 drop=dev(row_drop))
 
+    def shapley(self, *args, **kw):
+        """Refused: exact Shapley values are ``NarreCatalogue.shapley``'s.  NARRE reads its reviews one by one, so a
+        coalition of reviews is a re-selection of slots; here a coalition is a new document and a tower forward."""
+        raise RuntimeError('reviews4rec_amd.recommend: shapley needs the score of every coalition of reviews; model_type '
+                           '%r reads one document per owner, so a coalition there is a new document and a tower forward '
+                           '(2^n of them per pair): use leave_one_out. NarreCatalogue.shapley is exact because a NARRE '
+                           'review enters the score through its own latent and logit alone' % (self.hp.get('model_type'),))
+
     def review_counterfactual(self, users, items, target=None, k=None, direction='down', side='both', budget=5):
         """Which reviews would have to be missing from the user's and / or the item's document for the model to stop
         predicting ``target`` for (users[p], items[p]), and how few are enough?  ``NarreCatalogue.counterfactual``'s
@@ -1415,6 +1423,7 @@ WhatIf = namedtuple('WhatIf', 'scores base')                                    
 LeaveOneOut = namedtuple('LeaveOneOut', 'base without_user without_item delta_user delta_item live_user live_item')
 DeletionCurve = namedtuple('DeletionCurve', 'scores aopc order live')           # NarreCatalogue.deletion_curve
 Counterfactual = namedtuple('Counterfactual', 'removed_user removed_item order scores steps crossed base target')  # NarreCatalogue.counterfactual
+Shapley = namedtuple('Shapley', 'phi_user phi_item base empty_user empty_item live_user live_item values')  # NarreCatalogue.shapley
 DocLeaveOneOut = namedtuple('DocLeaveOneOut', LeaveOneOut._fields + ('reach_user', 'reach_item'))   # Catalogue.leave_one_out
 DocDeletionCurve = namedtuple('DocDeletionCurve', 'scores aopc positions live')                    # Catalogue.deletion_curve
 WHATIF_MAX_SLOTS = 64               # r4r_narre_whatif, r4r_tower_build_variants: one bit of an int64 mask per slot
@@ -2119,8 +2128,9 @@ class NarreCatalogue(Catalogue):
             order   int64 [n, R]        the slots in removal order; -1 beyond ``live``
             live    int64 [n]           min(number of reviews, R)
 
-        ``by``: 'rev' -- ``pair_reviews``' gradient x input of the side; 'attention' -- ``explain``'s weights; or a
-        float tensor [n, R] of your own.  ``direction`` 'up' removes the largest key first, 'down' the smallest; ties go
+        ``by``: 'rev' -- ``pair_reviews``' gradient x input of the side; 'attention' -- ``explain``'s weights;
+        'shapley' -- ``shapley``'s ``phi`` of the side's one-side game, with the same ``slide``; or a float tensor
+        [n, R] of your own.  ``direction`` 'up' removes the largest key first, 'down' the smallest; ties go
         to the ascending slot.  ``side``: 'user' or 'item'; the other side keeps every review.  ``slide``: as
         ``what_if``.  Refused before anything is enqueued: a bad ``by`` / ``side`` / ``direction`` (ValueError), unequal
         lengths (ValueError), an id outside its side's pool (KeyError)."""
@@ -2130,8 +2140,8 @@ class NarreCatalogue(Catalogue):
             raise ValueError("catalogue: direction must be 'up' or 'down', got %r" % (direction,))
         R = int(self.hp['narre_num_reviews'])
         named = isinstance(by, str)
-        if named and by not in ('rev', 'attention'):
-            raise ValueError("catalogue: by must be 'rev', 'attention' or a tensor [n, %d], got %r" % (R, by))
+        if named and by not in ('rev', 'attention', 'shapley'):
+            raise ValueError("catalogue: by must be 'rev', 'attention', 'shapley' or a tensor [n, %d], got %r" % (R, by))
         u, i = self._pair_request(users, items)
         n = int(u.numel())
         if not named:
@@ -2146,6 +2156,8 @@ class NarreCatalogue(Catalogue):
         live = torch.from_numpy(np.minimum(count, R).astype(np.int64)).to(self.dev)
         if named and n and by == 'rev':
             key = getattr(self._pair_reviews(u, i), 'rev_' + side)
+        elif named and by == 'shapley':                        # the side's one-side game, with the same slide
+            key = getattr(self.shapley(u, i, side=side, slide=slide), 'phi_' + side)
         elif named and n:                                      # the DISTINCT owners' attention, handed to their pairs
             distinct, inverse = torch.unique(ids, return_inverse=True)
             key = self.explain(distinct, k=1, side=side).attention[inverse.to(self.dev)]
@@ -2288,6 +2300,112 @@ class NarreCatalogue(Catalogue):
             removed = _removed_by_side(order)
             return Counterfactual(removed[0], removed[1], order, scores, steps.to(torch.int64), crossed != 0,
                                   scores[:, 0].contiguous(), tgt)
+
+    # ------------------------------------------------------------------ attributions: exact Shapley values of the reviews
+    def shapley(self, users, items, side='both', joint=False, slide=True, values=False):
+        """How much of the prediction for (users[p], items[p]) does each attended review carry?  The exact Shapley value
+        of the game "which of these reviews are present": the one share-out that is efficient (the shares add up to
+        what the reviews carry together), symmetric and exact -- ``leave_one_out`` double-counts redundant reviews and
+        misses those that matter only once another is gone -> ``Shapley`` of device tensors, n = len(users):
+
+            phi_user, phi_item      float32 [n, R]  review r's share of THIS pair's score; exactly 0 at a slot that holds
+                                                    no review and on a side that does not play
+            base                    float32 [n]     the prediction with nothing removed (``what_if``'s ``base``)
+            empty_user, empty_item  float32 [n]     the prediction with every player of that side's game removed:
+                                                    sum(phi_user) = base - empty_user up to the rounding (``base`` on a
+                                                    side that does not play; with ``joint`` both hold the score with
+                                                    both sides' reviews removed)
+            live_user, live_item    int64 [n]       ``explain``'s ``live``: min(number of reviews, R)
+            values                  None, or with ``values=True`` (user game's table, item game's table): float32
+                                                    [n, 2^P] each (None for a side that does not play; with ``joint``
+                                                    the one table twice), P the most players of any pair: entry c of
+                                                    row p is the prediction with exactly the players whose bit in c is
+                                                    set PRESENT (player t: the game's t-th live review, the user's
+                                                    first in a joint game); entries from 2^(the pair's players) on are
+                                                    not written
+
+        The players are the pair's live reviews among the first R slots: the reviews the model attends with nothing
+        removed.  ``side``: 'user' / 'item' plays one game with the other side intact; 'both' plays the two one-side
+        games.  ``joint=True`` plays ONE game over both sides' reviews (``side`` must be 'both').  A game takes at most
+        16 players: more on any pair is refused.  ``slide=True`` is the loader's removal -- each played side reaches
+        S = min(64, R + its players) reviews of its owners, as ``what_if`` does; ``slide=False`` is occlusion, S = R.
+
+        The DISTINCT owners go once through the towers and r4r_narre_logits; the pairs go ``pair_batch`` at a time
+        through r4r_narre_shapley (include/r4r.h, "NARRE Shapley values"; the results do not depend on the batch).
+        Every coalition's score is ``what_if``'s score of the same removals, bit for bit.  The score's scalars are summed
+        in float64 and rounded once.  Before anything is enqueued: a bad ``side``, ``joint`` with one side, unequal
+        lengths and a game of more than 16 players raise ValueError, an id outside its side's pool KeyError.  The
+        engine's pending updates are flushed first; the training state is left untouched."""
+        if side not in ('user', 'item', 'both'):
+            raise ValueError("catalogue: side must be 'user', 'item' or 'both', got %r" % (side,))
+        if joint and side != 'both':
+            raise ValueError("catalogue: shapley joint=True plays one game over both sides: side must be 'both', got %r"
+                             % (side,))
+        R = int(self.hp['narre_num_reviews'])
+        u, i = self._pair_request(users, items)
+        n = int(u.numel())
+        on_u, on_i = side in ('user', 'both'), side in ('item', 'both')
+        uu, u_inv = torch.unique(u, return_inverse=True)
+        ui, i_inv = torch.unique(i, return_inverse=True)
+
+        def live_of(which, ids):                               # min(number of reviews, R) of the DISTINCT owners
+            pool = self._narre_side(which)[1]
+            return np.minimum(pool.first[ids.numpy() + 1] - pool.first[ids.numpy()], R).astype(np.int64)
+        live_u, live_i = live_of('user', uu), live_of('item', ui)
+        most_u = int(live_u.max()) if (n and on_u) else 0
+        most_i = int(live_i.max()) if (n and on_i) else 0
+        most = int((live_u[u_inv.numpy()] + live_i[i_inv.numpy()]).max()) if (n and joint) else max(most_u, most_i)
+        if most > ops.NARRE_SHAPLEY_MAX_PLAYERS:
+            raise ValueError('catalogue: shapley takes at most %d players a game; the largest of this request has %d%s'
+                             % (ops.NARRE_SHAPLEY_MAX_PLAYERS, most, ' (joint=True counts both sides)' if joint else ''))
+        self._flush()
+        m = self.model
+        f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=self.dev)
+        if n == 0:
+            i64 = torch.empty((0,), dtype=torch.int64, device=self.dev)
+            table = lambda on: f32(0, 2) if on else None
+            return Shapley(f32(0, R), f32(0, R), f32(0), f32(0), f32(0), i64, i64.clone(),
+                           (table(on_u), table(on_i)) if values else None)
+        slots = lambda players: min(WHATIF_MAX_SLOTS, R + players) if slide else R
+        bits = lambda live, inv: torch.from_numpy((np.int64(1) << live) - 1).to(self.dev)[inv]
+        with torch.no_grad():
+            su = self._whatif_side('user', uu.numpy(), slots(most_u))
+            si = self._whatif_side('item', ui.numpy(), slots(most_i))
+            f64 = lambda t: t.detach().to(torch.float64)
+            qb = (f64(m.user_bias).reshape(-1)[uu.to(self.dev)] + f64(m.global_bias).reshape(())
+                  + f64(m.final[3].bias).reshape(())).to(torch.float32).contiguous()
+            cb = m.item_bias.detach().reshape(-1)[ui.to(self.dev)].to(torch.float32).contiguous()
+            W1, b1, w = m.final[1].weight.detach(), m.final[1].bias.detach(), m.final[3].weight.detach().reshape(-1)
+            u_inv, i_inv = u_inv.to(self.dev), i_inv.to(self.dev)
+            play_u, play_i = bits(live_u, u_inv), bits(live_i, i_inv)
+            # the games: (the user side's players, the item side's, the most players of a pair)
+            games = ([(play_u, play_i, most)] if joint else
+                     ([(play_u, None, most_u)] if on_u else []) + ([(None, play_i, most_i)] if on_i else []))
+            zero = torch.zeros((n, R), dtype=torch.float32, device=self.dev)
+            phi = [zero, zero.clone()]
+            base, empty, tables = f32(n), [None, None], [None, None]
+            step = max(1, int(self.pair_batch))
+            for pu, pi, players in games:
+                P = max(players, 1)
+                g_phi = [f32(n, R) if pl is not None else None for pl in (pu, pi)]
+                g_empty, g_table = f32(n), f32(n, 1 << P) if values else None
+                for s0 in range(0, n, step):
+                    sl = slice(s0, s0 + step)
+                    part = lambda t: None if t is None else t[sl].contiguous()
+                    got = ops.narre_shapley(su, si, part(u_inv), part(i_inv), W1, b1, w, play_u=part(pu), play_i=part(pi),
+                                            P=P, q_bias=qb, c_bias=cb, values=values)
+                    for k in (0, 1):
+                        if g_phi[k] is not None:
+                            g_phi[k][sl] = got[k][:, :R]
+                    base[sl], g_empty[sl] = got[2], got[3]
+                    if values:
+                        g_table[sl] = got[5]
+                for k, pl in enumerate((pu, pi)):
+                    if pl is not None:
+                        phi[k], empty[k], tables[k] = g_phi[k], g_empty, g_table
+            empty = [base if e is None else e for e in empty]
+            return Shapley(phi[0], phi[1], base, empty[0], empty[1], su['live'][u_inv], si['live'][i_inv],
+                           tuple(tables) if values else None)
 
     def explain_words(self, ids, k=5, side='item', weights=None, reviews=None):
         """``Catalogue.explain_words`` per REVIEW: NARRE's towers read an owner's first R reviews one by one
